@@ -7,14 +7,21 @@ A "step" is one full pass of the hot path over the workload: every image pair of
 through libamc.so's amc_match_pairs (match kernel -> finalize -> match tables on the host), with
 descriptors already resident in HBM when the timed region starts.
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1            # the headline alone
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full     # the headline and every other leg below
     python bench.py --gpus N --steps K --warmup W            # N > 1: launches itself under torch.distributed.run
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W [--config 3|4 | --weak]
 
+A plain run sets up, warms up, times the K steps of the headline and prints its line (with the roofline of the timed
+steps).  --full adds everything else the line has carried: the CPU baselines, the configs[3] / configs[4] legs and,
+at N=1, the legs listed below.  --dump-outputs DIR writes the match table the last timed step left its caller (offsets
+and rows; at N>1 the exchanged table of all pairs) as DIR/*.npy; the inputs are seeded, so two builds can be compared
+output for output.
+
 --config 1 (default at N=1): BASELINE.json configs[1] (500 x 4096, 124,750 pairs, 2.09e12 distances).  With N>1 it
   is only run on request (--weak): weak scaling - the image set grows as 500*sqrt(N) so every rank matches ~124,750
-  pairs of one replicated descriptor arena.  At N=1 the JSON line also carries
+  pairs of one replicated descriptor arena.  At N=1 with --full the JSON line also carries
     "verify"   BASELINE's second metric, verified image-pairs/s, with its own FP64 roofline and CPU baseline,
     "pipeline" configs[2] as stated: match + F/E/H verification of the same image set, chained on the device
                (amc_match_verify_pairs) on a scene with real geometry,
@@ -696,6 +703,7 @@ class _DryRunContext:
 
     def __init__(self):
         self.imgs = {}
+        self.match_calls = 0
 
     def set_stream(self, stream):
         pass
@@ -709,6 +717,7 @@ class _DryRunContext:
     def match_pairs(self, s1, s2, kernel="auto", cross_check=True, copy=True):
         sys.path.insert(0, str(ROOT / "tests"))
         import oracle_lib
+        self.match_calls += 1
         used = np.unique(np.concatenate([np.asarray(s1, np.int64), np.asarray(s2, np.int64)])) if len(s1) else np.zeros(0, np.int64)
         remap = {int(u): k for k, u in enumerate(used)}
         imgs = [self.imgs[int(u)] for u in used]
@@ -802,7 +811,46 @@ def spot_check(get_image, s1, s2, off, m, sample: int = 6, seed: int = 99):
     return {"gpu_vs_oracle_mismatching_pairs": int(mism), "pairs_checked": int(len(idx))}
 
 
-def config34_leg(args, config: int, steps: int, warmup: int, dist_state):
+DUMP_BUDGET_BYTES = 64_000_000     # all files of one dump, .npy headers included
+NPY_HEADER_BYTES = 4096            # an upper bound per file (np.save writes 128 bytes for these shapes)
+
+
+def dump_outputs(out_dir, off, m, seed: int = 0):
+    """--dump-outputs: the match table a caller of the timed step holds after it, written as DIR/match_offsets.npy
+    (float64, pairs + 1: pair p's rows are [off[p], off[p + 1])) and DIR/matches.npy (float32, rows x 2: feature index
+    in image 1, in image 2).  Exact in those types (offsets < 2^53, indices < 2^24).  A table that would take more than
+    DUMP_BUDGET_BYTES is cut to a seeded sample of its pairs - the longest prefix of one fixed permutation of the pair
+    indices that fits - and DIR/sampled_pairs.npy (float64) names them."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    off = np.asarray(off).astype(np.int64)
+    m = np.asarray(m).reshape(-1, 2)
+    counts = np.diff(off)
+    rows_bytes = counts * 2 * 4
+    if 2 * NPY_HEADER_BYTES + off.size * 8 + int(rows_bytes.sum()) > DUMP_BUDGET_BYTES:
+        room = DUMP_BUDGET_BYTES - 3 * NPY_HEADER_BYTES - 8        # three files; the leading 0 of the offsets
+        order = np.random.default_rng(seed).permutation(len(counts))
+        k = int(np.searchsorted(np.cumsum(rows_bytes[order] + 16), room, side="right"))
+        pick = np.sort(order[:k])
+        m = np.concatenate([m[off[p]:off[p + 1]] for p in pick]) if k else m[:0]
+        off = np.concatenate([[0], np.cumsum(counts[pick])])
+        np.save(d / "sampled_pairs.npy", pick.astype(np.float64))
+    assert m.size == 0 or int(m.max()) < (1 << 24), "feature indices beyond float32's exact range"
+    np.save(d / "match_offsets.npy", off.astype(np.float64))
+    np.save(d / "matches.npy", m.astype(np.float32))
+
+
+def dumped_table(mine, off, m, use_dist: bool, device, comm):
+    """The match table a caller of the timed step holds after it: with one rank the call's own; with more, what the
+    exchange hands out - every rank's pairs in the global order - gathered once more for this purpose, outside the
+    timed region, onto rank 0 (collective: every rank calls it; the others get (None, None))."""
+    if not use_dist:
+        return off, m
+    from pycolmap_amd import distributed as D
+    return D.all_gather_match_tables(mine, off, m, device=device, as_numpy=True, download_rank=0, comm=comm)
+
+
+def config34_leg(args, config: int, steps: int, warmup: int, dist_state, dump_dir=None):
     """BASELINE configs[3] (2000 x 8192 exhaustive) and configs[4] (10000 x 4096 sequential + loop): a FIXED
     workload whose pairs are sharded over the ranks by work (sum of n1 * n2), the descriptor arena replicated on
     every GPU, one all-gather of the match tables at the end of every step (inside the timed region) - through the
@@ -969,6 +1017,10 @@ def config34_leg(args, config: int, steps: int, warmup: int, dist_state):
         nd += d_; kms += k_; kl += l_
     fence()
     elapsed = time.perf_counter() - t0
+    if dump_dir and last_tab is not None:          # (configs[4]: the sequential pairs' table)
+        g_off, g_m = dumped_table(mine, last_tab[0], last_tab[1], use_dist, device, comm)
+        if rank == 0:
+            dump_outputs(dump_dir, g_off, g_m)
     nd_rank = nd
     kernel_ms_by_rank = [kms / max(args.steps, 1)]
     exch_ms_by_rank = [exch["ms"] / max(args.steps, 1)]
@@ -1148,7 +1200,7 @@ def run_config34(args):
     """`--config 3 | 4`: that configuration alone, as the line."""
     import torch.distributed as dist
     state = dist_setup(args)
-    out = config34_leg(args, args.config, args.steps, args.warmup, state)
+    out = config34_leg(args, args.config, args.steps, args.warmup, state, dump_dir=args.dump_outputs)
     if state[4]:
         dist.barrier()
         dist.destroy_process_group()
@@ -1214,6 +1266,13 @@ def main():
     ap.add_argument("--no-config3", action="store_true", help="skip the configs[3] strong-scaling leg of the default line")
     ap.add_argument("--config3-steps", type=int, default=0,
                     help="timed steps of the configs[3] leg (0 = one at N=1, where a step is ~11 s, two at N>1)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run everything else the line reports: CPU baselines, the configs[3] / "
+                         "configs[4] legs and, at N=1, the verify / pipeline / ragged / sift_stats / dense / db legs (the "
+                         "--no-* options above switch single legs off).  Off: the headline alone")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the match table the last timed step left its caller (offsets and rows; with N > 1 ranks "
+                         "the exchanged table of all pairs) to DIR/*.npy")
     args = ap.parse_args()
     if args.config is None:
         args.config = 1
@@ -1282,6 +1341,7 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
+    calls_before = ctx.match_calls if dry else 0
     t0 = time.perf_counter()
     kern_ms, kern_launches, ndist_local, last = 0.0, 0, 0, None
     for _ in range(args.steps):
@@ -1291,6 +1351,7 @@ def main():
         ndist_local = last[2]["num_distances"]
     fence()
     elapsed = time.perf_counter() - t0
+    timed_calls = ctx.match_calls - calls_before if dry else None
     if use_dist:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1301,15 +1362,19 @@ def main():
     else:
         ndist_total = float(ndist_local)
     headline_gather_path = D.last_gather_path() if use_dist else None
+    if args.dump_outputs:
+        g_off, g_m = dumped_table(mine, last[0], last[1], use_dist, device, comm)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, g_off, g_m)
 
-    # ---- BASELINE configs[3], fixed size, sharded: the strong-scaling leg of every line (collective) -----------------
+    # ---- BASELINE configs[3], fixed size, sharded: the strong-scaling leg of a --full line (collective) --------------
     c3 = None
-    if not args.no_config3:
+    if args.full and not args.no_config3:
         steps3 = args.config3_steps if args.config3_steps > 0 else (1 if world == 1 else 2)
         c3 = config34_leg(args, 3, steps3, 0 if world == 1 else 1, state)
 
     c4 = None
-    if world == 1 and not dry and not args.no_config4 and args.images == 500 and args.feats == 4096:
+    if args.full and world == 1 and not dry and not args.no_config4 and args.images == 500 and args.feats == 4096:
         # BASELINE configs[4] (10,000 x 4096, sequential + loop matching) at N = 1, one step: what the driver's default
         # line would otherwise never show (`--config 4` alone is the full line)
         c4 = config34_leg(args, 4, 1, 1, state)   # (one warm-up step: the first call of a context allocates its tables)
@@ -1371,6 +1436,8 @@ def main():
             out["dry_run"] = True
             out["metric"] = "DRY RUN (CPU oracle in place of the kernels, gloo in place of RCCL): NOT a measurement - " + out["metric"]
             out["data"] = "synthetic (cpu dry run)"
+            # the match calls rank 0 made, counted by the stand-in context: the warm-up's and the timed loop's
+            out["dry_run_match_calls"] = {"warmup": calls_before, "timed": timed_calls}
         if c3 is not None:
             out["config3"] = config3_summary(c3)
             # (the same scalars at the top level: a reader that keeps only one level of the line still has the curve)
@@ -1409,7 +1476,7 @@ def main():
                 out["roofline"]["algorithmic_bytes"] = float(per_launch) * 2 * args.feats * 128
         except (OSError, KeyError, ValueError, IndexError):
             pass
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             cores = host_cores()
             arena_cpu = arena.cpu().numpy()
             sample = args.cpu_sample_pairs if args.cpu_sample_pairs > 0 else 8 * cores
@@ -1437,7 +1504,7 @@ def main():
                 "default_cpu_matcher": cpu_default,   # the k-d forest COLMAP's CPU path uses by default (approximate)
                 "optimised": cpu_opt,   # None on a host without AVX-512 VNNI
             }
-        gpu_legs = world == 1 and not dry
+        gpu_legs = args.full and world == 1 and not dry
         if args.verify_pairs > 0 and gpu_legs:
             out["verify"] = verify_leg(lambda: _capi.Context(local_rank), local_rank, args.verify_pairs,
                                        max(1, args.steps), min(1, args.warmup),

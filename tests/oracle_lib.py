@@ -12,11 +12,24 @@ LIB = ROOT / "oracle" / "_build" / "liboracle.so"
 _lib = None
 
 
+def make_oracle(target: str, product: Path) -> None:
+    """`make -C oracle <target>` unless `product` is there already, one process at a time: pool workers and parallel
+    test processes that find it missing together wait on one lock instead of linking over each other's output (the
+    Makefile renames each finished library into place, so a library that exists is whole)."""
+    if product.exists():
+        return
+    import fcntl
+    product.parent.mkdir(parents=True, exist_ok=True)
+    with open(product.parent / ".make.lock", "w") as lk:
+        fcntl.flock(lk, fcntl.LOCK_EX)
+        if not product.exists():
+            subprocess.run(["make", "-C", str(ROOT / "oracle"), target], check=True, capture_output=True)
+
+
 def load() -> C.CDLL:
     global _lib
     if _lib is None:
-        if not LIB.exists():
-            subprocess.run(["make", "-C", str(ROOT / "oracle")], check=True, capture_output=True)
+        make_oracle("all", LIB)
         lib = C.CDLL(str(LIB))
         lib.oracle_match.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double,
                                      C.c_double, C.c_int, C.c_void_p]

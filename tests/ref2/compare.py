@@ -112,6 +112,9 @@ def evaluate(num_random: int = 500, no_ref2: bool = False, workers: int = 1, ver
     nscenes = 20 + 64 + num_random
     if workers > 1:
         import multiprocessing as mp
+        for n in variants.NAMES:         # built and loaded here, once: the forked workers inherit the libraries
+            if n in names:
+                variants.load(n)
         with mp.get_context("fork").Pool(workers) as pool:
             parts = pool.map(_rows_of, [(num_random, names, w, workers) for w in range(workers)])
     else:

@@ -6,7 +6,6 @@ from __future__ import annotations
 import ctypes as C
 import glob
 import os
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -35,8 +34,7 @@ def lapack_library() -> str | None:
 def load(name: str) -> C.CDLL:
     if name not in _libs:
         lib = BUILD / f"liboracle_{name}.so"
-        if not lib.exists():
-            subprocess.run(["make", "-C", str(ROOT / "oracle"), "variants"], check=True, capture_output=True)
+        o.make_oracle("variants", lib)
         if name != "seqsum":
             path = lapack_library()
             if path is None:

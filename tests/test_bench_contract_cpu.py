@@ -133,12 +133,12 @@ def _run_bench(*argv, timeout=600):
 
 
 def test_multi_rank_entry_launches_itself_and_carries_the_configs3_leg():
-    """`python bench.py --gpus 2` (no launcher around it, no --config): the entry starts its two ranks under
+    """`python bench.py --gpus 2 --full` (no launcher around it, no --config): the entry starts its two ranks under
     torch.distributed.run; the line is the weak-scaled configs[1] headline (the metric at every N) and carries
     BASELINE configs[3] - fixed pair set, sharded, strong scaling: the curve north_star states its ">= 7x at 8 GPUs"
     on - as the `config3` leg, with its scalars repeated at the top level.  Run here without a GPU (--cpu-dry-run:
     gloo, CPU oracle in place of the kernels, tiny sizes): a plumbing check, every value is null."""
-    d = _run_bench("--gpus", "2", "--cpu-dry-run", "--images", "9", "--feats", "64", "--steps", "1", "--warmup", "1")
+    d = _run_bench("--gpus", "2", "--cpu-dry-run", "--images", "9", "--feats", "64", "--steps", "1", "--warmup", "1", "--full")
     assert d["dry_run"] is True and d["value"] is None and d["metric"].startswith("DRY RUN")
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["higher_is_better"] is True
     assert "configs[1]" in d["config"]["workload"] and d["config"]["pairs_total"] == 13 * 12 // 2   # 9 x sqrt(2) images
@@ -193,11 +193,11 @@ def test_bench_refuses_gloo_for_a_measurement():
 
 
 def test_eight_rank_entry_dry_run():
-    """`python bench.py --gpus 8` as the driver will launch it on the 8-GPU node, rehearsed without a GPU: eight ranks,
+    """The 8-rank `python bench.py --gpus 8 --full` line, rehearsed without a GPU: eight ranks,
     the weak-scaled headline (500 * sqrt(8) images' worth of pairs at the reduced size) and the configs[3] strong-scaling
     leg, every pair matched exactly once over the eight ranks, one JSON line from rank 0."""
     d = _run_bench("--gpus", "8", "--cpu-dry-run", "--images", "6", "--feats", "32", "--steps", "1", "--warmup", "0",
-                   timeout=900)
+                   "--full", timeout=900)
     assert d["dry_run"] is True and d["n_gpus"] == 8 and d["scaling"] == "weak" and d["value"] is None
     n_img = d["config"]["images"] if "images" in d["config"] else None
     assert d["config"]["pairs_total"] >= 8 and 0 <= d["config"]["pairs_per_rank"] <= d["config"]["pairs_total"]
@@ -206,3 +206,78 @@ def test_eight_rank_entry_dry_run():
     c = l3["line"]["config"] if "line" in l3 else l3["config"]
     assert c["pairs_total"] == 15 and c["distances_per_step_all_ranks"] == 15 * 32 * 32
     assert len(c["kernel_ms_per_step_by_rank"]) == 8
+
+
+def test_plain_line_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times the headline and nothing else: no other leg, no CPU baseline in the line, and
+    --steps / --warmup are the match calls it really makes (counted by the dry run's stand-in context).  --dump-outputs
+    writes the match table the last timed step returned; a second run with the same arguments, and a run with other
+    step counts, write the same arrays (the inputs are seeded).  Run without a GPU (--cpu-dry-run: the CPU oracle in
+    place of the kernels)."""
+    import numpy as np
+    base = ("--gpus", "1", "--cpu-dry-run", "--images", "9", "--feats", "64")
+    argv = (*base, "--steps", "2", "--warmup", "1")
+    a = _run_bench(*argv, "--dump-outputs", str(tmp_path / "a"))
+    b = _run_bench(*argv, "--dump-outputs", str(tmp_path / "b"))
+    c = _run_bench(*base, "--steps", "3", "--warmup", "0", "--dump-outputs", str(tmp_path / "c"))
+    assert a["steps"] == 2 and a["warmup"] == 1 and a["ms_per_step"] > 0 and a["config"]["pairs_total"] == 36
+    assert a["dry_run_match_calls"] == {"warmup": 1, "timed": 2} and c["dry_run_match_calls"] == {"warmup": 0, "timed": 3}
+    for leg in ("cpu_baseline", "config3", "config4", "verify", "pipeline", "ragged", "sift_stats", "dense", "db"):
+        assert leg not in a, leg
+    off, m = np.load(tmp_path / "a" / "match_offsets.npy"), np.load(tmp_path / "a" / "matches.npy")
+    assert off.dtype == np.float64 and m.dtype == np.float32 and off.shape == (37,) and off[0] == 0
+    assert np.all(np.diff(off) >= 0) and m.shape == (int(off[-1]), 2) == (a["config"]["matches_rank0"], 2)
+    assert np.all((m >= 0) & (m < 64)) and not (tmp_path / "a" / "sampled_pairs.npy").exists()
+    assert sorted(p.name for p in (tmp_path / "b").iterdir()) == ["match_offsets.npy", "matches.npy"]
+    for run in ("b", "c"):
+        assert np.array_equal(off, np.load(tmp_path / run / "match_offsets.npy")), run
+        assert np.array_equal(m, np.load(tmp_path / run / "matches.npy")), run
+
+
+def test_multi_rank_dump_is_the_exchanged_table(tmp_path):
+    """At N > 1 --dump-outputs writes what the exchange hands a caller: the table of ALL pairs in the global order, not
+    rank 0's slice.  Two dry-run ranks on 13 images against one rank on the same 13 images: pair for pair the same rows
+    (one rank matches the pairs in its shard order, `mine` maps them to global positions)."""
+    import numpy as np
+    from pycolmap_amd import distributed as D, synth
+    two = _run_bench("--gpus", "2", "--cpu-dry-run", "--images", "9", "--feats", "64", "--steps", "1", "--warmup", "0",
+                     "--dump-outputs", str(tmp_path / "two"))
+    one = _run_bench("--gpus", "1", "--cpu-dry-run", "--images", "13", "--feats", "64", "--steps", "1", "--warmup", "0",
+                     "--dump-outputs", str(tmp_path / "one"))
+    assert two["config"]["pairs_total"] == one["config"]["pairs_total"] == 78 and two["config"]["pairs_per_rank"] < 78
+    g_off, g_m = np.load(tmp_path / "two" / "match_offsets.npy"), np.load(tmp_path / "two" / "matches.npy")
+    l_off, l_m = np.load(tmp_path / "one" / "match_offsets.npy"), np.load(tmp_path / "one" / "matches.npy")
+    assert g_off.shape == l_off.shape == (79,) and g_m.shape == l_m.shape
+    s1, s2 = synth.exhaustive_pairs(13)
+    _, _, mine = D.shard_pairs(s1, s2, 0, 1, rows=np.full(13, 64))
+    for k, p in enumerate(mine):
+        assert np.array_equal(l_m[int(l_off[k]):int(l_off[k + 1])], g_m[int(g_off[p]):int(g_off[p + 1])]), (k, p)
+
+
+def test_dump_outputs_cuts_a_large_table_to_a_seeded_sample(tmp_path, monkeypatch):
+    """A match table over the dump budget is written as a seeded sample of whole pairs that fits the budget; the sample
+    is the same from call to call, and its rows are the pairs' rows."""
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_for_dump", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    counts = rng.integers(0, 60, size=300)
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+    m = rng.integers(0, 4096, size=(int(off[-1]), 2)).astype(np.uint32)
+    bench.dump_outputs(tmp_path / "whole", off, m)
+    assert np.array_equal(np.load(tmp_path / "whole" / "match_offsets.npy"), off.astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "whole" / "matches.npy"), m.astype(np.float32))
+    budget = 40000
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", budget)
+    for name in ("cut1", "cut2"):
+        bench.dump_outputs(tmp_path / name, off, m)
+    arrays = {p.name: np.load(p) for p in (tmp_path / "cut1").iterdir()}
+    assert set(arrays) == {"match_offsets.npy", "matches.npy", "sampled_pairs.npy"}
+    assert 0 < sum(p.stat().st_size for p in (tmp_path / "cut1").iterdir()) <= budget      # the files, headers included
+    pick, coff, cm = arrays["sampled_pairs.npy"].astype(np.int64), arrays["match_offsets.npy"], arrays["matches.npy"]
+    assert len(pick) < len(counts) and np.all(np.diff(pick) > 0) and len(coff) == len(pick) + 1
+    for k, p in enumerate(pick):
+        assert np.array_equal(cm[int(coff[k]):int(coff[k + 1])], m[int(off[p]):int(off[p + 1])].astype(np.float32))
+    for name, a in arrays.items():
+        assert np.array_equal(a, np.load(tmp_path / "cut2" / name)), name

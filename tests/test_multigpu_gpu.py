@@ -166,10 +166,10 @@ def test_bench_two_gpus_sharded_configuration():
 
 @pytest.mark.skipif("_ngpus() < 2", reason="needs two GPUs")
 def test_bench_two_gpus_default_line_carries_both_curves():
-    """`python bench.py --gpus 2`: the weak-scaled configs[1] headline and the configs[3] strong-scaling leg in one line,
-    both exchanging through amc_allgather_match_tables."""
+    """`python bench.py --gpus 2 --full`: the weak-scaled configs[1] headline and the configs[3] strong-scaling leg in one
+    line, both exchanging through amc_allgather_match_tables."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--images", "48", "--feats", "1024", "--steps", "1",
-                        "--warmup", "1"], cwd=ROOT, capture_output=True, text=True, timeout=900,
+                        "--warmup", "1", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -180,10 +180,10 @@ def test_bench_two_gpus_default_line_carries_both_curves():
 
 
 def test_bench_one_gpu_line_carries_the_configs3_leg_through_the_c_abi():
-    """The same line at N = 1 (reduced sizes): the configs[3] leg runs its exchange step through the library's
+    """The same --full line at N = 1 (reduced sizes): the configs[3] leg runs its exchange step through the library's
     communicator with one rank, and its sample of pairs agrees with the oracle."""
     r = subprocess.run([sys.executable, "bench.py", "--images", "24", "--feats", "1024", "--steps", "1", "--warmup", "0",
-                        "--verify-pairs", "0", "--no-pipeline", "--no-ragged", "--no-sift-stats", "--no-dense", "--no-db"],
+                        "--full", "--verify-pairs", "0", "--no-pipeline", "--no-ragged", "--no-sift-stats", "--no-dense", "--no-db"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-2000:]

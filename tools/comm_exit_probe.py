@@ -33,9 +33,9 @@ for name, body in VARIANTS.items():
 for name, cmd in {
     "pytest_c_abi_test": [sys.executable, "-m", "pytest", "tests/test_multigpu_gpu.py", "-q", "-k", "c_abi_without"],
     "pytest_c_abi_plus_skips": [sys.executable, "-m", "pytest", "tests/test_multigpu_gpu.py", "-q", "-k", "c_abi_without or two_rank"],
-    "bench_config3_mid": [sys.executable, "bench.py", "--images", "120", "--feats", "4096", "--steps", "1", "--warmup", "0", "--verify-pairs", "0",
+    "bench_config3_mid": [sys.executable, "bench.py", "--images", "120", "--feats", "4096", "--steps", "1", "--warmup", "0", "--full", "--verify-pairs", "0",
                           "--no-pipeline", "--no-ragged", "--no-sift-stats", "--no-dense", "--no-db", "--no-cpu-baseline"],
-    "bench_no_config3_mid": [sys.executable, "bench.py", "--images", "120", "--feats", "4096", "--steps", "1", "--warmup", "0", "--verify-pairs", "0",
+    "bench_no_config3_mid": [sys.executable, "bench.py", "--images", "120", "--feats", "4096", "--steps", "1", "--warmup", "0", "--full", "--verify-pairs", "0",
                              "--no-pipeline", "--no-ragged", "--no-sift-stats", "--no-dense", "--no-db", "--no-cpu-baseline", "--no-config3"],
 }.items():
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)

@@ -8,14 +8,12 @@ OUT=$R/gpurun_out/r04/ladder_pmc_$TAG.txt
 : > $OUT
 run() {
   tag=$1; shift
-  for try in 1 2 3; do
-    rm -rf /tmp/lad_$tag
-    timeout 300 rocprofv3 --kernel-trace --pmc "$@" -d /tmp/lad_$tag -- $R/tools/bin/ubench_ladder > /tmp/lad_$tag.log 2>&1
-    rc=$?
-    db=$(find /tmp/lad_$tag -name "*.db" 2>/dev/null | head -1)
-    [ -n "$db" ] && break
-  done
-  echo "rc=$rc tries=$try" >> $OUT
+  rm -rf /tmp/lad_$tag
+  timeout 300 rocprofv3 --kernel-trace --pmc "$@" -d /tmp/lad_$tag -- $R/tools/bin/ubench_ladder > /tmp/lad_$tag.log 2>&1
+  rc=$?
+  db=$(find /tmp/lad_$tag -name "*.db" 2>/dev/null | head -1)
+  [ -n "$db" ] || { echo "rc=$rc: pass $tag left no trace, stopping (a failed GPU pass is not run again)" >> $OUT; exit 1; }
+  echo "rc=$rc" >> $OUT
   echo "=== pass $tag: $@" >> $OUT
   [ -n "$db" ] && python $R/tools/pmc_summary.py $db ladder | grep -E "calls=|n=" | grep -v "pmc tables" >> $OUT
   grep rung /tmp/lad_$tag.log >> $OUT

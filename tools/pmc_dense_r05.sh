@@ -6,14 +6,12 @@ OUT=$R/gpurun_out/r05/pmc_dense_r05_$TAG.txt
 : > $OUT
 run() {
   tag=$1; shift
-  for try in 1 2; do
-    rm -rf /tmp/pmcd_$tag
-    timeout 400 rocprofv3 --kernel-trace --pmc "$@" -d /tmp/pmcd_$tag -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --verify-pairs 0 --no-pipeline --no-ragged --no-db --no-sift-stats --no-config3 > /tmp/pmcd_$tag.log 2>&1
-    rc=$?
-    db=$(find /tmp/pmcd_$tag -name "*.db" 2>/dev/null | head -1)
-    [ -n "$db" ] && break
-  done
-  echo "rc=$rc tries=$try" >> $OUT
+  rm -rf /tmp/pmcd_$tag
+  timeout 400 rocprofv3 --kernel-trace --pmc "$@" -d /tmp/pmcd_$tag -- python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --verify-pairs 0 --no-pipeline --no-ragged --no-db --no-sift-stats --no-config3 > /tmp/pmcd_$tag.log 2>&1
+  rc=$?
+  db=$(find /tmp/pmcd_$tag -name "*.db" 2>/dev/null | head -1)
+  [ -n "$db" ] || { echo "rc=$rc: pass $tag left no trace, stopping (a failed GPU pass is not run again)" >> $OUT; exit 1; }
+  echo "rc=$rc" >> $OUT
   echo "=== pass $tag: $@" >> $OUT
   [ -n "$db" ] && python $R/tools/pmc_summary.py $db amc:: | grep -E "resolve_index|match_mfma_kernel<1|finalize_kernel|select_candidates" | sed -E 's/\(amc::[^)]*\)?[^ ]* +/ /' | cut -c1-230 >> $OUT
 }

@@ -5,17 +5,15 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; TAG=${1:-v1}; O=$R/gpurun_out/r06; mkdir -p $O
 OUT=$O/pmc_dense_r06_$TAG.txt
 echo "box: boot_id $(cat /proc/sys/kernel/random/boot_id 2>/dev/null)" > $OUT
-BENCH="python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --verify-pairs 0 --no-pipeline --no-ragged --no-db --no-sift-stats --no-config3 --no-config4 --detail-json /tmp/dense_line.json"
+BENCH="python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --verify-pairs 0 --no-pipeline --no-ragged --no-db --no-sift-stats --no-config3 --no-config4 --detail-json /tmp/dense_line.json"
 run() {
   tag=$1; shift
-  for try in 1 2 3; do
-    rm -rf /tmp/pmcd_$tag
-    timeout 400 rocprofv3 --kernel-trace --kernel-include-regex 'resolve_index|match_mfma_kernel<1|select_candidates|finalize_kernel|match_mfma_kernel<0' --pmc "$@" -d /tmp/pmcd_$tag -- $BENCH > /tmp/pmcd_$tag.log 2>&1
-    rc=$?
-    db=$(find /tmp/pmcd_$tag -name "*.db" 2>/dev/null | head -1)
-    [ -n "$db" ] && break
-  done
-  echo "rc=$rc tries=$try" >> $OUT
+  rm -rf /tmp/pmcd_$tag
+  timeout 400 rocprofv3 --kernel-trace --kernel-include-regex 'resolve_index|match_mfma_kernel<1|select_candidates|finalize_kernel|match_mfma_kernel<0' --pmc "$@" -d /tmp/pmcd_$tag -- $BENCH > /tmp/pmcd_$tag.log 2>&1
+  rc=$?
+  db=$(find /tmp/pmcd_$tag -name "*.db" 2>/dev/null | head -1)
+  [ -n "$db" ] || { echo "rc=$rc: pass $tag left no trace, stopping (a failed GPU pass is not run again)" >> $OUT; exit 1; }
+  echo "rc=$rc" >> $OUT
   echo "=== pass $tag: $@" >> $OUT
   [ -n "$db" ] && python $R/tools/pmc_dispatches.py $db resolve_index match_mfma_kernel finalize_kernel select_candidates >> $OUT
 }

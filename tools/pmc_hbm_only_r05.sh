@@ -5,14 +5,12 @@ BENCH="python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --verify-pairs 
 H=$O/pmc_hbm_r05_$TAG.txt; : > $H
 run() {
   tag=$1; shift
-  for try in 1 2; do
-    rm -rf /tmp/pmch_$tag
-    timeout 300 rocprofv3 --kernel-trace --pmc "$@" -d /tmp/pmch_$tag -- $BENCH > /tmp/pmch_$tag.log 2>&1
-    rc=$?
-    db=$(find /tmp/pmch_$tag -name "*.db" 2>/dev/null | head -1)
-    [ -n "$db" ] && break
-  done
-  echo "rc=$rc tries=$try" >> $H
+  rm -rf /tmp/pmch_$tag
+  timeout 300 rocprofv3 --kernel-trace --pmc "$@" -d /tmp/pmch_$tag -- $BENCH > /tmp/pmch_$tag.log 2>&1
+  rc=$?
+  db=$(find /tmp/pmch_$tag -name "*.db" 2>/dev/null | head -1)
+  [ -n "$db" ] || { echo "rc=$rc: pass $tag left no trace, stopping (a failed GPU pass is not run again)" >> $H; exit 1; }
+  echo "rc=$rc" >> $H
   echo "=== pass $tag: $@" >> $H
   [ -n "$db" ] && python $R/tools/pmc_summary.py $db match_mfma | grep -E "calls=|n=" | grep -v "pmc tables" >> $H
 }

@@ -7,16 +7,14 @@ TAG=${1:-v1}
 O=$R/gpurun_out/r05
 mkdir -p $O
 BENCH="python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --verify-pairs 0 --no-pipeline --no-dense --no-ragged --no-db --no-sift-stats --no-config3"
-run() {  # $1 = out file, $2 = tag, $3... = counters; a pass whose rocprofv3 dies (it happens on some boxes) is retried
+run() {  # $1 = out file, $2 = tag, $3... = counters; a pass whose rocprofv3 dies ends the script
   out=$1; tag=$2; shift; shift
-  for try in 1 2 3; do
-    rm -rf /tmp/pmc4_$tag
-    timeout 300 rocprofv3 --kernel-trace --pmc "$@" -d /tmp/pmc4_$tag -- $BENCH > /tmp/pmc4_$tag.log 2>&1
-    rc=$?
-    db=$(find /tmp/pmc4_$tag -name "*.db" 2>/dev/null | head -1)
-    [ -n "$db" ] && break
-  done
-  echo "rc=$rc tries=$try" >> $out
+  rm -rf /tmp/pmc4_$tag
+  timeout 300 rocprofv3 --kernel-trace --pmc "$@" -d /tmp/pmc4_$tag -- $BENCH > /tmp/pmc4_$tag.log 2>&1
+  rc=$?
+  db=$(find /tmp/pmc4_$tag -name "*.db" 2>/dev/null | head -1)
+  [ -n "$db" ] || { echo "rc=$rc: pass $tag left no trace, stopping (a failed GPU pass is not run again)" >> $out; exit 1; }
+  echo "rc=$rc" >> $out
   echo "=== pass $tag: $@" >> $out
   [ -n "$db" ] && python $R/tools/pmc_summary.py $db match_mfma | grep -E "calls=|n=" | grep -v "pmc tables" >> $out
 }

@@ -9,16 +9,14 @@ O=$R/gpurun_out/r06
 mkdir -p $O
 BOX="boot_id $(cat /proc/sys/kernel/random/boot_id 2>/dev/null) host $(hostname) gpu $(rocm-smi --showserial 2>/dev/null | grep -i serial | head -1 | tr -s ' ' | cut -c1-80)"
 BENCH="python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --verify-pairs 0 --no-pipeline --no-dense --no-ragged --no-db --no-sift-stats --no-config3 --no-config4"
-run() {  # $1 = out file, $2 = tag, $3... = counters; a pass whose rocprofv3 dies (it happens on some boxes) is retried
+run() {  # $1 = out file, $2 = tag, $3... = counters; a pass whose rocprofv3 dies ends the script
   out=$1; tag=$2; shift; shift
-  for try in 1 2 3; do
-    rm -rf /tmp/pmc6_$tag
-    timeout 300 rocprofv3 --kernel-trace --kernel-include-regex 'match_mfma_kernel<0' --pmc "$@" -d /tmp/pmc6_$tag -- $BENCH > /tmp/pmc6_$tag.log 2>&1
-    rc=$?
-    db=$(find /tmp/pmc6_$tag -name "*.db" 2>/dev/null | head -1)
-    [ -n "$db" ] && break
-  done
-  echo "rc=$rc tries=$try" >> $out
+  rm -rf /tmp/pmc6_$tag
+  timeout 300 rocprofv3 --kernel-trace --kernel-include-regex 'match_mfma_kernel<0' --pmc "$@" -d /tmp/pmc6_$tag -- $BENCH > /tmp/pmc6_$tag.log 2>&1
+  rc=$?
+  db=$(find /tmp/pmc6_$tag -name "*.db" 2>/dev/null | head -1)
+  [ -n "$db" ] || { echo "rc=$rc: pass $tag left no trace, stopping (a failed GPU pass is not run again)" >> $out; exit 1; }
+  echo "rc=$rc" >> $out
   echo "=== pass $tag: $@" >> $out
   [ -n "$db" ] && python $R/tools/pmc_summary.py $db match_mfma | grep -E "calls=|n=" | grep -v "pmc tables" >> $out
 }

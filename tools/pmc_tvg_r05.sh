@@ -1,5 +1,5 @@
 # round 5: SQ counters of the two verification kernels (tvg_e_kernel, tvg_fh_kernel) on 16,384 pairs of the bench's
-# verify workload, one counter group per pass (--kernel-trace + --pmc only; a pass whose rocprofv3 dies is retried).
+# verify workload, one counter group per pass (--kernel-trace + --pmc only; a pass whose rocprofv3 dies ends the script).
 #   bash tools/pmc_tvg_r05.sh [tag]      -> gpurun_out/r05/pmc_tvg_r05_<tag>.txt
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; TAG=${1:-v1}; mkdir -p $R/gpurun_out/r05
@@ -7,14 +7,12 @@ OUT=$R/gpurun_out/r05/pmc_tvg_r05_$TAG.txt
 : > $OUT
 run() {
   tag=$1; shift
-  for try in 1 2 3; do
-    rm -rf /tmp/pmct_$tag
-    timeout 300 rocprofv3 --kernel-trace --pmc "$@" -d /tmp/pmct_$tag -- python $R/bench.py --images 40 --steps 1 --warmup 0 --no-cpu-baseline --verify-pairs 16384 --no-pipeline --no-dense --no-ragged --no-db --no-sift-stats --no-config3 > /tmp/pmct_$tag.log 2>&1
-    rc=$?
-    db=$(find /tmp/pmct_$tag -name "*.db" 2>/dev/null | head -1)
-    [ -n "$db" ] && break
-  done
-  echo "rc=$rc tries=$try" >> $OUT
+  rm -rf /tmp/pmct_$tag
+  timeout 300 rocprofv3 --kernel-trace --pmc "$@" -d /tmp/pmct_$tag -- python $R/bench.py --full --images 40 --steps 1 --warmup 0 --no-cpu-baseline --verify-pairs 16384 --no-pipeline --no-dense --no-ragged --no-db --no-sift-stats --no-config3 > /tmp/pmct_$tag.log 2>&1
+  rc=$?
+  db=$(find /tmp/pmct_$tag -name "*.db" 2>/dev/null | head -1)
+  [ -n "$db" ] || { echo "rc=$rc: pass $tag left no trace, stopping (a failed GPU pass is not run again)" >> $OUT; exit 1; }
+  echo "rc=$rc" >> $OUT
   echo "=== pass $tag: $@" >> $OUT
   [ -n "$db" ] && python $R/tools/pmc_summary.py $db tvg_ | grep -E "tvg_(e|fh)_kernel" >> $OUT
 }

@@ -6,7 +6,7 @@ TAG=${1:-v1}
 mkdir -p $R/gpurun_out/r05
 OUT=$R/gpurun_out/r05/ab_dense_$TAG.txt
 : > $OUT
-ARGS="--steps 5 --warmup 2 --verify-pairs 0 --no-pipeline --no-ragged --no-sift-stats --no-db --no-cpu-baseline --no-config3"
+ARGS="--full --steps 5 --warmup 2 --verify-pairs 0 --no-pipeline --no-ragged --no-sift-stats --no-db --no-cpu-baseline --no-config3"
 for rep in 1 2; do
   for which in prev cur; do
     if [ $which = prev ]; then export AMC_LIB_PATH=$R/pycolmap_amd/csrc/_obj/libamc_prev.so; else unset AMC_LIB_PATH; fi

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out/r06; mkdir -p $O; TAG=${1:-v1}; REPS=${2:-2}; shift; shift
 CUS="${@:-8}"
 OUT=$O/ab_overlap_$TAG.txt; : > $OUT
-HEAD="--steps 8 --warmup 2 --no-cpu-baseline --verify-pairs 0 --no-pipeline --no-ragged --no-db --no-sift-stats --no-config3 --no-config4"
+HEAD="--full --steps 8 --warmup 2 --no-cpu-baseline --verify-pairs 0 --no-pipeline --no-ragged --no-db --no-sift-stats --no-config3 --no-config4"
 line() {
   python bench.py $HEAD 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; e=d.get('dense') or {}; print('$1', 'headline_ms', round(d['ms_per_step'],2), 'scan_ms', round(r['avg_kernel_ms'],3), 'scan_frac', round(r['frac'],4), 'whole_step_frac', round(r['whole_step_frac'],4), '| dense_ms', e.get('ms_per_step'), 'dense_stage_ms', e.get('resolve_select_reverse_scan_ms'))" >> $OUT
 }

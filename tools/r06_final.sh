@@ -9,7 +9,7 @@ O=gpurun_out/r06; mkdir -p $O; SEC=${1:-suite}; TAG=${2:-v1}
 NOLEGS="--no-cpu-baseline --verify-pairs 0 --no-pipeline --no-dense --no-ragged --no-db --no-sift-stats --no-config3 --no-config4"
 if [ $SEC = suite ]; then
   timeout 900 python -m pytest tests -x -q -m gpu > $O/pytest_gpu_$TAG.log 2>&1; echo "pytest rc=$?"; grep -E "passed|failed|error" $O/pytest_gpu_$TAG.log | tail -2
-  timeout 700 python bench.py --steps 20 --warmup 5 --detail-json $O/bench_detail_$TAG.json > $O/bench_line_unprofiled_$TAG.json 2> $O/bench_line_unprofiled_$TAG.err; echo "bench rc=$?"
+  timeout 700 python bench.py --full --steps 20 --warmup 5 --detail-json $O/bench_detail_$TAG.json > $O/bench_line_unprofiled_$TAG.json 2> $O/bench_line_unprofiled_$TAG.err; echo "bench rc=$?"
   (cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/kt5 && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt5 -- python $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 $NOLEGS > $GRAFT_REPO_ROOT/$O/bench_line_headline_only_under_rocprofv3_$TAG.json 2> /tmp/kt5.err; f=$(find /tmp/kt5 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $GRAFT_REPO_ROOT/$O/rocprofv3_kernel_stats_headline_only_$TAG.csv && head -4 $f | cut -c1-200)
   timeout 400 python bench.py --config 4 --steps 2 --warmup 1 --full-line > $O/bench_config4_n1_$TAG.json 2> /dev/null; echo "config4 rc=$?"
   timeout 300 python tools/stress_match.py > $O/stress_match_$TAG.txt 2>&1; tail -2 $O/stress_match_$TAG.txt

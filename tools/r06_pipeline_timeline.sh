@@ -2,7 +2,7 @@
 # processes, 10 steps each: where a step's wall time goes beside the kernels' spans.   bash tools/r06_pipeline_timeline.sh <tag> [reps]
 cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out/r06; mkdir -p $O; TAG=${1:-v1}; REPS=${2:-4}; OUT=$O/pipeline_timeline_$TAG.txt; : > $OUT
-PIPE="--steps 3 --warmup 1 --no-cpu-baseline --no-dense --verify-pairs 0 --no-ragged --no-db --no-sift-stats --no-config3 --no-config4 --pipeline-steps ${STEPS:-10} --full-line"
+PIPE="--full --steps 3 --warmup 1 --no-cpu-baseline --no-dense --verify-pairs 0 --no-ragged --no-db --no-sift-stats --no-config3 --no-config4 --pipeline-steps ${STEPS:-10} --full-line"
 for r in $(seq $REPS); do
   python bench.py $PIPE 2>/dev/null | tail -1 | python -c "
 import json,sys; p=json.loads(sys.stdin.read())['pipeline']; s=p['stage_ms_per_step']; h=p['host_timeline_ms_per_step']

@@ -1,7 +1,9 @@
 """`import pycolmap` for code written against the reference package: every name of the match + verify path
-(/root/reference/pycolmap/main.cc:91-118 registers them on the `pycolmap` module) resolves to pycolmap_amd's
-MI355X implementation.  Only what SURVEY.md section 8 puts in scope exists; anything else raises AttributeError
-naming this package, so that a script reaching for extraction / SfM / MVS fails at the attribute, not later."""
+(/root/reference/pycolmap/main.cc:91-118 registers them on the `pycolmap` module) and of SIFT feature extraction
+(`extract_features`, `Sift`, `SiftExtractionOptions`, `Normalization`, `ImageReaderOptions`, `CameraMode`) resolves to
+pycolmap_amd's MI355X implementation.  Only what SURVEY.md section 8 and DESIGN.md section 10 put in scope exists;
+anything else raises AttributeError naming this package, so that a script reaching for `import_images`, SfM or MVS
+fails at the attribute, not later."""
 import pycolmap_amd as _impl
 from pycolmap_amd import *  # noqa: F401,F403
 from pycolmap_amd import __version__  # noqa: F401
@@ -11,5 +13,5 @@ globals().update({n: getattr(_impl, n) for n in _PUBLIC})
 
 
 def __getattr__(name):
-    raise AttributeError(f"pycolmap.{name} is outside pycolmap_amd's scope (exhaustive / sequential matching + two-view "
-                         f"verification behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}")
+    raise AttributeError(f"pycolmap.{name} is outside pycolmap_amd's scope (SIFT feature extraction, exhaustive / sequential "
+                         f"matching + two-view verification behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}")

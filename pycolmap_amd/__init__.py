@@ -15,8 +15,8 @@ __version__ = "0.1.0"
 
 try:  # the compiled host layer; absent only before `python -m pycolmap_amd.build`
     from ._pycolmap import (  # noqa: F401
-        COLMAP_build, COLMAP_version, Camera, CameraModelId, Database, DatabaseTransaction, Device, ExhaustiveMatchingOptions, Image, RANSACOptions, Rigid3d,
-        Rotation3d,
+        COLMAP_build, COLMAP_version, Camera, CameraMode, CameraModelId, Database, DatabaseTransaction, Device, ExhaustiveMatchingOptions, Image, ImageReaderOptions, Normalization, RANSACOptions, Rigid3d,
+        Rotation3d, Sift, SiftExtractionOptions,
         SequentialMatchingOptions, SiftMatchingOptions, SpatialMatchingOptions, TwoViewGeometry, TwoViewGeometryConfiguration,
         VocabTreeMatchingOptions,
         TwoViewGeometryOptions, essential_matrix_estimation, estimate_calibrated_two_view_geometry,
@@ -24,6 +24,7 @@ try:  # the compiled host layer; absent only before `python -m pycolmap_amd.buil
         has_hip, homography_decomposition, homography_matrix_estimation, last_run_stats, logging, match_exhaustive, match_sequential,
         match_spatial, match_vocabtree, squared_sampson_error, verify_matches,
     )
+    from ._extraction import extract_features  # noqa: F401
     _HOST_LAYER_ERROR = None
 except ImportError as _e:  # pragma: no cover - exercised only on an unbuilt tree
     _HOST_LAYER_ERROR = _e

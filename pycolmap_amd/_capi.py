@@ -114,6 +114,27 @@ class MatchResult(C.Structure):
                 ("match_kernel_launches", C.c_uint32), ("_priv", C.c_void_p)]
 
 
+class SiftOpts(C.Structure):  # amc_sift_opts (include/amc_sift.h)
+    _fields_ = [("first_octave", C.c_int32), ("num_octaves", C.c_int32), ("octave_resolution", C.c_int32),
+                ("peak_threshold", C.c_double), ("edge_threshold", C.c_double), ("max_num_orientations", C.c_int32),
+                ("upright", C.c_int32), ("normalization", C.c_int32), ("max_num_features", C.c_int32),
+                ("max_image_size", C.c_int32)]
+
+
+class SiftImage(C.Structure):
+    _fields_ = [("pixels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("pitch", C.c_int64)]
+
+
+class SiftResult(C.Structure):
+    _fields_ = [("nimages", C.c_size_t), ("offsets", C.POINTER(C.c_uint64)), ("keypoints", C.POINTER(C.c_float)),
+                ("descriptors", C.POINTER(C.c_uint8)), ("device_ms", C.c_double), ("stage_ms", C.c_double * 4),
+                ("_priv", C.c_void_p)]
+
+
+SIFT_NORMALIZATIONS = {"L1_ROOT": 0, "L2": 1}
+SIFT_STAGES = ("scale_space", "detection", "orientation", "descriptors")
+
+
 class RansacOpts(C.Structure):
     _fields_ = [("max_error", C.c_double), ("min_inlier_ratio", C.c_double),
                 ("confidence", C.c_double), ("dyn_num_trials_multiplier", C.c_double),
@@ -211,6 +232,14 @@ def load() -> C.CDLL:
     lib.amc_match_result_free.argtypes = [C.POINTER(MatchResult)]
     lib.amc_match_result_free.restype = None
     lib.amc_match_opts_default.argtypes = [C.POINTER(MatchOpts)]
+    if hasattr(lib, "amc_sift_extract"):  # (an older library under AMC_LIB_PATH, for A/B runs, has no extractor)
+        lib.amc_sift_opts_default.argtypes = [C.POINTER(SiftOpts)]
+        lib.amc_sift_opts_default.restype = None
+        lib.amc_sift_extract.argtypes = [C.c_void_p, C.POINTER(SiftImage), C.c_size_t, C.POINTER(SiftOpts),
+                                         C.POINTER(SiftResult)]
+        lib.amc_sift_extract.restype = C.c_int
+        lib.amc_sift_result_free.argtypes = [C.POINTER(SiftResult)]
+        lib.amc_sift_result_free.restype = None
     lib.amc_match_opts_default.restype = None
     lib.amc_get_acos_lut.argtypes = [C.c_void_p, C.c_void_p]
     lib.amc_tvg_opts_default.argtypes = [C.POINTER(TvgOpts)]
@@ -524,6 +553,40 @@ class Context:
 
     def upload_descriptors_device(self, slot: int, dev_ptr: int, rows: int) -> None:
         _check(self._lib.amc_upload_descriptors_device(self._h, slot, C.c_void_p(dev_ptr), rows))
+
+    def sift_extract(self, images, **opts):
+        """amc_sift_extract on a batch of 2-D uint8 images (or one).  Keyword options are amc_sift_opts fields
+        (normalization: "L1_ROOT" / "L2" or 0 / 1); the rest keep amc_sift_opts_default.  Returns (list of
+        (N x 4 float32 keypoints (x, y, scale, orientation), N x 128 uint8 descriptors) per image, stats dict)."""
+        single = isinstance(images, np.ndarray)
+        imgs = [im if isinstance(im, np.ndarray) and im.ndim == 2 and im.strides[1] == 1 and im.strides[0] >= im.shape[1]
+                else np.ascontiguousarray(im) for im in ([images] if single else images)]
+        for im in imgs:
+            if im.dtype != np.uint8 or im.ndim != 2:
+                raise ValueError(f"sift_extract: images must be 2-D uint8, got {im.dtype} {im.shape}")
+        o = SiftOpts()
+        self._lib.amc_sift_opts_default(C.byref(o))
+        for k, v in opts.items():
+            if k == "normalization" and isinstance(v, str):
+                v = SIFT_NORMALIZATIONS[v]
+            if k not in dict(SiftOpts._fields_):
+                raise ValueError(f"sift_extract: unknown option {k!r}")
+            setattr(o, k, type(getattr(o, k))(v) if not isinstance(v, bool) else int(v))
+        arr = (SiftImage * max(1, len(imgs)))()
+        for i, im in enumerate(imgs):
+            arr[i] = SiftImage(im.ctypes.data, im.shape[1], im.shape[0], im.strides[0])
+        res = SiftResult()
+        _check(self._lib.amc_sift_extract(self._h, arr, len(imgs), C.byref(o), C.byref(res)))
+        try:
+            off = np.ctypeslib.as_array(res.offsets, (len(imgs) + 1,)).copy()
+            n = int(off[-1])
+            kp = np.ctypeslib.as_array(res.keypoints, (max(n, 1), 4))[:n].copy()
+            desc = np.ctypeslib.as_array(res.descriptors, (max(n, 1), 128))[:n].copy()
+            stats = {"device_ms": res.device_ms, "stage_ms": dict(zip(SIFT_STAGES, list(res.stage_ms)))}
+        finally:
+            self._lib.amc_sift_result_free(C.byref(res))
+        out = [(kp[off[i]:off[i + 1]], desc[off[i]:off[i + 1]]) for i in range(len(imgs))]
+        return (out[0] if single else out), stats
 
     def match_pairs(self, slot1, slot2, max_ratio: float = 0.8, max_distance: float = 0.7,
                     cross_check: bool = True, kernel: str = "auto", copy: bool = True):

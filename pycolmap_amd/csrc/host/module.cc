@@ -34,6 +34,7 @@
 #include "controller.h"
 #include "py_types.h"
 #include "estimators.h"
+#include "sift_host.h"
 
 namespace py = pybind11;
 using namespace pybind11::literals;
@@ -410,6 +411,95 @@ PYBIND11_MODULE(_pycolmap, m) {
                        "Whether to perform guided matching, if geometric verification succeeds.");
     MakeDataclass(PySift, {"num_threads", "gpu_index", "max_ratio", "max_distance", "cross_check",
                            "max_num_matches", "guided_matching"});
+
+    // ---- SIFT extraction (/root/reference/pycolmap/pipeline/extract_features.h:71-138, feature/sift.h) ---------------
+    using SEOpts = SiftExtractionOptions;
+    py::enum_<SEOpts::Normalization> PyNorm(m, "Normalization");
+    PyNorm.value("L1_ROOT", SEOpts::Normalization::L1_ROOT,
+                  "L1-normalizes each descriptor followed by element-wise square rooting.")
+        .value("L2", SEOpts::Normalization::L2, "Each vector is L2-normalized.");
+    PyNorm.def(py::init([](const std::string& s) {
+        if (s == "L1_ROOT") return SEOpts::Normalization::L1_ROOT;
+        if (s == "L2") return SEOpts::Normalization::L2;
+        throw py::value_error("Invalid string value " + s + " for enum Normalization");
+    }));
+    py::implicitly_convertible<std::string, SEOpts::Normalization>();
+    py::class_<SEOpts> PySEOpts(m, "SiftExtractionOptions");
+    PySEOpts.def(py::init<>())
+        .def_readwrite("num_threads", &SEOpts::num_threads)
+        .def_readwrite("gpu_index", &SEOpts::gpu_index, "Index of the GPU used for feature extraction.")
+        .def_readwrite("max_image_size", &SEOpts::max_image_size,
+                       "Maximum image size, otherwise image will be down-scaled.")
+        .def_readwrite("max_num_features", &SEOpts::max_num_features,
+                       "Maximum number of features to detect, keeping larger-scale features.")
+        .def_readwrite("first_octave", &SEOpts::first_octave,
+                       "First octave in the pyramid, i.e. -1 upsamples the image by one level.")
+        .def_readwrite("num_octaves", &SEOpts::num_octaves)
+        .def_readwrite("octave_resolution", &SEOpts::octave_resolution, "Number of levels per octave.")
+        .def_readwrite("peak_threshold", &SEOpts::peak_threshold, "Peak threshold for detection.")
+        .def_readwrite("edge_threshold", &SEOpts::edge_threshold, "Edge threshold for detection.")
+        .def_readwrite("estimate_affine_shape", &SEOpts::estimate_affine_shape,
+                       "Estimate affine shape of SIFT features (not supported: raises ValueError).")
+        .def_readwrite("max_num_orientations", &SEOpts::max_num_orientations,
+                       "Maximum number of orientations per keypoint if not estimate_affine_shape.")
+        .def_readwrite("upright", &SEOpts::upright, "Fix the orientation to 0 for upright features")
+        .def_readwrite("darkness_adaptivity", &SEOpts::darkness_adaptivity, "Not supported: raises ValueError.")
+        .def_readwrite("domain_size_pooling", &SEOpts::domain_size_pooling, "Not supported: raises ValueError.")
+        .def_readwrite("dsp_min_scale", &SEOpts::dsp_min_scale)
+        .def_readwrite("dsp_max_scale", &SEOpts::dsp_max_scale)
+        .def_readwrite("dsp_num_scales", &SEOpts::dsp_num_scales)
+        .def_readwrite("normalization", &SEOpts::normalization, "L1_ROOT or L2 descriptor normalization");
+    MakeDataclass(PySEOpts, {"num_threads", "gpu_index", "max_image_size", "max_num_features", "first_octave",
+                             "num_octaves", "octave_resolution", "peak_threshold", "edge_threshold",
+                             "estimate_affine_shape", "max_num_orientations", "upright", "darkness_adaptivity",
+                             "domain_size_pooling", "dsp_min_scale", "dsp_max_scale", "dsp_num_scales",
+                             "normalization"});
+    {
+        py::dict sift_defaults;  // "for backwards consistency" (/root/reference/pycolmap/feature/sift.h:98-102)
+        sift_defaults["peak_threshold"] = 0.01;
+        sift_defaults["first_octave"] = 0;
+        sift_defaults["max_image_size"] = 7000;
+        py::class_<SiftExtractor>(m, "Sift")
+            .def(py::init([](SEOpts options, Device device) {
+                     RequireAccelerator(device);
+                     return std::make_unique<SiftExtractor>(std::move(options));
+                 }),
+                 "options"_a = sift_defaults, "device"_a = Device::AUTO)
+            .def("extract", &SiftExtractor::Extract, "image"_a.noconvert())
+            .def("extract", &SiftExtractor::ExtractFloat, "image"_a.noconvert())
+            .def_property_readonly("options", &SiftExtractor::Options)
+            .def_property_readonly("device", [](const SiftExtractor&) { return Device::CUDA; })
+            .def_property_readonly("last_device_ms", &SiftExtractor::LastDeviceMs,
+                                   "Device time of the last extract call, ms (pycolmap_amd extension).");
+    }
+
+    py::enum_<CameraMode> PyCameraMode(m, "CameraMode");
+    PyCameraMode.value("AUTO", CameraMode::AUTO)
+        .value("SINGLE", CameraMode::SINGLE)
+        .value("PER_FOLDER", CameraMode::PER_FOLDER)
+        .value("PER_IMAGE", CameraMode::PER_IMAGE);
+    PyCameraMode.def(py::init([](const std::string& s) {
+        if (s == "AUTO") return CameraMode::AUTO;
+        if (s == "SINGLE") return CameraMode::SINGLE;
+        if (s == "PER_FOLDER") return CameraMode::PER_FOLDER;
+        if (s == "PER_IMAGE") return CameraMode::PER_IMAGE;
+        throw py::value_error("Invalid string value " + s + " for enum CameraMode");
+    }));
+    py::implicitly_convertible<std::string, CameraMode>();
+    py::class_<ImageReaderOptions> PyIROpts(m, "ImageReaderOptions");
+    PyIROpts.def(py::init<>())
+        .def_readwrite("camera_model", &ImageReaderOptions::camera_model, "Name of the camera model.")
+        .def_readwrite("mask_path", &ImageReaderOptions::mask_path, "Image masks (not supported: raises ValueError).")
+        .def_readwrite("existing_camera_id", &ImageReaderOptions::existing_camera_id,
+                       "Use an existing camera for all images (not supported: raises ValueError).")
+        .def_readwrite("camera_params", &ImageReaderOptions::camera_params,
+                       "Manual specification of camera parameters (comma-separated).")
+        .def_readwrite("default_focal_length_factor", &ImageReaderOptions::default_focal_length_factor,
+                       "The focal length is set to `default_focal_length_factor * max(width, height)` (EXIF is not read).")
+        .def_readwrite("camera_mask_path", &ImageReaderOptions::camera_mask_path,
+                       "A mask for all images (not supported: raises ValueError).");
+    MakeDataclass(PyIROpts, {"camera_model", "mask_path", "existing_camera_id", "camera_params",
+                             "default_focal_length_factor", "camera_mask_path"});
 
     py::class_<ExhaustiveMatchingOptions> PyExh(m, "ExhaustiveMatchingOptions");
     PyExh.def(py::init<>()).def_readwrite("block_size", &ExhaustiveMatchingOptions::block_size);

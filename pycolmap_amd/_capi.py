@@ -131,6 +131,20 @@ class SiftResult(C.Structure):
                 ("_priv", C.c_void_p)]
 
 
+class TriOpts(C.Structure):  # amc_tri_opts (include/amc_tri.h)
+    _fields_ = [("min_tri_angle", C.c_double), ("max_error", C.c_double), ("min_inlier_ratio", C.c_double),
+                ("confidence", C.c_double), ("dyn_num_trials_multiplier", C.c_double),
+                ("min_num_trials", C.c_int64), ("max_num_trials", C.c_int64)]
+
+
+class TriResult(C.Structure):
+    _fields_ = [("ntracks", C.c_size_t), ("nobs", C.c_size_t), ("xyz", C.POINTER(C.c_double)),
+                ("success", C.POINTER(C.c_uint8)), ("num_inliers", C.POINTER(C.c_uint32)),
+                ("num_trials", C.POINTER(C.c_uint64)), ("inlier_mask", C.POINTER(C.c_uint8)),
+                ("device_ms", C.c_double), ("kernel_ms", C.c_double), ("num_batches", C.c_uint32),
+                ("_priv", C.c_void_p)]
+
+
 SIFT_NORMALIZATIONS = {"L1_ROOT": 0, "L2": 1}
 SIFT_STAGES = ("scale_space", "detection", "orientation", "descriptors")
 
@@ -241,6 +255,14 @@ def load() -> C.CDLL:
         lib.amc_sift_result_free.argtypes = [C.POINTER(SiftResult)]
         lib.amc_sift_result_free.restype = None
     lib.amc_match_opts_default.restype = None
+    if hasattr(lib, "amc_triangulate_tracks"):  # (absent from a library built from an older revision)
+        lib.amc_tri_opts_default.argtypes = [C.POINTER(TriOpts)]
+        lib.amc_tri_opts_default.restype = None
+        lib.amc_triangulate_tracks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                               C.c_void_p, C.POINTER(TriOpts), C.POINTER(TriResult)]
+        lib.amc_triangulate_tracks.restype = C.c_int
+        lib.amc_tri_result_free.argtypes = [C.POINTER(TriResult)]
+        lib.amc_tri_result_free.restype = None
     lib.amc_get_acos_lut.argtypes = [C.c_void_p, C.c_void_p]
     lib.amc_tvg_opts_default.argtypes = [C.POINTER(TvgOpts)]
     lib.amc_tvg_opts_default.restype = None
@@ -587,6 +609,46 @@ class Context:
             self._lib.amc_sift_result_free(C.byref(res))
         out = [(kp[off[i]:off[i + 1]], desc[off[i]:off[i + 1]]) for i in range(len(imgs))]
         return (out[0] if single else out), stats
+
+    def triangulate_tracks(self, poses, track_offsets, obs_pose, obs_xy, **opts):
+        """amc_triangulate_tracks: one LO-RANSAC triangulation per track.
+        poses: (P, 3, 4) float64 cam_from_world [R | t]; track_offsets: (T + 1,) CSR over the observations;
+        obs_pose: (M,) pose index per observation; obs_xy: (M, 2) normalized image coordinates.  Keyword options
+        are amc_tri_opts fields (min_tri_angle, max_error, min_inlier_ratio, confidence, dyn_num_trials_multiplier,
+        min_num_trials, max_num_trials); the rest keep amc_tri_opts_default.  Returns (xyz (T, 3) float64,
+        success (T,) bool, inlier_mask (M,) bool, stats dict with num_inliers, num_trials, device_ms, kernel_ms,
+        num_batches)."""
+        P = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+        off = np.ascontiguousarray(track_offsets, dtype=np.uint64).reshape(-1)
+        if off.size < 1:
+            raise ValueError("triangulate_tracks: track_offsets needs ntracks + 1 entries")
+        nobs = int(off[-1])
+        op = np.ascontiguousarray(obs_pose, dtype=np.uint32).reshape(-1)
+        xy = np.ascontiguousarray(obs_xy, dtype=np.float64).reshape(-1, 2)
+        if op.size != nobs or xy.shape[0] != nobs:
+            raise ValueError(f"triangulate_tracks: {nobs} observations by track_offsets, {op.size} pose indices, "
+                             f"{xy.shape[0]} points")
+        o = TriOpts()
+        self._lib.amc_tri_opts_default(C.byref(o))
+        for k, v in opts.items():
+            if k not in dict(TriOpts._fields_):
+                raise ValueError(f"triangulate_tracks: unknown option {k!r}")
+            setattr(o, k, type(getattr(o, k))(v))
+        nt = off.size - 1
+        res = TriResult()
+        _check(self._lib.amc_triangulate_tracks(self._h, P.ctypes.data_as(C.c_void_p), P.shape[0],
+                                                 off.ctypes.data_as(C.c_void_p), nt, op.ctypes.data_as(C.c_void_p),
+                                                 xy.ctypes.data_as(C.c_void_p), C.byref(o), C.byref(res)))
+        try:
+            xyz = np.ctypeslib.as_array(res.xyz, (max(nt, 1), 3))[:nt].copy()
+            ok = np.ctypeslib.as_array(res.success, (max(nt, 1),))[:nt].astype(bool)
+            mask = np.ctypeslib.as_array(res.inlier_mask, (max(nobs, 1),))[:nobs].astype(bool)
+            stats = {"num_inliers": np.ctypeslib.as_array(res.num_inliers, (max(nt, 1),))[:nt].copy(),
+                     "num_trials": np.ctypeslib.as_array(res.num_trials, (max(nt, 1),))[:nt].copy(),
+                     "device_ms": res.device_ms, "kernel_ms": res.kernel_ms, "num_batches": int(res.num_batches)}
+        finally:
+            self._lib.amc_tri_result_free(C.byref(res))
+        return xyz, ok, mask, stats
 
     def match_pairs(self, slot1, slot2, max_ratio: float = 0.8, max_distance: float = 0.7,
                     cross_check: bool = True, kernel: str = "auto", copy: bool = True):

@@ -35,6 +35,7 @@
 #include "py_types.h"
 #include "estimators.h"
 #include "sift_host.h"
+#include "tri_host.h"
 
 namespace py = pybind11;
 using namespace pybind11::literals;
@@ -880,6 +881,50 @@ PYBIND11_MODULE(_pycolmap, m) {
                << im.name << "\", triangulated=0/" << im.keypoints.size() << ")";
             return ss.str();
         });
+
+    // ---- estimate_triangulation (/root/reference/pycolmap/estimators/triangulation.h; tri_host.h) ----------------------
+    py::class_<TriPointData>(m, "PointData")
+        .def(py::init([](const std::array<double, 2>& point, const std::array<double, 2>& point_normalized) {
+                 return TriPointData{point, point_normalized};
+             }),
+             "point"_a, "point_normalized"_a)
+        .def_readwrite("point", &TriPointData::point, "Pixel coordinates of the observation.")
+        .def_readwrite("point_normalized", &TriPointData::point_normalized,
+                       "Normalized image coordinates (Camera.cam_from_img of the pixel).")
+        .def("__repr__", [](const TriPointData& d) {
+            std::ostringstream ss;
+            ss.precision(17);
+            ss << "PointData(point=[" << d.point[0] << ", " << d.point[1] << "], point_normalized=["
+               << d.point_normalized[0] << ", " << d.point_normalized[1] << "])";
+            return ss.str();
+        });
+    const py::object py_ransac_cls = m.attr("RANSACOptions");
+    py::class_<EstimateTriangulationOptions> PyTriOpts(m, "EstimateTriangulationOptions");
+    PyTriOpts
+        .def(py::init([py_ransac_cls]() {
+            EstimateTriangulationOptions o;  // the RANSACOptions of pycolmap's Python-side defaults
+            o.ransac = py_ransac_cls().cast<RANSACOptions>();
+            return o;
+        }))
+        .def_readwrite("min_tri_angle", &EstimateTriangulationOptions::min_tri_angle,
+                       "Minimum triangulation angle in radians.")
+        .def_readwrite("ransac", &EstimateTriangulationOptions::ransac,
+                       "RANSAC options; max_error is the angular error in radians.");
+    MakeDataclass(PyTriOpts, {"min_tri_angle", "ransac"});
+    const EstimateTriangulationOptions tri_defaults = PyTriOpts().cast<EstimateTriangulationOptions>();
+    m.def(
+        "estimate_triangulation",
+        [](const std::vector<TriPointData>& point_data, const std::vector<PyImage>& images,
+           const std::vector<PyCamera>& cameras, const EstimateTriangulationOptions& options) -> py::object {
+            CheckSameSize(images.size(), cameras.size(), "images.size() == cameras.size()");
+            CheckSameSize(images.size(), point_data.size(), "images.size() == point_data.size()");
+            std::vector<std::array<double, 12>> poses;
+            poses.reserve(images.size());
+            for (const PyImage& im : images) poses.push_back(TriPoseMatrix(im.cam_from_world));
+            return EstimateTriangulationTrack(point_data, poses, options);
+        },
+        "point_data"_a, "images"_a, "cameras"_a, "opions"_a = tri_defaults,
+        "Robustly estimate 3D point from observations in multiple views using RANSAC");
 
     // ---- Database ---------------------------------------------------------------------------
     py::class_<Database>(m, "Database")

@@ -1,0 +1,587 @@
+// tri.hip — track triangulation on gfx950 (include/amc_tri.h): COLMAP 3.9.1's EstimateTriangulation with the angular
+// residual, one LO-RANSAC per track, restated in DESIGN.md section 11.  Every FP64 operation below is written in the
+// order of that section, the order tests/tri_ref/tri_ref.cc follows too: the two are bit-identical.  acos is the
+// project's own (+ - * /, correctly rounded sqrt), both eigen problems use the round-robin Jacobi solver of D1
+// (pose_math.h), and the dynamic trial count comes from a host-built table (host libm), as in verification.
+//
+// Work split: one lane runs one track's whole RANSAC.  The host orders each batch's tracks by length, longest first
+// (a counting sort, "binning"), so that the 64 tracks of a wave have the same length and finish together; a track's
+// result depends on its own observations only, never on its neighbours, the batch or the order.  No atomics, no LDS,
+// no scratch: the lane's state is a few dozen registers, and the inlier set of a local optimisation is kept in the
+// track's own bytes of the output mask until the final mask overwrites them.
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "amc_internal.h"
+#include "pose_math.h"
+#include "../../include/amc_tri.h"
+
+using namespace amc;
+
+namespace {
+
+using tvg::dsqrt;
+
+constexpr double kPi = 3.14159265358979311600e+00;  // M_PI
+constexpr uint64_t kNoTable = ~(uint64_t)0;
+constexpr int kBlock = 256;
+// device batch bounds: a call with more observations or tracks is split into several launches on the same buffers
+constexpr uint64_t kMaxBatchObs = (uint64_t)1 << 23;
+constexpr uint64_t kMaxBatchTracks = (uint64_t)1 << 20;
+
+// one pose: cam_from_world [R | t] row-major, the projection centre -R^T t, padding to 128 bytes
+struct TriPose {
+    double P[12];
+    double C[3];
+    double pad;
+};
+
+struct TriParams {
+    const uint64_t* off;      // batch tracks + 1: the caller's observation offsets (obs_base = the batch's first)
+    const uint32_t* order;    // batch tracks: batch-local track index, longest tracks first
+    const uint32_t* pose;     // the batch's observations, batch-local index
+    const double* xy;         // 2 per observation
+    const TriPose* poses;
+    const uint64_t* dyn_off;  // by track length (< dyn_n): start of its dyn_max_num_trials row in dyn_tab, or kNoTable
+    const uint64_t* dyn_tab;  // row of length n: ComputeNumTrials(num_inliers, n) for num_inliers = 0 .. n
+    uint64_t dyn_n;
+    uint64_t obs_base;
+    uint32_t ntracks;
+    double max_residual;      // max_error^2
+    double min_tri_angle;
+    uint64_t min_trials;
+    uint64_t max_trials;      // RANSACOptions::max_num_trials after the RANSAC constructor's clamp
+    double* xyz;              // batch tracks x 3
+    uint32_t* num_inliers;
+    uint64_t* num_trials;
+    uint8_t* success;
+    uint8_t* mask;            // the batch's observations
+};
+
+// ---- numerics ---------------------------------------------------------------------------------------
+// acos of fdlibm's e_acos.c (the rational approximation of asin on [0, 0.5] and its two reductions), written in
+// + - * / and sqrt; NaN outside [-1, 1]
+__device__ __forceinline__ double tri_acos_r(double z) {
+    const double p = z * (1.66666666666666657415e-01 +
+                          z * (-3.25565818622400915405e-01 +
+                               z * (2.01212532134862925881e-01 +
+                                    z * (-4.00555345006794114027e-02 +
+                                         z * (7.91534994289814532176e-04 + z * 3.47933107596021167570e-05)))));
+    const double q = 1.0 + z * (-2.40339491173441421878e+00 +
+                                z * (2.02094576023350569471e+00 +
+                                     z * (-6.88283971605453293030e-01 + z * 7.70381505559019352791e-02)));
+    return p / q;
+}
+__device__ __forceinline__ double tri_acos(double x) {
+    const double pio2_hi = 1.57079632679489655800e+00, pio2_lo = 6.12323399573676603587e-17;
+    const double ax = x < 0.0 ? -x : x;
+    if (!(ax <= 1.0)) return __builtin_nan("");
+    if (x == 1.0) return 0.0;
+    if (x == -1.0) return kPi;
+    if (ax < 0.5) return pio2_hi - (x - (pio2_lo - x * tri_acos_r(x * x)));
+    if (x < 0.0) {
+        const double z = (1.0 + x) * 0.5;
+        const double s = dsqrt(z);
+        const double w = tri_acos_r(z) * s - pio2_lo;
+        return kPi - 2.0 * (s + w);
+    }
+    const double z = (1.0 - x) * 0.5;
+    const double s = dsqrt(z);
+    return 2.0 * (s + s * tri_acos_r(z));
+}
+
+// CalculateTriangulationAngle: law of cosines, min(angle, pi - angle); 0 for a zero denominator, NaN when the ratio
+// rounds outside [-1, 1]
+__device__ __forceinline__ double tri_angle(const double* c1, const double* c2, const double* X) {
+    const double b0 = c1[0] - c2[0], b1 = c1[1] - c2[1], b2 = c1[2] - c2[2];
+    const double baseline2 = b0 * b0 + b1 * b1 + b2 * b2;
+    const double r0 = X[0] - c1[0], r1 = X[1] - c1[1], r2 = X[2] - c1[2];
+    const double ray1 = r0 * r0 + r1 * r1 + r2 * r2;
+    const double s0 = X[0] - c2[0], s1 = X[1] - c2[1], s2 = X[2] - c2[2];
+    const double ray2 = s0 * s0 + s1 * s1 + s2 * s2;
+    const double den = 2.0 * dsqrt(ray1 * ray2);
+    if (den == 0.0) return 0.0;
+    const double nom = ray1 + ray2 - baseline2;
+    const double a = tri_acos(nom / den);
+    const double angle = a < 0.0 ? -a : a;
+    const double other = kPi - angle;
+    return other < angle ? other : angle;  // std::min(angle, pi - angle)
+}
+
+// P.row(2) . [X; 1]
+__device__ __forceinline__ double tri_depth(const double* P, const double* X) {
+    return P[8] * X[0] + P[9] * X[1] + P[10] * X[2] + P[11];
+}
+
+// squared angular error of observation (x, y) under pose P for the point X
+__device__ __forceinline__ double tri_residual(double x, double y, const double* P, const double* X) {
+    const double na = dsqrt(x * x + y * y + 1.0);
+    const double a0 = x / na, a1 = y / na, a2 = 1.0 / na;
+    const double q0 = P[0] * X[0] + P[1] * X[1] + P[2] * X[2] + P[3];
+    const double q1 = P[4] * X[0] + P[5] * X[1] + P[6] * X[2] + P[7];
+    const double q2 = P[8] * X[0] + P[9] * X[1] + P[10] * X[2] + P[11];
+    const double nb = dsqrt(q0 * q0 + q1 * q1 + q2 * q2);
+    const double c = a0 * (q0 / nb) + a1 * (q1 / nb) + a2 * (q2 / nb);
+    const double e = tri_acos(c);
+    return e * e;
+}
+
+// eigenvector of the smallest eigenvalue of the symmetric 4 x 4 `a` (first minimum of the Jacobi diagonal), dehomogenised
+__device__ __forceinline__ void tri_smallest_dehom(double (&a)[16], double* X) {
+    double v[16];
+    tvg::jacobi_eigen_t<4>(a, v);
+    double dmin = a[0];
+    double e0 = v[0], e1 = v[4], e2 = v[8], w = v[12];
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+        if (a[5 * i] < dmin) { dmin = a[5 * i]; e0 = v[i]; e1 = v[4 + i]; e2 = v[8 + i]; w = v[12 + i]; }
+    X[0] = e0 / w; X[1] = e1 / w; X[2] = e2 / w;
+}
+
+// ---- the estimator ------------------------------------------------------------------------------------
+// two observations: DLT rows x P2 - P0, y P2 - P1 of both views, A^T A, smallest eigenvector; then both depths and the
+// angle
+__device__ __forceinline__ bool tri_estimate_two(const TriParams& p, uint64_t i, uint64_t j, double* X) {
+    const double xi = p.xy[2 * i], yi = p.xy[2 * i + 1], xj = p.xy[2 * j], yj = p.xy[2 * j + 1];
+    const TriPose& Pi = p.poses[p.pose[i]];
+    const TriPose& Pj = p.poses[p.pose[j]];
+    double A[4][4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        A[0][c] = xi * Pi.P[8 + c] - Pi.P[c];
+        A[1][c] = yi * Pi.P[8 + c] - Pi.P[4 + c];
+        A[2][c] = xj * Pj.P[8 + c] - Pj.P[c];
+        A[3][c] = yj * Pj.P[8 + c] - Pj.P[4 + c];
+    }
+    double ata[16];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s += A[k][r] * A[k][c];
+            ata[4 * r + c] = s;
+        }
+    tri_smallest_dehom(ata, X);
+    return tri_depth(Pi.P, X) >= DBL_EPSILON && tri_depth(Pj.P, X) >= DBL_EPSILON &&
+           tri_angle(Pi.C, Pj.C, X) >= p.min_tri_angle;
+}
+
+// (observation indices below are batch-local)
+// the local estimator on the inlier set marked in mask[o0 .. o0 + n) (cnt >= 2 members): two members -> the two-view
+// estimator; more -> A = sum term^T term, term = P - p p^T P, p = normalized([x, y, 1]); every depth, then any pair
+// (i, j < i) with the angle
+__device__ __forceinline__ bool tri_estimate_set(const TriParams& p, uint64_t o0, uint64_t n, uint32_t cnt, double* X) {
+    const uint8_t* set = p.mask + o0;
+    if (cnt == 2) {
+        uint64_t i = 0;
+        while (!set[i]) ++i;
+        uint64_t j = i + 1;
+        while (!set[j]) ++j;
+        return tri_estimate_two(p, o0 + i, o0 + j, X);
+    }
+    double A[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) A[k] = 0.0;
+    for (uint64_t k = 0; k < n; ++k) {
+        if (!set[k]) continue;
+        const uint64_t o = o0 + k;
+        const double x = p.xy[2 * o], y = p.xy[2 * o + 1];
+        const double* P = p.poses[p.pose[o]].P;
+        const double nrm = dsqrt(x * x + y * y + 1.0);
+        const double h[3] = {x / nrm, y / nrm, 1.0 / nrm};
+        double T[3][4];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const double m = h[r] * h[0] * P[c] + h[r] * h[1] * P[4 + c] + h[r] * h[2] * P[8 + c];
+                T[r][c] = P[4 * r + c] - m;
+            }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) A[4 * r + c] = A[4 * r + c] + (T[0][r] * T[0][c] + T[1][r] * T[1][c] + T[2][r] * T[2][c]);
+    }
+    tri_smallest_dehom(A, X);
+    for (uint64_t k = 0; k < n; ++k)
+        if (set[k] && !(tri_depth(p.poses[p.pose[o0 + k]].P, X) >= DBL_EPSILON)) return false;
+    for (uint64_t i = 1; i < n; ++i) {
+        if (!set[i]) continue;
+        const double* ci = p.poses[p.pose[o0 + i]].C;
+        for (uint64_t j = 0; j < i; ++j) {
+            if (!set[j]) continue;
+            if (tri_angle(ci, p.poses[p.pose[o0 + j]].C, X) >= p.min_tri_angle) return true;
+        }
+    }
+    return false;
+}
+
+// InlierSupportMeasurer::Evaluate: inliers have residual <= max_residual (NaN is an outlier); the residual sum adds
+// the inliers' residuals in observation order.  mark: also write the inlier flags to the track's mask bytes.
+struct TriSupport {
+    uint32_t cnt;
+    double sum;
+};
+__device__ __forceinline__ TriSupport tri_score(const TriParams& p, uint64_t o0, uint64_t n, const double* X, bool mark) {
+    TriSupport s{0u, 0.0};
+    uint8_t* m = p.mask + o0;
+    for (uint64_t k = 0; k < n; ++k) {
+        const uint64_t o = o0 + k;
+        const double r = tri_residual(p.xy[2 * o], p.xy[2 * o + 1], p.poses[p.pose[o]].P, X);
+        const bool in = r <= p.max_residual;
+        if (in) {
+            s.cnt += 1;
+            s.sum += r;
+        }
+        if (mark) m[k] = in ? 1 : 0;
+    }
+    return s;
+}
+__device__ __forceinline__ bool tri_better(const TriSupport a, const TriSupport b) {
+    return a.cnt > b.cnt || (a.cnt == b.cnt && a.sum < b.sum);
+}
+
+// ---- LORANSAC<TriangulationEstimator x 2, InlierSupportMeasurer, CombinationSampler> -----------------
+__global__ __launch_bounds__(kBlock) void tri_kernel(TriParams p) {
+    const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+    if (g >= p.ntracks) return;
+    const uint32_t t = p.order[g];
+    const uint64_t o0 = p.off[t] - p.obs_base, n = p.off[t + 1] - p.off[t];
+    uint8_t* mask = p.mask + o0;
+    double best_xyz[3] = {0.0, 0.0, 0.0};
+    TriSupport best{0u, DBL_MAX};
+    uint64_t trial = 0;
+    if (n >= 2) {
+        const uint64_t combos = n * (n - 1) / 2;
+        const uint64_t max_trials = p.max_trials < combos ? p.max_trials : combos;
+        const uint64_t tab = n < p.dyn_n ? p.dyn_off[n] : kNoTable;
+        uint64_t dyn_max = max_trials;
+        uint64_t a = 0, b = 1;  // the next pair of the lexicographic combination order
+        bool abort = false;
+        for (trial = 0; trial < max_trials; ++trial) {
+            if (abort) {
+                trial += 1;
+                break;
+            }
+            const uint64_t i = a, j = b;
+            if (++b == n) {
+                ++a;
+                b = a + 1;
+                if (b == n) { a = 0; b = 1; }
+            }
+            double X[3];
+            if (!tri_estimate_two(p, o0 + i, o0 + j, X)) continue;
+            const TriSupport s = tri_score(p, o0, n, X, false);
+            if (tri_better(s, best)) {
+                best = s;
+                best_xyz[0] = X[0]; best_xyz[1] = X[1]; best_xyz[2] = X[2];
+                if (s.cnt > 2) {
+                    for (int lt = 0; lt < 10; ++lt) {
+                        const uint32_t prev = best.cnt;
+                        // the inlier set of the current best model, in the mask bytes
+                        const TriSupport cur = tri_score(p, o0, n, best_xyz, true);
+                        double L[3];
+                        if (tri_estimate_set(p, o0, n, cur.cnt, L)) {
+                            const TriSupport ls = tri_score(p, o0, n, L, false);
+                            if (tri_better(ls, best)) {
+                                best = ls;
+                                best_xyz[0] = L[0]; best_xyz[1] = L[1]; best_xyz[2] = L[2];
+                            }
+                        }
+                        if (best.cnt <= prev) break;
+                    }
+                }
+                dyn_max = tab == kNoTable ? kNoTable : p.dyn_tab[tab + best.cnt];
+            }
+            if (trial >= dyn_max && trial >= p.min_trials) abort = true;
+        }
+    }
+    const bool ok = best.cnt >= 2;
+    if (ok) {
+        tri_score(p, o0, n, best_xyz, true);
+    } else {
+        for (uint64_t k = 0; k < n; ++k) mask[k] = 0;
+    }
+    p.xyz[3 * t] = ok ? best_xyz[0] : 0.0;
+    p.xyz[3 * t + 1] = ok ? best_xyz[1] : 0.0;
+    p.xyz[3 * t + 2] = ok ? best_xyz[2] : 0.0;
+    p.num_inliers[t] = best.cnt;
+    p.num_trials[t] = trial;
+    p.success[t] = ok ? 1 : 0;
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+#define TRI_HIPCHK(expr)                                                                                     \
+    do {                                                                                                     \
+        hipError_t e_ = (expr);                                                                              \
+        if (e_ != hipSuccess)                                                                                \
+            return api_fail(AMC_E_HIP, "amc_triangulate_tracks: %s:%d: %s -> %s", __FILE__, __LINE__, #expr,  \
+                            hipGetErrorString(e_));                                                          \
+    } while (0)
+
+struct DevMem {
+    void* p = nullptr;
+    ~DevMem() {
+        if (p) (void)hipFree(p);
+    }
+};
+
+struct Events {
+    hipEvent_t a = nullptr, b = nullptr;
+    std::vector<hipEvent_t> k;  // around each batch's kernel
+    ~Events() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+        for (hipEvent_t e : k)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// colmap/optim/ransac.h ComputeNumTrials with kMinNumSamples = 2 (host libm, as oracle/tvg_oracle.cc has it)
+uint64_t compute_num_trials(uint64_t num_inliers, uint64_t num_samples, double confidence, double multiplier) {
+    const double inlier_ratio = num_inliers / static_cast<double>(num_samples);
+    const double nom = 1 - confidence;
+    if (nom <= 0) return ~(uint64_t)0;
+    const double denom = 1 - std::pow(inlier_ratio, 2);
+    if (denom <= 0) return 1;
+    if (denom == 1.0) return ~(uint64_t)0;
+    return static_cast<uint64_t>(std::ceil(std::log(nom) / std::log(denom) * multiplier));
+}
+
+}  // namespace
+
+extern "C" {
+
+void amc_tri_opts_default(amc_tri_opts* o) {
+    if (!o) return;
+    o->min_tri_angle = 0.0;  // EstimateTriangulationOptions() with pycolmap's RANSACOptions()
+    o->max_error = 4.0;
+    o->min_inlier_ratio = 0.01;
+    o->confidence = 0.9999;
+    o->dyn_num_trials_multiplier = 3.0;
+    o->min_num_trials = 1000;
+    o->max_num_trials = 100000;
+}
+
+void amc_tri_result_free(amc_tri_result* r) {
+    if (!r) return;
+    std::free(r->xyz);
+    std::free(r->success);
+    std::free(r->num_inliers);
+    std::free(r->num_trials);
+    std::free(r->inlier_mask);
+    std::memset(r, 0, sizeof *r);
+}
+
+static int triangulate_impl(amc_ctx* ctx, const double* poses, size_t nposes, const uint64_t* track_offsets,
+                            size_t ntracks, const uint32_t* obs_pose, const double* obs_xy, const amc_tri_opts* opts,
+                            amc_tri_result* result) {
+    if (!ctx || !opts || !result || !track_offsets || (nposes && !poses))
+        return api_fail(AMC_E_INVALID, "amc_triangulate_tracks: NULL argument");
+    std::memset(result, 0, sizeof *result);
+    const amc_tri_opts op = *opts;
+    // EstimateTriangulationOptions::Check and RANSACOptions::Check
+    if (!(op.min_tri_angle >= 0.0) || !(op.max_error > 0.0) || !(op.min_inlier_ratio >= 0.0) ||
+        !(op.min_inlier_ratio <= 1.0) || !(op.confidence >= 0.0) || !(op.confidence <= 1.0) || op.min_num_trials < 0 ||
+        op.max_num_trials < 0 || op.min_num_trials > op.max_num_trials)
+        return api_fail(AMC_E_INVALID, "amc_triangulate_tracks: invalid options (min_tri_angle %g, max_error %g, "
+                        "min_inlier_ratio %g, confidence %g, min_num_trials %lld, max_num_trials %lld)",
+                        op.min_tri_angle, op.max_error, op.min_inlier_ratio, op.confidence,
+                        (long long)op.min_num_trials, (long long)op.max_num_trials);
+    if (track_offsets[0] != 0) return api_fail(AMC_E_INVALID, "amc_triangulate_tracks: track_offsets[0] != 0");
+    for (size_t i = 0; i < ntracks; ++i)
+        if (track_offsets[i + 1] < track_offsets[i])
+            return api_fail(AMC_E_INVALID, "amc_triangulate_tracks: track_offsets decrease at track %zu", i);
+    const uint64_t nobs = track_offsets[ntracks];
+    if (nobs && (!obs_pose || !obs_xy)) return api_fail(AMC_E_INVALID, "amc_triangulate_tracks: NULL observations");
+    for (uint64_t k = 0; k < nobs; ++k)
+        if (obs_pose[k] >= nposes)
+            return api_fail(AMC_E_INVALID, "amc_triangulate_tracks: observation %llu names pose %u of %zu",
+                            (unsigned long long)k, obs_pose[k], nposes);
+
+    result->ntracks = ntracks;
+    result->nobs = nobs;
+    result->xyz = static_cast<double*>(std::malloc(std::max<size_t>(ntracks, 1) * 3 * sizeof(double)));
+    result->success = static_cast<uint8_t*>(std::malloc(std::max<size_t>(ntracks, 1)));
+    result->num_inliers = static_cast<uint32_t*>(std::malloc(std::max<size_t>(ntracks, 1) * sizeof(uint32_t)));
+    result->num_trials = static_cast<uint64_t*>(std::malloc(std::max<size_t>(ntracks, 1) * sizeof(uint64_t)));
+    result->inlier_mask = static_cast<uint8_t*>(std::malloc(std::max<uint64_t>(nobs, 1)));
+    if (!result->xyz || !result->success || !result->num_inliers || !result->num_trials || !result->inlier_mask) {
+        amc_tri_result_free(result);
+        return api_fail(AMC_E_NOMEM, "amc_triangulate_tracks: out of host memory for %zu tracks", ntracks);
+    }
+    if (ntracks == 0) return AMC_OK;
+
+    // the pose table with its centres
+    std::vector<TriPose> tab(std::max<size_t>(nposes, 1));
+    for (size_t i = 0; i < nposes; ++i) {
+        TriPose& q = tab[i];
+        std::memcpy(q.P, poses + 12 * i, sizeof q.P);
+        for (int c = 0; c < 3; ++c) q.C[c] = -(q.P[c] * q.P[3] + q.P[4 + c] * q.P[7] + q.P[8 + c] * q.P[11]);
+        q.pad = 0.0;
+    }
+    // the RANSAC constructor's clamp of max_num_trials by min_inlier_ratio
+    const uint64_t kNumSamples = 100000;
+    const uint64_t max_trials = std::min<uint64_t>(
+        (uint64_t)op.max_num_trials, compute_num_trials((uint64_t)(op.min_inlier_ratio * kNumSamples), kNumSamples,
+                                                        op.confidence, op.dyn_num_trials_multiplier));
+    const uint64_t min_trials = (uint64_t)op.min_num_trials;
+
+    // dyn_max_num_trials rows for the track lengths whose RANSAC can stop early (more trials than min_num_trials)
+    uint64_t nmax = 0;
+    for (size_t i = 0; i < ntracks; ++i) nmax = std::max<uint64_t>(nmax, track_offsets[i + 1] - track_offsets[i]);
+    std::vector<uint64_t> dyn_off(nmax + 1, kNoTable), dyn_tab;
+    for (size_t i = 0; i < ntracks; ++i) {
+        const uint64_t n = track_offsets[i + 1] - track_offsets[i];
+        if (n < 2 || dyn_off[n] != kNoTable) continue;
+        const uint64_t combos = n * (n - 1) / 2;
+        if (std::min(max_trials, combos) <= min_trials) continue;
+        dyn_off[n] = dyn_tab.size();
+        for (uint64_t c = 0; c <= n; ++c)
+            dyn_tab.push_back(compute_num_trials(c, n, op.confidence, op.dyn_num_trials_multiplier));
+    }
+    if (dyn_tab.empty()) dyn_tab.push_back(0);
+
+    // batches: contiguous track ranges of at most kMaxBatchTracks tracks and kMaxBatchObs observations (a longer track
+    // is a batch of its own)
+    std::vector<size_t> bstart{0};
+    uint64_t max_bt = 0, max_bo = 0;
+    for (size_t i = 0; i < ntracks;) {
+        size_t j = i + 1;
+        while (j < ntracks && j - i < kMaxBatchTracks && track_offsets[j + 1] - track_offsets[i] <= kMaxBatchObs) ++j;
+        max_bt = std::max<uint64_t>(max_bt, j - i);
+        max_bo = std::max<uint64_t>(max_bo, track_offsets[j] - track_offsets[i]);
+        bstart.push_back(j);
+        i = j;
+    }
+    const size_t nbatch = bstart.size() - 1;
+    max_bo = std::max<uint64_t>(max_bo, 1);
+
+    // one device allocation: constants, then the batch buffers
+    const size_t sz_pose = align256(tab.size() * sizeof(TriPose)), sz_doff = align256(dyn_off.size() * 8),
+                 sz_dtab = align256(dyn_tab.size() * 8), sz_off = align256((max_bt + 1) * 8),
+                 sz_ord = align256(max_bt * 4), sz_opose = align256(max_bo * 4), sz_xy = align256(max_bo * 16),
+                 sz_xyz = align256(max_bt * 24), sz_ninl = align256(max_bt * 4), sz_ntr = align256(max_bt * 8),
+                 sz_succ = align256(max_bt), sz_mask = align256(max_bo);
+    const size_t total = sz_pose + sz_doff + sz_dtab + sz_off + sz_ord + sz_opose + sz_xy + sz_xyz + sz_ninl + sz_ntr +
+                         sz_succ + sz_mask;
+    const CtxView cv = ctx_view(ctx);
+    TRI_HIPCHK(hipSetDevice(cv.device));
+    hipStream_t st = cv.stream;
+    Events ev;
+    TRI_HIPCHK(hipEventCreate(&ev.a));
+    TRI_HIPCHK(hipEventCreate(&ev.b));
+    TRI_HIPCHK(hipEventRecord(ev.a, st));
+    DevMem mem;
+    TRI_HIPCHK(hipMalloc(&mem.p, total));
+    char* base = static_cast<char*>(mem.p);
+    size_t at = 0;
+    auto carve = [&](size_t bytes) {
+        char* q = base + at;
+        at += bytes;
+        return q;
+    };
+    TriPose* d_pose = reinterpret_cast<TriPose*>(carve(sz_pose));
+    uint64_t* d_doff = reinterpret_cast<uint64_t*>(carve(sz_doff));
+    uint64_t* d_dtab = reinterpret_cast<uint64_t*>(carve(sz_dtab));
+    uint64_t* d_off = reinterpret_cast<uint64_t*>(carve(sz_off));
+    uint32_t* d_ord = reinterpret_cast<uint32_t*>(carve(sz_ord));
+    uint32_t* d_opose = reinterpret_cast<uint32_t*>(carve(sz_opose));
+    double* d_xy = reinterpret_cast<double*>(carve(sz_xy));
+    double* d_xyz = reinterpret_cast<double*>(carve(sz_xyz));
+    uint32_t* d_ninl = reinterpret_cast<uint32_t*>(carve(sz_ninl));
+    uint64_t* d_ntr = reinterpret_cast<uint64_t*>(carve(sz_ntr));
+    uint8_t* d_succ = reinterpret_cast<uint8_t*>(carve(sz_succ));
+    uint8_t* d_mask = reinterpret_cast<uint8_t*>(carve(sz_mask));
+    TRI_HIPCHK(hipMemcpyAsync(d_pose, tab.data(), tab.size() * sizeof(TriPose), hipMemcpyHostToDevice, st));
+    TRI_HIPCHK(hipMemcpyAsync(d_doff, dyn_off.data(), dyn_off.size() * 8, hipMemcpyHostToDevice, st));
+    TRI_HIPCHK(hipMemcpyAsync(d_dtab, dyn_tab.data(), dyn_tab.size() * 8, hipMemcpyHostToDevice, st));
+
+    std::vector<std::vector<uint32_t>> orders(nbatch);  // host copies stay alive until the stream is drained
+    for (size_t bi = 0; bi < nbatch; ++bi) {
+        const size_t t0 = bstart[bi], t1 = bstart[bi + 1], nt = t1 - t0;
+        const uint64_t ob = track_offsets[t0], no = track_offsets[t1] - ob;
+        // counting sort by length, longest first (lengths above 64 share the first bin, in track order)
+        constexpr int kBins = 66;
+        size_t cnt[kBins + 1] = {};
+        auto bin_of = [&](size_t t) {
+            const uint64_t n = track_offsets[t + 1] - track_offsets[t];
+            return n > 64 ? 0 : (int)(65 - n);
+        };
+        for (size_t t = t0; t < t1; ++t) cnt[bin_of(t) + 1] += 1;
+        for (int b = 0; b < kBins; ++b) cnt[b + 1] += cnt[b];
+        std::vector<uint32_t>& ord = orders[bi];
+        ord.resize(nt);
+        for (size_t t = t0; t < t1; ++t) ord[cnt[bin_of(t)]++] = (uint32_t)(t - t0);
+
+        TRI_HIPCHK(hipMemcpyAsync(d_off, track_offsets + t0, (nt + 1) * 8, hipMemcpyHostToDevice, st));
+        TRI_HIPCHK(hipMemcpyAsync(d_ord, ord.data(), nt * 4, hipMemcpyHostToDevice, st));
+        if (no) {
+            TRI_HIPCHK(hipMemcpyAsync(d_opose, obs_pose + ob, no * 4, hipMemcpyHostToDevice, st));
+            TRI_HIPCHK(hipMemcpyAsync(d_xy, obs_xy + 2 * ob, no * 16, hipMemcpyHostToDevice, st));
+        }
+        TriParams p{};
+        p.off = d_off;
+        p.order = d_ord;
+        p.pose = d_opose;
+        p.xy = d_xy;
+        p.poses = d_pose;
+        p.dyn_off = d_doff;
+        p.dyn_tab = d_dtab;
+        p.dyn_n = dyn_off.size();
+        p.obs_base = ob;
+        p.ntracks = (uint32_t)nt;
+        p.max_residual = op.max_error * op.max_error;
+        p.min_tri_angle = op.min_tri_angle;
+        p.min_trials = min_trials;
+        p.max_trials = max_trials;
+        p.xyz = d_xyz;
+        p.num_inliers = d_ninl;
+        p.num_trials = d_ntr;
+        p.success = d_succ;
+        p.mask = d_mask;
+        ev.k.push_back(nullptr);
+        TRI_HIPCHK(hipEventCreate(&ev.k.back()));
+        ev.k.push_back(nullptr);
+        TRI_HIPCHK(hipEventCreate(&ev.k.back()));
+        TRI_HIPCHK(hipEventRecord(ev.k[2 * bi], st));
+        hipLaunchKernelGGL(tri_kernel, dim3((unsigned)((nt + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, p);
+        TRI_HIPCHK(hipGetLastError());
+        TRI_HIPCHK(hipEventRecord(ev.k[2 * bi + 1], st));
+        TRI_HIPCHK(hipMemcpyAsync(result->xyz + 3 * t0, d_xyz, nt * 24, hipMemcpyDeviceToHost, st));
+        TRI_HIPCHK(hipMemcpyAsync(result->num_inliers + t0, d_ninl, nt * 4, hipMemcpyDeviceToHost, st));
+        TRI_HIPCHK(hipMemcpyAsync(result->num_trials + t0, d_ntr, nt * 8, hipMemcpyDeviceToHost, st));
+        TRI_HIPCHK(hipMemcpyAsync(result->success + t0, d_succ, nt, hipMemcpyDeviceToHost, st));
+        if (no) TRI_HIPCHK(hipMemcpyAsync(result->inlier_mask + ob, d_mask, no, hipMemcpyDeviceToHost, st));
+    }
+    TRI_HIPCHK(hipEventRecord(ev.b, st));
+    TRI_HIPCHK(hipEventSynchronize(ev.b));
+    float ms = 0.f;
+    TRI_HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
+    result->device_ms = ms;
+    result->kernel_ms = 0.0;
+    for (size_t bi = 0; bi < nbatch; ++bi) {
+        TRI_HIPCHK(hipEventElapsedTime(&ms, ev.k[2 * bi], ev.k[2 * bi + 1]));
+        result->kernel_ms += ms;
+    }
+    result->num_batches = (uint32_t)nbatch;
+    return AMC_OK;
+}
+
+int amc_triangulate_tracks(amc_ctx* ctx, const double* poses, size_t nposes, const uint64_t* track_offsets,
+                           size_t ntracks, const uint32_t* obs_pose, const double* obs_xy, const amc_tri_opts* opts,
+                           amc_tri_result* result) {
+    const int rc = triangulate_impl(ctx, poses, nposes, track_offsets, ntracks, obs_pose, obs_xy, opts, result);
+    if (rc != AMC_OK && result) amc_tri_result_free(result);  // no partial results
+    return rc;
+}
+
+}  // extern "C"

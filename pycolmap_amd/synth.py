@@ -325,3 +325,46 @@ def tower_scene(rng, num_images=500, n_feats=4096, f=1200.0, width=1600, height=
                            model=1 if camera is None else CAMERA_MODEL_IDS[camera[0]], width=width, height=height,
                            params=(f, f, width / 2.0, height / 2.0) if camera is None else tuple(camera[1])))
     return images
+
+
+def triangulation_scene(rng, num_tracks, num_cameras=200, max_len=50, mean_len=4.0, noise_px=0.5, outlier_frac=0.1,
+                        f=1000.0, radius=8.0, extent=2.0):
+    """Tracks for known-pose triangulation: `num_cameras` cameras on a sphere of `radius` looking at the origin, points
+    uniform in a cube of half-size `extent`, track lengths 2 + geometric (skewed short, mean about `mean_len`) capped
+    at `max_len`, distinct cameras per track, `noise_px` pixel noise at focal length `f` and a fraction `outlier_frac`
+    of observations replaced by uniform points of a 1000 x 1000 px image.  Returns a dict: poses (C, 3, 4)
+    cam_from_world, offsets (T + 1,) uint64, obs_pose (M,) uint32, obs_xy (M, 2) normalized, xyz (T, 3), outlier (M,)
+    bool."""
+    C = int(num_cameras)
+    d = rng.normal(size=(C, 3))
+    centers = radius * d / np.linalg.norm(d, axis=1, keepdims=True)
+    poses = np.zeros((C, 3, 4))
+    for i, c in enumerate(centers):
+        fwd = -c / np.linalg.norm(c)
+        up = np.array([0.0, 0.0, 1.0]) if abs(fwd[2]) < 0.9 else np.array([1.0, 0.0, 0.0])
+        right = np.cross(fwd, up)
+        right /= np.linalg.norm(right)
+        down = np.cross(fwd, right)
+        R = np.stack([right, down, fwd])
+        poses[i, :, :3] = R
+        poses[i, :, 3] = -R @ c
+    T = int(num_tracks)
+    lens = np.minimum(2 + rng.geometric(1.0 / max(mean_len - 1.0, 1.0), size=T) - 1, min(max_len, C)).astype(np.int64)
+    offsets = np.zeros(T + 1, np.uint64)
+    offsets[1:] = np.cumsum(lens)
+    M = int(offsets[-1])
+    track_of = np.repeat(np.arange(T), lens)
+    k = np.arange(M) - np.repeat(offsets[:-1].astype(np.int64), lens)
+    # distinct cameras: start + k * step (mod C) with step coprime to C
+    steps = np.array([s for s in range(1, C) if np.gcd(s, C) == 1])
+    start = rng.integers(0, C, size=T)
+    step = steps[rng.integers(0, len(steps), size=T)]
+    obs_pose = ((start[track_of] + k * step[track_of]) % C).astype(np.uint32)
+    xyz = rng.uniform(-extent, extent, size=(T, 3))
+    P = poses[obs_pose]
+    Xc = np.einsum("mij,mj->mi", P[:, :, :3], xyz[track_of]) + P[:, :, 3]
+    xy = Xc[:, :2] / Xc[:, 2:3] + rng.normal(scale=noise_px / f, size=(M, 2))
+    outlier = rng.random(M) < outlier_frac
+    xy[outlier] = rng.uniform(-500.0 / f, 500.0 / f, size=(int(outlier.sum()), 2))
+    return dict(poses=poses, offsets=offsets, obs_pose=obs_pose, obs_xy=np.ascontiguousarray(xy), xyz=xyz,
+                outlier=outlier)

@@ -1,8 +1,10 @@
 """`import pycolmap` for code written against the reference package: every name of the match + verify path
 (/root/reference/pycolmap/main.cc:91-118 registers them on the `pycolmap` module) and of SIFT feature extraction
 (`extract_features`, `Sift`, `SiftExtractionOptions`, `Normalization`, `ImageReaderOptions`, `CameraMode`) and of
-known-pose triangulation (`estimate_triangulation`, `PointData`, `EstimateTriangulationOptions`) resolves to
-pycolmap_amd's MI355X implementation.  Only what SURVEY.md section 8 and DESIGN.md sections 10 and 11 put in scope exists;
+known-pose triangulation (`estimate_triangulation`, `PointData`, `EstimateTriangulationOptions`) and of absolute pose
+(`absolute_pose_estimation`, `pose_refinement`, `AbsolutePoseEstimationOptions`, `AbsolutePoseRefinementOptions`)
+resolves to pycolmap_amd's MI355X implementation.  Only what SURVEY.md section 8 and DESIGN.md sections 10 to 12 put in
+scope exists;
 anything else raises AttributeError naming this package, so that a script reaching for `import_images`, SfM or MVS
 fails at the attribute, not later."""
 import pycolmap_amd as _impl
@@ -15,4 +17,4 @@ globals().update({n: getattr(_impl, n) for n in _PUBLIC})
 
 def __getattr__(name):
     raise AttributeError(f"pycolmap.{name} is outside pycolmap_amd's scope (SIFT feature extraction, exhaustive / sequential "
-                         f"matching + two-view verification, known-pose triangulation behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}")
+                         f"matching + two-view verification, known-pose triangulation, absolute pose behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}")

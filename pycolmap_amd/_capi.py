@@ -131,6 +131,73 @@ class SiftResult(C.Structure):
                 ("_priv", C.c_void_p)]
 
 
+class AbsPoseOpts(C.Structure):  # amc_abspose_opts (include/amc_abspose.h)
+    _fields_ = [("estimate_focal_length", C.c_int32), ("num_focal_length_samples", C.c_int32),
+                ("min_focal_length_ratio", C.c_double), ("max_focal_length_ratio", C.c_double),
+                ("max_error", C.c_double), ("min_inlier_ratio", C.c_double), ("confidence", C.c_double),
+                ("dyn_num_trials_multiplier", C.c_double), ("min_num_trials", C.c_int64),
+                ("max_num_trials", C.c_int64)]
+
+
+class AbsPoseRefineOpts(C.Structure):  # amc_abspose_refine_opts
+    _fields_ = [("gradient_tolerance", C.c_double), ("max_num_iterations", C.c_int64),
+                ("loss_function_scale", C.c_double), ("refine_focal_length", C.c_int32),
+                ("refine_extra_params", C.c_int32), ("print_summary", C.c_int32)]
+
+
+class AbsPoseResult(C.Structure):
+    _fields_ = [("nqueries", C.c_size_t), ("ncorr", C.c_size_t), ("success", C.POINTER(C.c_uint8)),
+                ("qvec", C.POINTER(C.c_double)), ("tvec", C.POINTER(C.c_double)),
+                ("num_inliers", C.POINTER(C.c_uint32)), ("num_trials", C.POINTER(C.c_uint64)),
+                ("focal_factor", C.POINTER(C.c_double)), ("covariance", C.POINTER(C.c_double)),
+                ("inlier_mask", C.POINTER(C.c_uint8)), ("device_ms", C.c_double), ("kernel_ms", C.c_double),
+                ("num_batches", C.c_uint32), ("_priv", C.c_void_p)]
+
+
+def abspose_options(estimation=None, refinement=None):
+    """amc_abspose_opts / amc_abspose_refine_opts at their defaults (the C defaults, no library needed) with the
+    given fields replaced; an unknown field raises ValueError."""
+    eo, ro = AbsPoseOpts(), AbsPoseRefineOpts()
+    for k, v in dict(estimate_focal_length=0, num_focal_length_samples=30, min_focal_length_ratio=0.1,
+                     max_focal_length_ratio=10.0, max_error=12.0, min_inlier_ratio=0.01, confidence=0.9999,
+                     dyn_num_trials_multiplier=3.0, min_num_trials=1000, max_num_trials=100000).items():
+        setattr(eo, k, v)
+    for k, v in dict(gradient_tolerance=1.0, max_num_iterations=100, loss_function_scale=1.0, refine_focal_length=0,
+                     refine_extra_params=0, print_summary=0).items():
+        setattr(ro, k, v)
+    for o, given in ((eo, estimation or {}), (ro, refinement or {})):
+        for k, v in given.items():
+            if k not in dict(type(o)._fields_):
+                raise ValueError(f"unknown absolute pose option {k!r}")
+            setattr(o, k, type(getattr(o, k))(v))
+    return eo, ro
+
+
+def abspose_inputs(offsets, camera_models, camera_params, points2D, points3D):
+    """The CSR batch of amc_estimate_absolute_poses as contiguous arrays: offsets (Q + 1,) uint64, models (Q,) int32,
+    params (Q, 12) float64 (each camera's parameters first), points2D (N, 2), points3D (N, 3)."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    if off.size < 1:
+        raise ValueError("absolute poses: offsets needs nqueries + 1 entries")
+    nq, n = off.size - 1, int(off[-1])
+    models = np.ascontiguousarray(camera_models, dtype=np.int32).reshape(-1)
+    if models.size != nq or len(camera_params) != nq:
+        raise ValueError(f"absolute poses: {nq} queries by offsets, {models.size} camera models, "
+                         f"{len(camera_params)} parameter sets")
+    prm = np.zeros((nq, 12), np.float64)
+    for i, p in enumerate(camera_params):
+        p = np.asarray(p, dtype=np.float64).reshape(-1)
+        if p.size > 12:
+            raise ValueError(f"absolute poses: camera {i} has {p.size} parameters (at most 12)")
+        prm[i, :p.size] = p
+    p2 = np.ascontiguousarray(points2D, dtype=np.float64).reshape(-1, 2)
+    p3 = np.ascontiguousarray(points3D, dtype=np.float64).reshape(-1, 3)
+    if p2.shape[0] != n or p3.shape[0] != n:
+        raise ValueError(f"absolute poses: {n} correspondences by offsets, {p2.shape[0]} points2D, "
+                         f"{p3.shape[0]} points3D")
+    return off, models, prm, p2, p3
+
+
 class TriOpts(C.Structure):  # amc_tri_opts (include/amc_tri.h)
     _fields_ = [("min_tri_angle", C.c_double), ("max_error", C.c_double), ("min_inlier_ratio", C.c_double),
                 ("confidence", C.c_double), ("dyn_num_trials_multiplier", C.c_double),
@@ -255,6 +322,16 @@ def load() -> C.CDLL:
         lib.amc_sift_result_free.argtypes = [C.POINTER(SiftResult)]
         lib.amc_sift_result_free.restype = None
     lib.amc_match_opts_default.restype = None
+    if hasattr(lib, "amc_estimate_absolute_poses"):
+        lib.amc_estimate_absolute_poses.argtypes = ([C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 +
+                                                    [C.POINTER(AbsPoseOpts), C.POINTER(AbsPoseRefineOpts), C.c_int,
+                                                     C.POINTER(AbsPoseResult)])
+        lib.amc_estimate_absolute_poses.restype = C.c_int
+        lib.amc_refine_absolute_poses.argtypes = ([C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7 +
+                                                  [C.POINTER(AbsPoseRefineOpts), C.c_int, C.POINTER(AbsPoseResult)])
+        lib.amc_refine_absolute_poses.restype = C.c_int
+        lib.amc_abspose_result_free.argtypes = [C.POINTER(AbsPoseResult)]
+        lib.amc_abspose_result_free.restype = None
     if hasattr(lib, "amc_triangulate_tracks"):  # (absent from a library built from an older revision)
         lib.amc_tri_opts_default.argtypes = [C.POINTER(TriOpts)]
         lib.amc_tri_opts_default.restype = None
@@ -609,6 +686,57 @@ class Context:
             self._lib.amc_sift_result_free(C.byref(res))
         out = [(kp[off[i]:off[i + 1]], desc[off[i]:off[i + 1]]) for i in range(len(imgs))]
         return (out[0] if single else out), stats
+
+    def estimate_absolute_poses(self, offsets, camera_models, camera_params, points2D, points3D, estimation=None,
+                                refinement=None, return_covariance=False):
+        """amc_estimate_absolute_poses: one LO-RANSAC per focal-length factor and one refinement per query (DESIGN.md
+        section 12).  offsets: (Q + 1,) CSR over the correspondences; camera_models: (Q,) COLMAP model ids;
+        camera_params: Q parameter vectors; points2D: (N, 2) pixels; points3D: (N, 3).  estimation / refinement: dicts
+        of amc_abspose_opts / amc_abspose_refine_opts fields (the rest keep their defaults).  Returns a dict: success
+        (Q,) bool, qvec (Q, 4) x y z w, tvec (Q, 3), num_inliers, num_trials, focal_factor, inlier_mask (N,) bool,
+        covariance (Q, 6, 6) when asked, device_ms, kernel_ms, num_batches."""
+        off, models, prm, p2, p3 = abspose_inputs(offsets, camera_models, camera_params, points2D, points3D)
+        eo, ro = abspose_options(estimation, refinement)
+        res = AbsPoseResult()
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _check(self._lib.amc_estimate_absolute_poses(self._h, ptr(off), off.size - 1, ptr(models), ptr(prm), ptr(p2),
+                                                      ptr(p3), C.byref(eo), C.byref(ro), int(bool(return_covariance)),
+                                                      C.byref(res)))
+        return self._abspose_out(res, off.size - 1, int(off[-1]), return_covariance)
+
+    def refine_absolute_poses(self, offsets, camera_models, camera_params, points2D, points3D, qvec, tvec, inlier_mask,
+                              refinement=None, return_covariance=False):
+        """amc_refine_absolute_poses: RefineAbsolutePose per query from the poses qvec (Q, 4) x y z w, tvec (Q, 3) over
+        the correspondences inlier_mask (N,) marks; the rest as estimate_absolute_poses, same result dict."""
+        off, models, prm, p2, p3 = abspose_inputs(offsets, camera_models, camera_params, points2D, points3D)
+        nq, n = off.size - 1, int(off[-1])
+        q = np.ascontiguousarray(qvec, dtype=np.float64).reshape(-1, 4)
+        t = np.ascontiguousarray(tvec, dtype=np.float64).reshape(-1, 3)
+        m = np.ascontiguousarray(inlier_mask, dtype=bool).reshape(-1).astype(np.uint8)
+        if q.shape[0] != nq or t.shape[0] != nq or m.size != n:
+            raise ValueError(f"refine_absolute_poses: {nq} queries and {n} correspondences by offsets, {q.shape[0]} "
+                             f"rotations, {t.shape[0]} translations, {m.size} mask entries")
+        _, ro = abspose_options(None, refinement)
+        res = AbsPoseResult()
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _check(self._lib.amc_refine_absolute_poses(self._h, ptr(off), nq, ptr(models), ptr(prm), ptr(p2), ptr(p3),
+                                                    ptr(q), ptr(t), ptr(m), C.byref(ro), int(bool(return_covariance)),
+                                                    C.byref(res)))
+        return self._abspose_out(res, nq, n, return_covariance)
+
+    def _abspose_out(self, res, nq, n, cov):
+        try:
+            a = lambda p, shape: np.ctypeslib.as_array(p, (max(shape[0], 1),) + shape[1:])[:shape[0]].copy()  # noqa: E731
+            out = {"success": a(res.success, (nq,)).astype(bool), "qvec": a(res.qvec, (nq, 4)),
+                   "tvec": a(res.tvec, (nq, 3)), "num_inliers": a(res.num_inliers, (nq,)),
+                   "num_trials": a(res.num_trials, (nq,)), "focal_factor": a(res.focal_factor, (nq,)),
+                   "inlier_mask": a(res.inlier_mask, (n,)).astype(bool), "device_ms": res.device_ms,
+                   "kernel_ms": res.kernel_ms, "num_batches": int(res.num_batches)}
+            if cov:
+                out["covariance"] = a(res.covariance, (nq, 36)).reshape(nq, 6, 6)
+        finally:
+            self._lib.amc_abspose_result_free(C.byref(res))
+        return out
 
     def triangulate_tracks(self, poses, track_offsets, obs_pose, obs_xy, **opts):
         """amc_triangulate_tracks: one LO-RANSAC triangulation per track.

@@ -36,6 +36,7 @@
 #include "estimators.h"
 #include "sift_host.h"
 #include "tri_host.h"
+#include "abspose_host.h"
 
 namespace py = pybind11;
 using namespace pybind11::literals;
@@ -925,6 +926,43 @@ PYBIND11_MODULE(_pycolmap, m) {
         },
         "point_data"_a, "images"_a, "cameras"_a, "opions"_a = tri_defaults,
         "Robustly estimate 3D point from observations in multiple views using RANSAC");
+
+    // ---- absolute_pose_estimation / pose_refinement (reference: pycolmap/estimators/absolute_pose.h; abspose_host.h) -
+    py::class_<AbsolutePoseEstimationOptions> PyAbsEst(m, "AbsolutePoseEstimationOptions");
+    PyAbsEst
+        .def(py::init([py_ransac_cls]() {
+            AbsolutePoseEstimationOptions o;  // pycolmap's RANSACOptions() with max_error = 12, as the binding builds it
+            o.ransac = py_ransac_cls().cast<RANSACOptions>();
+            o.ransac.max_error = 12.0;
+            return o;
+        }))
+        .def_readwrite("estimate_focal_length", &AbsolutePoseEstimationOptions::estimate_focal_length)
+        .def_readwrite("num_focal_length_samples", &AbsolutePoseEstimationOptions::num_focal_length_samples)
+        .def_readwrite("min_focal_length_ratio", &AbsolutePoseEstimationOptions::min_focal_length_ratio)
+        .def_readwrite("max_focal_length_ratio", &AbsolutePoseEstimationOptions::max_focal_length_ratio)
+        .def_readwrite("ransac", &AbsolutePoseEstimationOptions::ransac);
+    MakeDataclass(PyAbsEst, {"estimate_focal_length", "num_focal_length_samples", "min_focal_length_ratio",
+                             "max_focal_length_ratio", "ransac"});
+    const AbsolutePoseEstimationOptions abs_est_defaults = PyAbsEst().cast<AbsolutePoseEstimationOptions>();
+    py::class_<AbsolutePoseRefinementOptions> PyAbsRef(m, "AbsolutePoseRefinementOptions");
+    PyAbsRef.def(py::init<>())
+        .def_readwrite("gradient_tolerance", &AbsolutePoseRefinementOptions::gradient_tolerance)
+        .def_readwrite("max_num_iterations", &AbsolutePoseRefinementOptions::max_num_iterations)
+        .def_readwrite("loss_function_scale", &AbsolutePoseRefinementOptions::loss_function_scale)
+        .def_readwrite("refine_focal_length", &AbsolutePoseRefinementOptions::refine_focal_length,
+                       "Not supported: True raises ValueError (DESIGN.md 12, A11).")
+        .def_readwrite("refine_extra_params", &AbsolutePoseRefinementOptions::refine_extra_params,
+                       "Not supported: True raises ValueError (DESIGN.md 12, A11).")
+        .def_readwrite("print_summary", &AbsolutePoseRefinementOptions::print_summary,
+                       "Accepted; has no effect (no solver report is printed).");
+    MakeDataclass(PyAbsRef, {"gradient_tolerance", "max_num_iterations", "loss_function_scale", "refine_focal_length",
+                             "refine_extra_params", "print_summary"});
+    const AbsolutePoseRefinementOptions abs_ref_defaults = PyAbsRef().cast<AbsolutePoseRefinementOptions>();
+    m.def("absolute_pose_estimation", &EstimateAndRefineAbsolutePose, "points2D"_a, "points3D"_a, "camera"_a,
+          "estimation_options"_a = abs_est_defaults, "refinement_options"_a = abs_ref_defaults,
+          "return_covariance"_a = false, "Absolute pose estimation with non-linear refinement.");
+    m.def("pose_refinement", &RefineAbsolutePose, "cam_from_world"_a, "points2D"_a, "points3D"_a, "inlier_mask"_a,
+          "camera"_a, "refinement_options"_a = abs_ref_defaults, "Non-linear refinement of absolute pose.");
 
     // ---- Database ---------------------------------------------------------------------------
     py::class_<Database>(m, "Database")

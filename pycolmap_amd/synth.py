@@ -368,3 +368,81 @@ def triangulation_scene(rng, num_tracks, num_cameras=200, max_len=50, mean_len=4
     xy[outlier] = rng.uniform(-500.0 / f, 500.0 / f, size=(int(outlier.sum()), 2))
     return dict(poses=poses, offsets=offsets, obs_pose=obs_pose, obs_xy=np.ascontiguousarray(xy), xyz=xyz,
                 outlier=outlier)
+
+
+# camera parameters of the eleven COLMAP models for localisation_scene: focal length(s), principal point, mild
+# distortion
+def _localisation_params(model, f, width, height):
+    cx, cy = width / 2.0, height / 2.0
+    return {
+        0: [f, cx, cy],
+        1: [f, 1.02 * f, cx, cy],
+        2: [f, cx, cy, 0.02],
+        3: [f, cx, cy, 0.02, -0.01],
+        4: [f, 1.02 * f, cx, cy, 0.02, -0.01, 1e-3, -5e-4],
+        5: [f, 1.02 * f, cx, cy, 0.02, -0.01, 5e-3, -1e-3],
+        6: [f, 1.02 * f, cx, cy, 0.02, -0.01, 1e-3, -5e-4, 1e-3, 0.01, -5e-3, 1e-3],
+        7: [f, 1.02 * f, cx, cy, 0.9],
+        8: [f, cx, cy, 0.02],
+        9: [f, cx, cy, 0.02, -0.01],
+        10: [f, 1.02 * f, cx, cy, 0.02, -0.01, 1e-3, -5e-4, 1e-3, -1e-3, 1e-3, -1e-3],
+    }[int(model)]
+
+
+def random_rotation(rng):
+    """A uniformly random rotation: (R (3, 3), quaternion (x, y, z, w) with w >= 0)."""
+    q = rng.normal(size=4)
+    q /= np.linalg.norm(q)
+    if q[3] < 0:
+        q = -q
+    x, y, z, w = q
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+    return R, q
+
+
+def localisation_scene(rng, num_queries, num_points=1000, outlier_frac=0.4, noise_px=0.5, model=0, behind_frac=0.0,
+                       f=1200.0, width=1600, height=1200, depth=(4.0, 12.0)):
+    """Localisation queries for absolute pose: per query a random camera (uniform rotation, centre in a 10 m cube),
+    `num_points` (an int or a per-query sequence) 3D points in front of it at depths in `depth` whose projections
+    through the camera `model` (a COLMAP model id; parameters from focal length `f` and a `width` x `height` image)
+    fill the image, `noise_px` Gaussian pixel noise, a fraction `outlier_frac` of the observations replaced by uniform
+    pixels and a fraction `behind_frac` of the points moved behind the camera.  Returns a dict: offsets (Q + 1,)
+    uint64, camera_models (Q,) int32, camera_params (list of Q arrays), points2D (N, 2), points3D (N, 3), qvec (Q, 4)
+    x y z w and tvec (Q, 3) of the true cam_from_world, outlier (N,) bool."""
+    Q = int(num_queries)
+    ns = np.broadcast_to(np.asarray(num_points, dtype=np.int64), (Q,))
+    offsets = np.zeros(Q + 1, np.uint64)
+    offsets[1:] = np.cumsum(ns)
+    N = int(offsets[-1])
+    prm = np.asarray(_localisation_params(model, f, width, height), dtype=np.float64)
+    fx = prm[0]
+    fy = prm[1] if int(model) not in (0, 2, 3, 8, 9) else prm[0]
+    p2 = np.zeros((N, 2))
+    p3 = np.zeros((N, 3))
+    out = np.zeros(N, bool)
+    qv = np.zeros((Q, 4))
+    tv = np.zeros((Q, 3))
+    for i in range(Q):
+        n, o = int(ns[i]), int(offsets[i])
+        R, q = random_rotation(rng)
+        c = rng.uniform(-5.0, 5.0, size=3)
+        t = -R @ c
+        # normalized coordinates inside the image (the pinhole footprint, shrunk a little for distortion)
+        u = rng.uniform(-0.45 * width / fx, 0.45 * width / fx, size=n)
+        v = rng.uniform(-0.45 * height / fy, 0.45 * height / fy, size=n)
+        d = rng.uniform(depth[0], depth[1], size=n)
+        x, y = img_from_cam(model, prm, np.stack([u, v], axis=1)).T
+        xc = np.stack([u * d, v * d, d], axis=1)
+        behind = rng.random(n) < behind_frac
+        xc[behind] = -xc[behind]
+        p3[o:o + n] = (xc - t) @ R  # R^T (xc - t)
+        p2[o:o + n, 0] = x + rng.normal(scale=noise_px, size=n) if noise_px > 0 else x
+        p2[o:o + n, 1] = y + rng.normal(scale=noise_px, size=n) if noise_px > 0 else y
+        bad = rng.random(n) < outlier_frac
+        p2[o:o + n][bad] = np.stack([rng.uniform(0, width, int(bad.sum())), rng.uniform(0, height, int(bad.sum()))], 1)
+        out[o:o + n] = bad | behind
+        qv[i], tv[i] = q, t
+    return dict(offsets=offsets, camera_models=np.full(Q, int(model), np.int32), camera_params=[prm.copy() for _ in range(Q)],
+                points2D=p2, points3D=p3, qvec=qv, tvec=tv, outlier=out)

@@ -205,31 +205,6 @@ __global__ __launch_bounds__(kWave) void abspose_refine_kernel(RefineLaunch p) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-#define AP_HIPCHK(expr)                                                                                             \
-    do {                                                                                                            \
-        hipError_t e_ = (expr);                                                                                     \
-        if (e_ != hipSuccess)                                                                                       \
-            return api_fail(AMC_E_HIP, "%s: %s:%d: %s -> %s", fn, __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevMem {
-    void* p = nullptr;
-    ~DevMem() {
-        if (p) (void)hipFree(p);
-    }
-};
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    std::vector<hipEvent_t> k;
-    ~Events() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-        for (hipEvent_t e : k)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 void result_alloc(amc_abspose_result* r, size_t nq, uint64_t ncorr, bool cov) {
     const size_t q = std::max<size_t>(nq, 1);
     r->nqueries = nq;
@@ -252,6 +227,7 @@ int run_impl(const char* fn, amc_ctx* ctx, bool estimate, const uint64_t* offset
              const double* cparams, const double* points2D, const double* points3D, const double* init_q,
              const double* init_t, const uint8_t* in_mask, const amc_abspose_opts* eo_in,
              const amc_abspose_refine_opts* ro_in, int want_cov, amc_abspose_result* result) {
+    const char* const hipchk_who = fn;
     if (!ctx || !result || !offsets || !ro_in || (estimate && !eo_in))
         return api_fail(AMC_E_INVALID, "%s: NULL argument", fn);
     std::memset(result, 0, sizeof *result);
@@ -284,98 +260,73 @@ int run_impl(const char* fn, amc_ctx* ctx, bool estimate, const uint64_t* offset
 
     const std::vector<double> factors = estimate ? ap::focal_factors(eo) : std::vector<double>{1.0};
     const uint64_t F = estimate ? factors.size() : 0;
-    const uint64_t max_trials = ap::clamped_max_trials(eo), min_trials = (uint64_t)eo.min_num_trials;
+    const uint64_t max_trials = tvg::ransac_max_trials(eo.max_num_trials, eo.min_inlier_ratio, eo.confidence,
+                                                       eo.dyn_num_trials_multiplier, ap::kMinSamples);
+    const uint64_t min_trials = (uint64_t)eo.min_num_trials;
 
     // batches: contiguous query ranges
     const uint64_t per = estimate ? F : 1;
-    std::vector<size_t> bstart{0};
-    uint64_t max_bq = 0, max_bc = 0, max_bsc = 0;
-    for (size_t i = 0; i < nq;) {
-        size_t j = i + 1;
-        while (j < nq && j - i < kMaxBatchQueries && (offsets[j + 1] - offsets[i]) * per <= kMaxBatchSlotCorr) ++j;
-        max_bq = std::max<uint64_t>(max_bq, j - i);
-        max_bc = std::max<uint64_t>(max_bc, offsets[j] - offsets[i]);
-        max_bsc = std::max<uint64_t>(max_bsc, (offsets[j] - offsets[i]) * per);
-        bstart.push_back(j);
-        i = j;
-    }
-    const size_t nbatch = bstart.size() - 1;
-    max_bc = std::max<uint64_t>(max_bc, 1);
-    max_bsc = std::max<uint64_t>(max_bsc, 1);
+    const Batches batches = split_batches(offsets, nq, kMaxBatchQueries, kMaxBatchSlotCorr, per);
+    const std::vector<size_t>& bstart = batches.start;
+    const size_t nbatch = batches.count();
+    const uint64_t max_bq = batches.most_items, max_bc = std::max<uint64_t>(batches.most_elems, 1);
     const uint64_t max_bs = estimate ? max_bq * F : 1;
-    if (!estimate) max_bsc = 1;
+    const uint64_t max_bsc = estimate ? std::max<uint64_t>(batches.most_elems * per, 1) : 1;
 
-    const size_t sz_slots = align256(max_bs * sizeof(SlotDesc)), sz_sord = align256(max_bs * 4),
-                 sz_xy = align256(max_bc * 16), sz_X = align256(max_bc * 24), sz_uv = align256(max_bsc * 16),
-                 sz_perm = align256(max_bsc * 4), sz_smask = align256(max_bsc), sz_s8 = align256(max_bs),
-                 sz_s32 = align256(max_bs * 4), sz_s64 = align256(max_bs * 8), sz_smod = align256(max_bs * 96),
-                 sz_doff = align256((max_bc + 2) * 8), sz_dtab = align256((max_bc + max_bq + 1) * 8),
-                 sz_q8 = align256(max_bq * 8), sz_q4 = align256(max_bq * 4), sz_qb = align256((max_bq + 1) * 4),
-                 sz_q1 = align256(max_bq), sz_qprm = align256(max_bq * 8 * cam::kMaxParams),
-                 sz_qq = align256(max_bq * 32), sz_qt = align256(max_bq * 24), sz_cov = align256(max_bq * 288),
-                 sz_mask = align256(max_bc);
-    const size_t total = sz_slots + sz_sord + sz_xy + sz_X + sz_uv + sz_perm + sz_smask + 2 * sz_s8 + sz_s32 + sz_s64 +
-                         sz_smod + sz_doff + sz_dtab + sz_q8 + 4 * sz_q4 + sz_qb + sz_q1 + sz_qprm + 2 * sz_qq +
-                         2 * sz_qt + sz_cov + sz_q8 + sz_q8 + sz_mask;
     const CtxView cv = ctx_view(ctx);
-    AP_HIPCHK(hipSetDevice(cv.device));
+    HIPCHK(hipSetDevice(cv.device));
     hipStream_t st = cv.stream;
-    Events ev;
-    AP_HIPCHK(hipEventCreate(&ev.a));
-    AP_HIPCHK(hipEventCreate(&ev.b));
-    AP_HIPCHK(hipEventRecord(ev.a, st));
-    DevMem mem, smem;
-    AP_HIPCHK(hipMalloc(&mem.p, total));
-    char* base = static_cast<char*>(mem.p);
-    size_t at = 0;
-    auto carve = [&](size_t bytes) {
-        char* q = base + at;
-        at += bytes;
-        return q;
-    };
-    SlotDesc* d_slots = reinterpret_cast<SlotDesc*>(carve(sz_slots));
-    uint32_t* d_sord = reinterpret_cast<uint32_t*>(carve(sz_sord));
-    double* d_xy = reinterpret_cast<double*>(carve(sz_xy));
-    double* d_X = reinterpret_cast<double*>(carve(sz_X));
-    double* d_uv = reinterpret_cast<double*>(carve(sz_uv));
-    uint32_t* d_perm = reinterpret_cast<uint32_t*>(carve(sz_perm));
-    uint8_t* d_smask = reinterpret_cast<uint8_t*>(carve(sz_smask));
-    uint8_t* d_ssucc = reinterpret_cast<uint8_t*>(carve(sz_s8));
-    uint8_t* d_sover = reinterpret_cast<uint8_t*>(carve(sz_s8));
-    uint32_t* d_sninl = reinterpret_cast<uint32_t*>(carve(sz_s32));
-    uint64_t* d_sntr = reinterpret_cast<uint64_t*>(carve(sz_s64));
-    double* d_smod = reinterpret_cast<double*>(carve(sz_smod));
-    uint64_t* d_doff = reinterpret_cast<uint64_t*>(carve(sz_doff));
-    uint64_t* d_dtab = reinterpret_cast<uint64_t*>(carve(sz_dtab));
-    uint64_t* d_qc0 = reinterpret_cast<uint64_t*>(carve(sz_q8));
-    uint32_t* d_qn = reinterpret_cast<uint32_t*>(carve(sz_q4));
-    uint32_t* d_qord = reinterpret_cast<uint32_t*>(carve(sz_q4));
-    int32_t* d_qmod = reinterpret_cast<int32_t*>(carve(sz_q4));
-    uint32_t* d_sbeg = reinterpret_cast<uint32_t*>(carve(sz_qb));
-    uint8_t* d_osucc = reinterpret_cast<uint8_t*>(carve(sz_q1));
-    double* d_qprm = reinterpret_cast<double*>(carve(sz_qprm));
-    double* d_iq = reinterpret_cast<double*>(carve(sz_qq));
-    double* d_oq = reinterpret_cast<double*>(carve(sz_qq));
-    double* d_it = reinterpret_cast<double*>(carve(sz_qt));
-    double* d_ot = reinterpret_cast<double*>(carve(sz_qt));
-    double* d_ocov = reinterpret_cast<double*>(carve(sz_cov));
-    uint64_t* d_ontr = reinterpret_cast<uint64_t*>(carve(sz_q8));
-    double* d_ofac = reinterpret_cast<double*>(carve(sz_q8));
-    uint8_t* d_mask = reinterpret_cast<uint8_t*>(carve(sz_mask));
-    uint32_t* d_oninl = reinterpret_cast<uint32_t*>(carve(sz_q4));
+    StreamTimer timer(st);
+    HIPCHK(timer.start());
+    SlotDesc* d_slots;
+    uint32_t *d_sord, *d_perm, *d_sninl, *d_qn, *d_qord, *d_sbeg, *d_oninl;
+    double *d_xy, *d_X, *d_uv, *d_smod, *d_qprm, *d_iq, *d_oq, *d_it, *d_ot, *d_ocov, *d_ofac;
+    uint8_t *d_smask, *d_ssucc, *d_sover, *d_osucc, *d_mask;
+    uint64_t *d_sntr, *d_doff, *d_dtab, *d_qc0, *d_ontr;
+    int32_t* d_qmod;
+    DevBuf<void> mem;
+    HIPCHK(DevParts()
+               .part(&d_slots, max_bs)
+               .part(&d_sord, max_bs)
+               .part(&d_xy, 2 * max_bc)
+               .part(&d_X, 3 * max_bc)
+               .part(&d_uv, 2 * max_bsc)
+               .part(&d_perm, max_bsc)
+               .part(&d_smask, max_bsc)
+               .part(&d_ssucc, max_bs)
+               .part(&d_sover, max_bs)
+               .part(&d_sninl, max_bs)
+               .part(&d_sntr, max_bs)
+               .part(&d_smod, 12 * max_bs)
+               .part(&d_doff, max_bc + 2)
+               .part(&d_dtab, max_bc + max_bq + 1)
+               .part(&d_qc0, max_bq)
+               .part(&d_qn, max_bq)
+               .part(&d_qord, max_bq)
+               .part(&d_qmod, max_bq)
+               .part(&d_sbeg, max_bq + 1)
+               .part(&d_osucc, max_bq)
+               .part(&d_qprm, max_bq * cam::kMaxParams)
+               .part(&d_iq, 4 * max_bq)
+               .part(&d_oq, 4 * max_bq)
+               .part(&d_it, 3 * max_bq)
+               .part(&d_ot, 3 * max_bq)
+               .part(&d_ocov, 36 * max_bq)
+               .part(&d_ontr, max_bq)
+               .part(&d_ofac, max_bq)
+               .part(&d_mask, max_bc)
+               .part(&d_oninl, max_bq)
+               .carve(mem));
 
     // the sample stream (estimation only)
+    DevBuf<uint32_t> smem;
     size_t stream_len = 0;
     std::vector<uint32_t> words;
     auto upload_stream = [&](size_t len) -> int {
-        AP_HIPCHK(hipStreamSynchronize(st));
-        if (smem.p) {
-            AP_HIPCHK(hipFree(smem.p));
-            smem.p = nullptr;
-        }
+        HIPCHK(hipStreamSynchronize(st));
         words = ap::sample_stream_words(len);
-        AP_HIPCHK(hipMalloc(&smem.p, len * 4));
-        AP_HIPCHK(hipMemcpyAsync(smem.p, words.data(), len * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(smem.ensure(len));
+        HIPCHK(hipMemcpyAsync(smem.p, words.data(), len * 4, hipMemcpyHostToDevice, st));
         stream_len = len;
         return AMC_OK;
     };
@@ -413,12 +364,12 @@ int run_impl(const char* fn, amc_ctx* ctx, bool estimate, const uint64_t* offset
             qmod[i] = models[q0 + i];
             ap::scaled_params(qmod[i], cparams + cam::kMaxParams * (q0 + i), 1.0, &H.qprm[cam::kMaxParams * i]);
         }
-        AP_HIPCHK(hipMemcpyAsync(d_qc0, H.qc0.data(), bq * 8, hipMemcpyHostToDevice, st));
-        AP_HIPCHK(hipMemcpyAsync(d_qn, H.qn.data(), bq * 4, hipMemcpyHostToDevice, st));
-        AP_HIPCHK(hipMemcpyAsync(d_qord, H.qord.data(), bq * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_qc0, H.qc0.data(), bq * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_qn, H.qn.data(), bq * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_qord, H.qord.data(), bq * 4, hipMemcpyHostToDevice, st));
         if (bc) {
-            AP_HIPCHK(hipMemcpyAsync(d_xy, points2D + 2 * ob, bc * 16, hipMemcpyHostToDevice, st));
-            AP_HIPCHK(hipMemcpyAsync(d_X, points3D + 3 * ob, bc * 24, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_xy, points2D + 2 * ob, bc * 16, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_X, points3D + 3 * ob, bc * 24, hipMemcpyHostToDevice, st));
         }
         RefineLaunch rl{};
         if (estimate) {
@@ -455,14 +406,14 @@ int run_impl(const char* fn, amc_ctx* ctx, bool estimate, const uint64_t* offset
                         cam::cam_from_img(d.model, d.params, xy[2 * k], xy[2 * k + 1], H.uv[2 * (d.scratch0 + k)],
                                           H.uv[2 * (d.scratch0 + k) + 1]);
                 }
-                AP_HIPCHK(hipMemcpyAsync(d_uv, H.uv.data(), sc * 16, hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(d_uv, H.uv.data(), sc * 16, hipMemcpyHostToDevice, st));
             }
             H.sord.resize(ns);
             for (size_t i = 0; i < bq; ++i)
                 for (uint64_t f = 0; f < F; ++f) H.sord[i * F + f] = (uint32_t)(H.qord[i] * F + f);
-            AP_HIPCHK(hipMemcpyAsync(d_slots, H.slots.data(), ns * sizeof(SlotDesc), hipMemcpyHostToDevice, st));
-            AP_HIPCHK(hipMemcpyAsync(d_sord, H.sord.data(), ns * 4, hipMemcpyHostToDevice, st));
-            AP_HIPCHK(hipMemcpyAsync(d_sbeg, H.sbeg.data(), (bq + 1) * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_slots, H.slots.data(), ns * sizeof(SlotDesc), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_sord, H.sord.data(), ns * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_sbeg, H.sbeg.data(), (bq + 1) * 4, hipMemcpyHostToDevice, st));
             // dynamic trial-count rows (ComputeNumTrials(c, n), c = 0 .. n) for the batch's sizes whose RANSAC can stop
             // before max_trials: at most (batch correspondences + 1) offsets and (batch correspondences + queries) rows
             H.dyn_off.assign(1, ap::kNoRow);
@@ -475,12 +426,13 @@ int run_impl(const char* fn, amc_ctx* ctx, bool estimate, const uint64_t* offset
                     if (n < 3 || H.dyn_off[n] != ap::kNoRow) continue;
                     H.dyn_off[n] = H.dyn_tab.size();
                     for (uint64_t c = 0; c <= n; ++c)
-                        H.dyn_tab.push_back(ap::compute_num_trials(c, n, eo.confidence, eo.dyn_num_trials_multiplier));
+                        H.dyn_tab.push_back(tvg::compute_num_trials(c, n, eo.confidence, eo.dyn_num_trials_multiplier,
+                                                                    ap::kMinSamples));
                 }
             }
             if (H.dyn_tab.empty()) H.dyn_tab.push_back(0);
-            AP_HIPCHK(hipMemcpyAsync(d_doff, H.dyn_off.data(), H.dyn_off.size() * 8, hipMemcpyHostToDevice, st));
-            AP_HIPCHK(hipMemcpyAsync(d_dtab, H.dyn_tab.data(), H.dyn_tab.size() * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_doff, H.dyn_off.data(), H.dyn_off.size() * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_dtab, H.dyn_tab.data(), H.dyn_tab.size() * 8, hipMemcpyHostToDevice, st));
             H.over.assign(ns, 0);
             for (;;) {
                 RansacLaunch p{};
@@ -504,16 +456,12 @@ int run_impl(const char* fn, amc_ctx* ctx, bool estimate, const uint64_t* offset
                 p.s_ninl = d_sninl;
                 p.s_ntr = d_sntr;
                 p.s_model = d_smod;
-                ev.k.push_back(nullptr);
-                AP_HIPCHK(hipEventCreate(&ev.k.back()));
-                ev.k.push_back(nullptr);
-                AP_HIPCHK(hipEventCreate(&ev.k.back()));
-                AP_HIPCHK(hipEventRecord(ev.k[ev.k.size() - 2], st));
+                HIPCHK(timer.span_begin());
                 hipLaunchKernelGGL(abspose_ransac_kernel, dim3((unsigned)ns), dim3(kWave), 0, st, p);
-                AP_HIPCHK(hipGetLastError());
-                AP_HIPCHK(hipEventRecord(ev.k.back(), st));
-                AP_HIPCHK(hipMemcpyAsync(H.over.data(), d_sover, ns, hipMemcpyDeviceToHost, st));
-                AP_HIPCHK(hipStreamSynchronize(st));
+                HIPCHK(hipGetLastError());
+                HIPCHK(timer.span_end());
+                HIPCHK(hipMemcpyAsync(H.over.data(), d_sover, ns, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
                 bool any = false;
                 for (uint8_t v : H.over) any = any || v;
                 if (!any) break;
@@ -531,11 +479,11 @@ int run_impl(const char* fn, amc_ctx* ctx, bool estimate, const uint64_t* offset
             rl.s_ntr = d_sntr;
             rl.s_model = d_smod;
         } else {
-            AP_HIPCHK(hipMemcpyAsync(d_qmod, qmod.data(), bq * 4, hipMemcpyHostToDevice, st));
-            AP_HIPCHK(hipMemcpyAsync(d_qprm, H.qprm.data(), bq * 8 * cam::kMaxParams, hipMemcpyHostToDevice, st));
-            AP_HIPCHK(hipMemcpyAsync(d_iq, init_q + 4 * q0, bq * 32, hipMemcpyHostToDevice, st));
-            AP_HIPCHK(hipMemcpyAsync(d_it, init_t + 3 * q0, bq * 24, hipMemcpyHostToDevice, st));
-            if (bc) AP_HIPCHK(hipMemcpyAsync(d_mask, in_mask + ob, bc, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_qmod, qmod.data(), bq * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_qprm, H.qprm.data(), bq * 8 * cam::kMaxParams, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_iq, init_q + 4 * q0, bq * 32, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_it, init_t + 3 * q0, bq * 24, hipMemcpyHostToDevice, st));
+            if (bc) HIPCHK(hipMemcpyAsync(d_mask, in_mask + ob, bc, hipMemcpyHostToDevice, st));
         }
         rl.nq = (uint32_t)bq;
         rl.estimate = estimate ? 1 : 0;
@@ -560,34 +508,22 @@ int run_impl(const char* fn, amc_ctx* ctx, bool estimate, const uint64_t* offset
         rl.o_ntr = d_ontr;
         rl.o_factor = d_ofac;
         rl.o_cov = cov ? d_ocov : nullptr;
-        ev.k.push_back(nullptr);
-        AP_HIPCHK(hipEventCreate(&ev.k.back()));
-        ev.k.push_back(nullptr);
-        AP_HIPCHK(hipEventCreate(&ev.k.back()));
-        AP_HIPCHK(hipEventRecord(ev.k[ev.k.size() - 2], st));
+        HIPCHK(timer.span_begin());
         hipLaunchKernelGGL(abspose_refine_kernel, dim3((unsigned)bq), dim3(kWave), 0, st, rl);
-        AP_HIPCHK(hipGetLastError());
-        AP_HIPCHK(hipEventRecord(ev.k.back(), st));
-        AP_HIPCHK(hipMemcpyAsync(result->success + q0, d_osucc, bq, hipMemcpyDeviceToHost, st));
-        AP_HIPCHK(hipMemcpyAsync(result->qvec + 4 * q0, d_oq, bq * 32, hipMemcpyDeviceToHost, st));
-        AP_HIPCHK(hipMemcpyAsync(result->tvec + 3 * q0, d_ot, bq * 24, hipMemcpyDeviceToHost, st));
-        AP_HIPCHK(hipMemcpyAsync(result->num_inliers + q0, d_oninl, bq * 4, hipMemcpyDeviceToHost, st));
-        AP_HIPCHK(hipMemcpyAsync(result->num_trials + q0, d_ontr, bq * 8, hipMemcpyDeviceToHost, st));
-        AP_HIPCHK(hipMemcpyAsync(result->focal_factor + q0, d_ofac, bq * 8, hipMemcpyDeviceToHost, st));
-        if (cov) AP_HIPCHK(hipMemcpyAsync(result->covariance + 36 * q0, d_ocov, bq * 288, hipMemcpyDeviceToHost, st));
-        if (bc) AP_HIPCHK(hipMemcpyAsync(result->inlier_mask + ob, d_mask, bc, hipMemcpyDeviceToHost, st));
-        if (nbatch > 1) AP_HIPCHK(hipStreamSynchronize(st));  // the next batch reuses the buffers the copies read
+        HIPCHK(hipGetLastError());
+        HIPCHK(timer.span_end());
+        HIPCHK(hipMemcpyAsync(result->success + q0, d_osucc, bq, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(result->qvec + 4 * q0, d_oq, bq * 32, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(result->tvec + 3 * q0, d_ot, bq * 24, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(result->num_inliers + q0, d_oninl, bq * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(result->num_trials + q0, d_ontr, bq * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(result->focal_factor + q0, d_ofac, bq * 8, hipMemcpyDeviceToHost, st));
+        if (cov) HIPCHK(hipMemcpyAsync(result->covariance + 36 * q0, d_ocov, bq * 288, hipMemcpyDeviceToHost, st));
+        if (bc) HIPCHK(hipMemcpyAsync(result->inlier_mask + ob, d_mask, bc, hipMemcpyDeviceToHost, st));
+        if (nbatch > 1) HIPCHK(hipStreamSynchronize(st));  // the next batch reuses the buffers the copies read
     }
-    AP_HIPCHK(hipEventRecord(ev.b, st));
-    AP_HIPCHK(hipEventSynchronize(ev.b));
-    float ms = 0.f;
-    AP_HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
-    result->device_ms = ms;
-    result->kernel_ms = 0.0;
-    for (size_t i = 0; i + 1 < ev.k.size(); i += 2) {
-        AP_HIPCHK(hipEventElapsedTime(&ms, ev.k[i], ev.k[i + 1]));
-        result->kernel_ms += ms;
-    }
+    HIPCHK(timer.stop(result->device_ms));  // (result was zeroed on entry)
+    HIPCHK(timer.spans(result->kernel_ms));
     result->num_batches = (uint32_t)nbatch;
     if (!estimate)  // refinement: the input mask and its count
         for (size_t i = 0; i < nq; ++i) {

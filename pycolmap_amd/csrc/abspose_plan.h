@@ -18,25 +18,7 @@ namespace amc {
 namespace ap {
 
 constexpr uint64_t kNoRow = ~(uint64_t)0;
-
-// colmap/optim/ransac.h ComputeNumTrials with kMinNumSamples = 3 (P3P)
-inline uint64_t compute_num_trials(uint64_t num_inliers, uint64_t num_samples, double confidence, double multiplier) {
-    const double inlier_ratio = num_inliers / static_cast<double>(num_samples);
-    const double nom = 1 - confidence;
-    if (nom <= 0) return ~(uint64_t)0;
-    const double denom = 1 - std::pow(inlier_ratio, 3);
-    if (denom <= 0) return 1;
-    if (denom == 1.0) return ~(uint64_t)0;
-    return static_cast<uint64_t>(std::ceil(std::log(nom) / std::log(denom) * multiplier));
-}
-
-// the RANSAC constructor's clamp of max_num_trials by min_inlier_ratio
-inline uint64_t clamped_max_trials(const amc_abspose_opts& o) {
-    const uint64_t kNumSamples = 100000;
-    return std::min<uint64_t>((uint64_t)o.max_num_trials,
-                              compute_num_trials((uint64_t)(o.min_inlier_ratio * kNumSamples), kNumSamples,
-                                                 o.confidence, o.dyn_num_trials_multiplier));
-}
+constexpr int kMinSamples = 3;  // P3P: ComputeNumTrials' kMinNumSamples (tvg_math.h)
 
 // AbsolutePoseEstimationOptions::Check + RANSACOptions::Check; empty string = valid
 inline std::string check_estimation(const amc_abspose_opts& o) {

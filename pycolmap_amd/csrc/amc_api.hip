@@ -33,24 +33,6 @@ namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIPCHK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return fail(AMC_E_HIP, "%s:%d: %s -> %s", __FILE__, __LINE__, #expr,            \
-                        hipGetErrorString(e_));                                             \
-    } while (0)
-
 inline uint32_t round_up(uint32_t x, uint32_t m) { return (x + m - 1) / m * m; }
 
 struct Slot {
@@ -67,50 +49,6 @@ struct Slot {
     CameraDev cam{};
     void* grid_base = nullptr;  // guided matching's keypoint grid: sxy | sidx | cell_start (one allocation)
     GridDev grid{};             // n == 0: none (no float32 keypoints, or non-finite coordinates)
-};
-
-// grow-only device / pinned-host scratch
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = std::max(n, (size_t)16);
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-template <typename T>
-struct PinBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = std::max(n, (size_t)16);
-        // default flags: mapped and coherent - kernels write it through the same pointer (the scan's copy parts,
-        // launch_host_copy) and the host sees the data once the kernel's completion event has been waited for
-        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), want * sizeof(T), 0);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
 };
 
 // The slots' device memory: amc::SlotArenaT (slot_arena.h) over the HIP allocator.
@@ -151,14 +89,14 @@ struct PinnedPool {
         size_t best = 0;
         for (size_t i = 1; i < idle.size(); ++i)
             if (better(idle[i], idle[best])) best = i;
-        PinBuf<uint32_t> b = idle[best];
+        PinBuf<uint32_t> b = std::move(idle[best]);
         idle.erase(idle.begin() + best);
         return b;
     }
     void give_back(PinBuf<uint32_t> b) {
         if (!b.p) return;
         std::lock_guard<std::mutex> lock(mu);
-        idle.push_back(b);
+        idle.push_back(std::move(b));
         auto total = [&] {
             size_t t = 0;
             for (auto& x : idle) t += x.cap * sizeof(uint32_t);
@@ -170,17 +108,12 @@ struct PinnedPool {
             size_t small = 0;
             for (size_t i = 1; i < idle.size(); ++i)
                 if (idle[i].cap < idle[small].cap) small = i;
-            idle[small].release();
             idle.erase(idle.begin() + small);
         }
     }
     void trim() {
         std::lock_guard<std::mutex> lock(mu);
-        for (auto& b : idle) b.release();
         idle.clear();
-    }
-    ~PinnedPool() {
-        for (auto& b : idle) b.release();
     }
 };
 
@@ -207,7 +140,6 @@ struct VerifySliceBufs {
         for (auto& k : cls) k.release();
     }
     ~VerifySliceBufs() {
-        release();
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
         if (ev_e_done) (void)hipEventDestroy(ev_e_done);
@@ -381,7 +313,7 @@ int amc_device_count(void) {
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess) {
         if (e == hipErrorNoDevice) return 0;
-        return fail(AMC_E_HIP, "hipGetDeviceCount: %s", hipGetErrorString(e));
+        return api_fail(AMC_E_HIP, "hipGetDeviceCount: %s", hipGetErrorString(e));
     }
     return n;
 }
@@ -395,33 +327,33 @@ void amc_match_opts_default(amc_match_opts* o) {
 }
 
 int amc_ctx_create(int device_id, amc_ctx** out) {
-    if (!out) return fail(AMC_E_INVALID, "amc_ctx_create: out is NULL");
+    if (!out) return api_fail(AMC_E_INVALID, "amc_ctx_create: out is NULL");
     *out = nullptr;
     int n = 0;
     HIPCHK(hipGetDeviceCount(&n));
     if (device_id < 0 || device_id >= n)
-        return fail(AMC_E_INVALID, "amc_ctx_create: device %d out of range (%d devices)",
-                    device_id, n);
+        return api_fail(AMC_E_INVALID, "amc_ctx_create: device %d out of range (%d devices)",
+                        device_id, n);
     HIPCHK(hipSetDevice(device_id));
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device_id));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(AMC_E_HIP, "amc_ctx_create: device %d is %s; this library is gfx950-only",
-                    device_id, prop.gcnArchName);
+        return api_fail(AMC_E_HIP, "amc_ctx_create: device %d is %s; this library is gfx950-only",
+                        device_id, prop.gcnArchName);
     amc_ctx* c = new (std::nothrow) amc_ctx();
-    if (!c) return fail(AMC_E_NOMEM, "amc_ctx_create: out of host memory");
+    if (!c) return api_fail(AMC_E_NOMEM, "amc_ctx_create: out of host memory");
     c->device = device_id;
     hipError_t e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;
-        return fail(AMC_E_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
+        return api_fail(AMC_E_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
     }
     c->stream = c->own_stream;
     e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         (void)hipStreamDestroy(c->own_stream);
         delete c;
-        return fail(AMC_E_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
+        return api_fail(AMC_E_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
     }
     bool ev_ok = true;  // (an event that was never created would fail every later record: fail here instead)
     for (auto& ev : c->cev) ev_ok &= hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
@@ -446,7 +378,7 @@ int amc_ctx_create(int device_id, amc_ctx** out) {
         for (auto& ev : set) ev_ok &= hipEventCreate(&ev) == hipSuccess;
     if (!ev_ok) {
         amc_ctx_destroy(c);
-        return fail(AMC_E_HIP, "amc_ctx_create: hipEventCreate failed");
+        return api_fail(AMC_E_HIP, "amc_ctx_create: hipEventCreate failed");
     }
     // acos table with the HOST libm (the same one COLMAP's CPU path and the oracle call)
     c->h_lut.resize(kAcosLutSize);
@@ -463,7 +395,7 @@ int amc_ctx_create(int device_id, amc_ctx** out) {
                   hipMemcpyHostToDevice) != hipSuccess ||
         c->h_scalars.ensure(16) != hipSuccess) {
         amc_ctx_destroy(c);
-        return fail(AMC_E_HIP, "amc_ctx_create: device allocation failed");
+        return api_fail(AMC_E_HIP, "amc_ctx_create: device allocation failed");
     }
     c->ms[0].scalars = c->d_scalars;
     c->ms[1].scalars = c->d_scalars_alt;
@@ -543,13 +475,13 @@ void amc_ctx_destroy(amc_ctx* c) {
 }
 
 int amc_ctx_set_stream(amc_ctx* c, void* hip_stream) {
-    if (!c) return fail(AMC_E_INVALID, "amc_ctx_set_stream: ctx is NULL");
+    if (!c) return api_fail(AMC_E_INVALID, "amc_ctx_set_stream: ctx is NULL");
     c->stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
     return AMC_OK;
 }
 
 int amc_ctx_trim(amc_ctx* c) {
-    if (!c) return fail(AMC_E_INVALID, "amc_ctx_trim: NULL ctx");
+    if (!c) return api_fail(AMC_E_INVALID, "amc_ctx_trim: NULL ctx");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->copy_stream) HIPCHK(hipStreamSynchronize(c->copy_stream));
@@ -587,15 +519,15 @@ int amc_ctx_trim(amc_ctx* c) {
 }
 
 int amc_ctx_resident_matches(amc_ctx* c, const uint32_t** dev_matches, uint64_t* num_matches) {
-    if (!c || !dev_matches || !num_matches) return fail(AMC_E_INVALID, "amc_ctx_resident_matches: NULL argument");
+    if (!c || !dev_matches || !num_matches) return api_fail(AMC_E_INVALID, "amc_ctx_resident_matches: NULL argument");
     *dev_matches = c->resident_matches ? c->d_keep.p : nullptr;
     *num_matches = c->resident_matches;
     return AMC_OK;
 }
 
 int amc_upload_matches(amc_ctx* c, const uint32_t* matches, uint64_t num_matches) {
-    if (!c) return fail(AMC_E_INVALID, "amc_upload_matches: ctx is NULL");
-    if (num_matches > 0 && !matches) return fail(AMC_E_INVALID, "amc_upload_matches: NULL rows");
+    if (!c) return api_fail(AMC_E_INVALID, "amc_upload_matches: ctx is NULL");
+    if (num_matches > 0 && !matches) return api_fail(AMC_E_INVALID, "amc_upload_matches: NULL rows");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));  // (nothing of an earlier call reads the table any more: every entry point blocks)
     c->resident_matches = 0;
@@ -609,7 +541,7 @@ int amc_upload_matches(amc_ctx* c, const uint32_t* matches, uint64_t num_matches
 }
 
 int amc_ctx_reserve_slots(amc_ctx* c, uint32_t num_slots) {
-    if (!c) return fail(AMC_E_INVALID, "amc_ctx_reserve_slots: ctx is NULL");
+    if (!c) return api_fail(AMC_E_INVALID, "amc_ctx_reserve_slots: ctx is NULL");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->slots.assign(num_slots, Slot());
@@ -619,10 +551,10 @@ int amc_ctx_reserve_slots(amc_ctx* c, uint32_t num_slots) {
 }
 
 int amc_ctx_grow_slots(amc_ctx* c, uint32_t num_slots) {
-    if (!c) return fail(AMC_E_INVALID, "amc_ctx_grow_slots: ctx is NULL");
+    if (!c) return api_fail(AMC_E_INVALID, "amc_ctx_grow_slots: ctx is NULL");
     if (num_slots < c->slots.size())
-        return fail(AMC_E_INVALID, "amc_ctx_grow_slots: %u < current %zu slots (use amc_ctx_reserve_slots to reset)",
-                    num_slots, c->slots.size());
+        return api_fail(AMC_E_INVALID, "amc_ctx_grow_slots: %u < current %zu slots (use amc_ctx_reserve_slots to reset)",
+                        num_slots, c->slots.size());
     c->slots.resize(num_slots);
     c->table_dirty = true;
     return AMC_OK;
@@ -630,12 +562,12 @@ int amc_ctx_grow_slots(amc_ctx* c, uint32_t num_slots) {
 
 static int upload_common(amc_ctx* c, uint32_t slot, const void* src, uint32_t rows,
                          hipMemcpyKind kind) {
-    if (!c) return fail(AMC_E_INVALID, "upload_descriptors: ctx is NULL");
+    if (!c) return api_fail(AMC_E_INVALID, "upload_descriptors: ctx is NULL");
     if (slot >= c->slots.size())
-        return fail(AMC_E_INVALID, "upload_descriptors: slot %u >= reserved %zu", slot,
-                    c->slots.size());
-    if (rows > 0 && !src) return fail(AMC_E_INVALID, "upload_descriptors: NULL data, rows=%u", rows);
-    if (rows > (1u << 30)) return fail(AMC_E_INVALID, "upload_descriptors: rows=%u too large", rows);
+        return api_fail(AMC_E_INVALID, "upload_descriptors: slot %u >= reserved %zu", slot,
+                        c->slots.size());
+    if (rows > 0 && !src) return api_fail(AMC_E_INVALID, "upload_descriptors: NULL data, rows=%u", rows);
+    if (rows > (1u << 30)) return api_fail(AMC_E_INVALID, "upload_descriptors: rows=%u too large", rows);
     HIPCHK(hipSetDevice(c->device));
     Slot& s = c->slots[slot];
     if (s.base) {
@@ -655,8 +587,8 @@ static int upload_common(amc_ctx* c, uint32_t slot, const void* src, uint32_t ro
     if (e != hipSuccess) {
         s.valid = false;
         s.dev = ImageDev{};
-        return fail(AMC_E_NOMEM, "upload_descriptors: hipMalloc(%zu): %s", bytes,
-                    hipGetErrorString(e));
+        return api_fail(AMC_E_NOMEM, "upload_descriptors: hipMalloc(%zu): %s", bytes,
+                        hipGetErrorString(e));
     }
     uint8_t* raw = static_cast<uint8_t*>(s.base);
     uint8_t* prep = raw + rp * kDim;
@@ -685,7 +617,7 @@ int amc_upload_descriptors_device(amc_ctx* c, uint32_t slot, const void* dev_des
 }
 
 int amc_get_acos_lut(amc_ctx* c, float* out) {
-    if (!c || !out) return fail(AMC_E_INVALID, "amc_get_acos_lut: NULL argument");
+    if (!c || !out) return api_fail(AMC_E_INVALID, "amc_get_acos_lut: NULL argument");
     HIPCHK(hipSetDevice(c->device));
     // read it back from the device so the test sees what the kernels see
     HIPCHK(hipMemcpy(out, c->d_lut, kAcosLutSize * sizeof(float), hipMemcpyDeviceToHost));
@@ -699,8 +631,7 @@ struct ResultPriv {
     PinBuf<uint32_t> matches;               // leased from the context's pool, returned by amc_match_result_free
     std::shared_ptr<PinnedPool> pool;
     ~ResultPriv() {
-        if (pool) pool->give_back(matches);
-        else matches.release();
+        if (pool) pool->give_back(std::move(matches));
     }
 };
 
@@ -754,10 +685,10 @@ static void verify_streams_sync(amc_ctx* c);
 static int match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, size_t npairs,
                       const amc_match_opts* opts_in, const amc_tvg* geoms, double max_error,
                       amc_match_result* out, std::vector<uint64_t>* keep_off = nullptr, const BatchHook* batch_hook = nullptr) {
-    if (!c || !out) return fail(AMC_E_INVALID, "amc_match_pairs: NULL ctx/out");
+    if (!c || !out) return api_fail(AMC_E_INVALID, "amc_match_pairs: NULL ctx/out");
     std::memset(out, 0, sizeof *out);
     if (npairs > 0 && (!slot1 || !slot2))
-        return fail(AMC_E_INVALID, "amc_match_pairs: NULL pair arrays");
+        return api_fail(AMC_E_INVALID, "amc_match_pairs: NULL pair arrays");
     // AMC_MATCH_PROFILE=1: wall-clock of the call's host phases on stderr
     const bool prof = std::getenv("AMC_MATCH_PROFILE") != nullptr;
     const auto wall0 = std::chrono::steady_clock::now();
@@ -768,14 +699,14 @@ static int match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, 
     amc_match_opts o;
     if (opts_in) o = *opts_in; else amc_match_opts_default(&o);
     if (o.kernel != AMC_KERNEL_AUTO && o.kernel != AMC_KERNEL_MFMA && o.kernel != AMC_KERNEL_DOT4)
-        return fail(AMC_E_INVALID, "amc_match_pairs: unknown kernel %d", o.kernel);
+        return api_fail(AMC_E_INVALID, "amc_match_pairs: unknown kernel %d", o.kernel);
     uint64_t rows_total = 0;  // rows of image 1 (padded) over the call: what is left when a batch is carved
     for (size_t i = 0; i < npairs; ++i) {
         if (slot1[i] >= c->slots.size() || slot2[i] >= c->slots.size())
-            return fail(AMC_E_INVALID, "amc_match_pairs: pair %zu references slot out of range", i);
+            return api_fail(AMC_E_INVALID, "amc_match_pairs: pair %zu references slot out of range", i);
         if (!c->slots[slot1[i]].valid || !c->slots[slot2[i]].valid)
-            return fail(AMC_E_STATE, "amc_match_pairs: pair %zu references a slot with no "
-                        "descriptors uploaded", i);
+            return api_fail(AMC_E_STATE, "amc_match_pairs: pair %zu references a slot with no "
+                            "descriptors uploaded", i);
         rows_total += c->slots[slot1[i]].dev.rows_pad;  // (one pass over the pair list: a loop-closure call has 10^7 pairs)
     }
     std::vector<GuidedDev> h_guided;
@@ -789,16 +720,16 @@ static int match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, 
                      : (cfg == AMC_TVG_PLANAR || cfg == AMC_TVG_PANORAMIC || cfg == AMC_TVG_PLANAR_OR_PANORAMIC)
                          ? kGuidedH : kGuidedNone;
             if (g.kind == kGuidedNone)
-                return fail(AMC_E_INVALID, "amc_match_guided_pairs: pair %zu: configuration %d has no guided "
-                            "matching (COLMAP keeps the inlier matches it has)", i, cfg);
+                return api_fail(AMC_E_INVALID, "amc_match_guided_pairs: pair %zu: configuration %d has no guided "
+                                "matching (COLMAP keeps the inlier matches it has)", i, cfg);
             const double* m = g.kind == kGuidedF ? geoms[i].F : geoms[i].H;
             for (int k = 0; k < 9; ++k) g.m[k] = (float)m[k];
             g.max_residual = (float)(max_error * max_error);
             const Slot& a = c->slots[slot1[i]];
             const Slot& b = c->slots[slot2[i]];
             if (!a.kp || !b.kp || a.kp_rows < a.dev.rows || b.kp_rows < b.dev.rows)
-                return fail(AMC_E_STATE, "amc_match_guided_pairs: pair %zu: float32 keypoints (one per descriptor) "
-                            "must be uploaded for both images", i);
+                return api_fail(AMC_E_STATE, "amc_match_guided_pairs: pair %zu: float32 keypoints (one per descriptor) "
+                                "must be uploaded for both images", i);
             guided_grid_setup(g, a.grid, b.grid, guided_dense_only);
         }
     }
@@ -843,7 +774,7 @@ static int match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, 
     // (everything above returns through HIPCHK: from here on errors go through rc / hc, which give the result's
     // pinned lease back)
     ResultPriv* priv = new (std::nothrow) ResultPriv();
-    if (!priv) return fail(AMC_E_NOMEM, "amc_match_pairs: out of host memory");
+    if (!priv) return api_fail(AMC_E_NOMEM, "amc_match_pairs: out of host memory");
     priv->offsets.assign(npairs + 1, 0);
     priv->pool = c->result_pool;
     priv->matches = c->result_pool->acquire();
@@ -861,7 +792,7 @@ static int match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, 
     int rc = AMC_OK;
     auto hc = [&](hipError_t e, const char* what) {
         if (e != hipSuccess && rc == AMC_OK)
-            rc = fail(AMC_E_HIP, "amc_match_pairs: %s: %s", what, hipGetErrorString(e));
+            rc = api_fail(AMC_E_HIP, "amc_match_pairs: %s: %s", what, hipGetErrorString(e));
         return e == hipSuccess;
     };
     // test hook: a smaller per-batch budget, so that small inputs exercise the multi-batch pipeline
@@ -1002,10 +933,10 @@ static int match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, 
             const Slot& y = c->slots[slot2[begin + i]];
             const bool nonempty = x.dev.rows > 0 && y.dev.rows > 0;
             if (o.kernel == AMC_KERNEL_MFMA && nonempty && !want_mfma[i]) {
-                rc = fail(AMC_E_INVALID,
-                          "amc_match_pairs: kernel=MFMA forced but pair %zu is not eligible "
-                          "(rows_pad=%u, cols_pad=%u > %zu)", begin + i, x.dev.rows_pad,
-                          y.dev.rows_pad, mfma_max_cols);
+                rc = api_fail(AMC_E_INVALID,
+                              "amc_match_pairs: kernel=MFMA forced but pair %zu is not eligible "
+                              "(rows_pad=%u, cols_pad=%u > %zu)", begin + i, x.dev.rows_pad,
+                              y.dev.rows_pad, mfma_max_cols);
                 return false;
             }
             PairDev& pd = hp[i];
@@ -1259,12 +1190,12 @@ static int match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, 
         if (!hc(hipEventSynchronize(c->bev[k][3]), "wait for the batch")) return false;
         b.total = c->h_bscalars[k].p[0];
         if (c->h_bscalars[k].p[3] != 0) {
-            rc = fail(AMC_E_HIP, "amc_match_pairs: internal: %u accepted rows could not be resolved "
-                      "to an index (scan/recompute mismatch)", c->h_bscalars[k].p[3]);
+            rc = api_fail(AMC_E_HIP, "amc_match_pairs: internal: %u accepted rows could not be resolved "
+                          "to an index (scan/recompute mismatch)", c->h_bscalars[k].p[3]);
             return false;
         }
         if (b.total > b.cap) {
-            rc = fail(AMC_E_HIP, "amc_match_pairs: internal: %u matches exceed capacity %zu", b.total, b.cap);
+            rc = api_fail(AMC_E_HIP, "amc_match_pairs: internal: %u matches exceed capacity %zu", b.total, b.cap);
             return false;
         }
         // The batch's matches lie in d_matches in the order the workgroups claimed space (atomic cursor).  Put them
@@ -1280,8 +1211,8 @@ static int match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, 
             priv->offsets[b.begin + i + 1] = run;  // the result's CSR (offsets[0] = 0; batches are collected in order)
         }
         if (run - keep_used != b.total) {
-            rc = fail(AMC_E_HIP, "amc_match_pairs: internal: pair counts (%llu) disagree with the cursor (%u)",
-                      (unsigned long long)(run - keep_used), b.total);
+            rc = api_fail(AMC_E_HIP, "amc_match_pairs: internal: pair counts (%llu) disagree with the cursor (%u)",
+                          (unsigned long long)(run - keep_used), b.total);
             return false;
         }
         rows_collected += b.top_rows;
@@ -1310,8 +1241,7 @@ static int match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, 
                     !hc(hipStreamSynchronize(c->copy_stream), "sync before freeing the old resident table"))
                     return false;
                 if (batch_hook) verify_streams_sync(c);  // (verification slices of earlier batches read the old table)
-                c->d_keep.release();
-                c->d_keep = bigger;
+                c->d_keep = std::move(bigger);
             }
             if (need > priv->matches.cap) {  // grow the result buffer (first calls only: the pool keeps it)
                 if (!sync_batch_streams("sync before growing the result buffer") ||
@@ -1324,8 +1254,7 @@ static int match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, 
                     if (!hc(bigger.ensure(need), "pinned result")) return false;
                 }
                 if (keep_used) std::memcpy(bigger.p, priv->matches.p, 2 * keep_used * sizeof(uint32_t));
-                priv->matches.release();
-                priv->matches = bigger;
+                priv->matches = std::move(bigger);
             }
             if (prof && since(tgrow) > 5.0)
                 std::fprintf(stderr, "[amc match profile] batch of %zu pairs: %.1f ms growing the result tables to %zu words\n", b.nb,
@@ -1447,7 +1376,7 @@ static int match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, 
             have_prev = true;
             cur = next;
         }
-        if (!ok && rc == AMC_OK) rc = fail(AMC_E_HIP, "amc_match_pairs: batch failed");
+        if (!ok && rc == AMC_OK) rc = api_fail(AMC_E_HIP, "amc_match_pairs: batch failed");
         if (rc != AMC_OK) {  // nothing of this call stays in flight
             (void)hipStreamSynchronize(st);
             if (overlap) (void)hipStreamSynchronize(cs);
@@ -1499,11 +1428,11 @@ int amc_match_guided_pairs(amc_ctx* c, const uint32_t* slot1, const uint32_t* sl
                            amc_match_result* out) {
     if (npairs > 0 && !geoms) {
         if (out) std::memset(out, 0, sizeof *out);
-        return fail(AMC_E_INVALID, "amc_match_guided_pairs: NULL geometries");
+        return api_fail(AMC_E_INVALID, "amc_match_guided_pairs: NULL geometries");
     }
     if (!(max_error >= 0.0)) {
         if (out) std::memset(out, 0, sizeof *out);
-        return fail(AMC_E_INVALID, "amc_match_guided_pairs: max_error must be >= 0");
+        return api_fail(AMC_E_INVALID, "amc_match_guided_pairs: max_error must be >= 0");
     }
     static const amc_tvg kNone{};
     return match_impl(c, slot1, slot2, npairs, opts_in, npairs ? geoms : &kNone, max_error, out);
@@ -1555,7 +1484,7 @@ static int build_keypoint_grid(amc_ctx* c, Slot& s, const float* xy, uint32_t ro
     }
     const size_t b_xy = sxy.size() * sizeof(float), b_idx = sidx.size() * sizeof(uint32_t), b_st = start.size() * sizeof(uint32_t);
     hipError_t e = c->arena.alloc(&s.grid_base, b_xy + b_idx + b_st);
-    if (e != hipSuccess) return fail(AMC_E_NOMEM, "amc_upload_keypoints: hipMalloc (grid): %s", hipGetErrorString(e));
+    if (e != hipSuccess) return api_fail(AMC_E_NOMEM, "amc_upload_keypoints: hipMalloc (grid): %s", hipGetErrorString(e));
     char* base = static_cast<char*>(s.grid_base);
     HIPCHK(hipMemcpy(base, sxy.data(), b_xy, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(base + b_xy, sidx.data(), b_idx, hipMemcpyHostToDevice));
@@ -1569,11 +1498,11 @@ static int build_keypoint_grid(amc_ctx* c, Slot& s, const float* xy, uint32_t ro
 
 int amc_upload_keypoints(amc_ctx* c, uint32_t slot, const float* xy, uint32_t rows,
                          uint32_t stride_floats) {
-    if (!c) return fail(AMC_E_INVALID, "amc_upload_keypoints: ctx is NULL");
+    if (!c) return api_fail(AMC_E_INVALID, "amc_upload_keypoints: ctx is NULL");
     if (slot >= c->slots.size())
-        return fail(AMC_E_INVALID, "amc_upload_keypoints: slot %u >= reserved %zu", slot, c->slots.size());
+        return api_fail(AMC_E_INVALID, "amc_upload_keypoints: slot %u >= reserved %zu", slot, c->slots.size());
     if (rows > 0 && (!xy || stride_floats < 2))
-        return fail(AMC_E_INVALID, "amc_upload_keypoints: need x,y columns (stride %u) and data", stride_floats);
+        return api_fail(AMC_E_INVALID, "amc_upload_keypoints: need x,y columns (stride %u) and data", stride_floats);
     HIPCHK(hipSetDevice(c->device));
     Slot& s = c->slots[slot];
     if (s.kp || s.kp64 || s.kpn || s.grid_base) {
@@ -1603,7 +1532,7 @@ int amc_upload_keypoints(amc_ctx* c, uint32_t slot, const float* xy, uint32_t ro
     hipError_t e = c->arena.alloc(&s.kp, packed.size() * sizeof(float));
     if (e != hipSuccess) {
         s.has_kp = false;
-        return fail(AMC_E_NOMEM, "amc_upload_keypoints: hipMalloc: %s", hipGetErrorString(e));
+        return api_fail(AMC_E_NOMEM, "amc_upload_keypoints: hipMalloc: %s", hipGetErrorString(e));
     }
     HIPCHK(hipMemcpy(s.kp, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
     s.dev.kp = s.kp;  // guided matching reads the float32 keypoints from the image table
@@ -1613,10 +1542,10 @@ int amc_upload_keypoints(amc_ctx* c, uint32_t slot, const float* xy, uint32_t ro
 }
 
 int amc_upload_points_f64(amc_ctx* c, uint32_t slot, const double* xy, uint32_t rows) {
-    if (!c) return fail(AMC_E_INVALID, "amc_upload_points_f64: ctx is NULL");
+    if (!c) return api_fail(AMC_E_INVALID, "amc_upload_points_f64: ctx is NULL");
     if (slot >= c->slots.size())
-        return fail(AMC_E_INVALID, "amc_upload_points_f64: slot %u >= reserved %zu", slot, c->slots.size());
-    if (rows > 0 && !xy) return fail(AMC_E_INVALID, "amc_upload_points_f64: NULL data");
+        return api_fail(AMC_E_INVALID, "amc_upload_points_f64: slot %u >= reserved %zu", slot, c->slots.size());
+    if (rows > 0 && !xy) return api_fail(AMC_E_INVALID, "amc_upload_points_f64: NULL data");
     HIPCHK(hipSetDevice(c->device));
     Slot& s = c->slots[slot];
     if (s.kp || s.kp64 || s.kpn || s.grid_base) {
@@ -1641,7 +1570,7 @@ int amc_upload_points_f64(amc_ctx* c, uint32_t slot, const double* xy, uint32_t 
     hipError_t e = c->arena.alloc(&s.kp64, (size_t)rows * 2 * sizeof(double));
     if (e != hipSuccess) {
         s.has_kp = false;
-        return fail(AMC_E_NOMEM, "amc_upload_points_f64: hipMalloc: %s", hipGetErrorString(e));
+        return api_fail(AMC_E_NOMEM, "amc_upload_points_f64: hipMalloc: %s", hipGetErrorString(e));
     }
     HIPCHK(hipMemcpy(s.kp64, xy, (size_t)rows * 2 * sizeof(double), hipMemcpyHostToDevice));
     return AMC_OK;
@@ -1649,17 +1578,17 @@ int amc_upload_points_f64(amc_ctx* c, uint32_t slot, const double* xy, uint32_t 
 
 int amc_upload_camera(amc_ctx* c, uint32_t slot, int32_t model_id, uint64_t width, uint64_t height,
                       const double* params, int32_t num_params, int32_t has_prior) {
-    if (!c) return fail(AMC_E_INVALID, "amc_upload_camera: ctx is NULL");
+    if (!c) return api_fail(AMC_E_INVALID, "amc_upload_camera: ctx is NULL");
     if (slot >= c->slots.size())
-        return fail(AMC_E_INVALID, "amc_upload_camera: slot %u >= reserved %zu", slot, c->slots.size());
+        return api_fail(AMC_E_INVALID, "amc_upload_camera: slot %u >= reserved %zu", slot, c->slots.size());
     if (num_params < 0 || (num_params > 0 && !params))
-        return fail(AMC_E_INVALID, "amc_upload_camera: bad params");
+        return api_fail(AMC_E_INVALID, "amc_upload_camera: bad params");
     // Camera::VerifyParams: the parameter vector must have the model's length
     if (cam::num_params(model_id) < 0)
-        return fail(AMC_E_INVALID, "amc_upload_camera: unknown camera model id %d", model_id);
+        return api_fail(AMC_E_INVALID, "amc_upload_camera: unknown camera model id %d", model_id);
     if (num_params != cam::num_params(model_id))
-        return fail(AMC_E_INVALID, "amc_upload_camera: camera model %d takes %d parameters, got %d", model_id,
-                    cam::num_params(model_id), num_params);
+        return api_fail(AMC_E_INVALID, "amc_upload_camera: camera model %d takes %d parameters, got %d", model_id,
+                        cam::num_params(model_id), num_params);
     Slot& s = c->slots[slot];
     s.cam = CameraDev{};
     s.cam.model_id = model_id;
@@ -1687,7 +1616,7 @@ static int ensure_normalized(amc_ctx* c, uint32_t slot) {
     }
     if (!s.kpn) {
         hipError_t e = c->arena.alloc(&s.kpn, (size_t)rows * 2 * sizeof(double));
-        if (e != hipSuccess) return fail(AMC_E_NOMEM, "CamFromImg buffer: hipMalloc: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return api_fail(AMC_E_NOMEM, "CamFromImg buffer: hipMalloc: %s", hipGetErrorString(e));
     }
     if (!cam::needs_libm(s.cam.model_id)) {
         HIPCHK(launch_undistort(s.kp, s.kp64, rows, s.cam, s.kpn, c->stream));
@@ -1728,14 +1657,14 @@ static int ensure_normalized(amc_ctx* c, uint32_t slot) {
 
 int amc_cam_from_img(amc_ctx* c, int32_t model_id, const double* params, int32_t num_params, const double* xy,
                      size_t n, double* uv) {
-    if (!c) return fail(AMC_E_INVALID, "amc_cam_from_img: ctx is NULL");
-    if (cam::num_params(model_id) < 0) return fail(AMC_E_INVALID, "amc_cam_from_img: unknown camera model id %d", model_id);
+    if (!c) return api_fail(AMC_E_INVALID, "amc_cam_from_img: ctx is NULL");
+    if (cam::num_params(model_id) < 0) return api_fail(AMC_E_INVALID, "amc_cam_from_img: unknown camera model id %d", model_id);
     if (num_params != cam::num_params(model_id) || !params)
-        return fail(AMC_E_INVALID, "amc_cam_from_img: camera model %d takes %d parameters, got %d", model_id,
-                    cam::num_params(model_id), num_params);
+        return api_fail(AMC_E_INVALID, "amc_cam_from_img: camera model %d takes %d parameters, got %d", model_id,
+                        cam::num_params(model_id), num_params);
     if (n == 0) return AMC_OK;
-    if (!xy || !uv) return fail(AMC_E_INVALID, "amc_cam_from_img: NULL points");
-    if (n > 0x7FFFFFFFull) return fail(AMC_E_INVALID, "amc_cam_from_img: too many points");
+    if (!xy || !uv) return api_fail(AMC_E_INVALID, "amc_cam_from_img: NULL points");
+    if (n > 0x7FFFFFFFull) return api_fail(AMC_E_INVALID, "amc_cam_from_img: too many points");
     if (cam::needs_libm(model_id)) {
         for (size_t i = 0; i < n; ++i) cam::cam_from_img(model_id, params, xy[2 * i], xy[2 * i + 1], uv[2 * i], uv[2 * i + 1]);
         return AMC_OK;
@@ -1749,26 +1678,25 @@ int amc_cam_from_img(amc_ctx* c, int32_t model_id, const double* params, int32_t
     hipStream_t st = c->stream;
     int rc = AMC_OK;
     auto chk = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == AMC_OK) rc = fail(AMC_E_HIP, "amc_cam_from_img: %s: %s", what, hipGetErrorString(e));
+        if (e != hipSuccess && rc == AMC_OK) rc = api_fail(AMC_E_HIP, "amc_cam_from_img: %s: %s", what, hipGetErrorString(e));
     };
     chk(hipMemcpyAsync(buf.p, xy, 2 * n * sizeof(double), hipMemcpyHostToDevice, st), "copy in");
     if (rc == AMC_OK) chk(launch_undistort(nullptr, buf.p, (uint32_t)n, cd, buf.p + 2 * n, st), "launch");
     if (rc == AMC_OK) chk(hipMemcpyAsync(uv, buf.p + 2 * n, 2 * n * sizeof(double), hipMemcpyDeviceToHost, st), "copy out");
     chk(hipStreamSynchronize(st), "sync");
-    buf.release();
     return rc;
 }
 
 int amc_img_from_cam(amc_ctx* c, int32_t model_id, const double* params, int32_t num_params, const double* uv,
                      size_t n, double* xy) {
-    if (!c) return fail(AMC_E_INVALID, "amc_img_from_cam: ctx is NULL");
-    if (cam::num_params(model_id) < 0) return fail(AMC_E_INVALID, "amc_img_from_cam: unknown camera model id %d", model_id);
+    if (!c) return api_fail(AMC_E_INVALID, "amc_img_from_cam: ctx is NULL");
+    if (cam::num_params(model_id) < 0) return api_fail(AMC_E_INVALID, "amc_img_from_cam: unknown camera model id %d", model_id);
     if (num_params != cam::num_params(model_id) || !params)
-        return fail(AMC_E_INVALID, "amc_img_from_cam: camera model %d takes %d parameters, got %d", model_id,
-                    cam::num_params(model_id), num_params);
+        return api_fail(AMC_E_INVALID, "amc_img_from_cam: camera model %d takes %d parameters, got %d", model_id,
+                        cam::num_params(model_id), num_params);
     if (n == 0) return AMC_OK;
-    if (!uv || !xy) return fail(AMC_E_INVALID, "amc_img_from_cam: NULL points");
-    if (n > 0x7FFFFFFFull) return fail(AMC_E_INVALID, "amc_img_from_cam: too many points");
+    if (!uv || !xy) return api_fail(AMC_E_INVALID, "amc_img_from_cam: NULL points");
+    if (n > 0x7FFFFFFFull) return api_fail(AMC_E_INVALID, "amc_img_from_cam: too many points");
     if (cam::needs_libm(model_id)) {
         for (size_t i = 0; i < n; ++i) cam::img_from_cam(model_id, params, uv[2 * i], uv[2 * i + 1], xy[2 * i], xy[2 * i + 1]);
         return AMC_OK;
@@ -1782,13 +1710,12 @@ int amc_img_from_cam(amc_ctx* c, int32_t model_id, const double* params, int32_t
     hipStream_t st = c->stream;
     int rc = AMC_OK;
     auto chk = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == AMC_OK) rc = fail(AMC_E_HIP, "amc_img_from_cam: %s: %s", what, hipGetErrorString(e));
+        if (e != hipSuccess && rc == AMC_OK) rc = api_fail(AMC_E_HIP, "amc_img_from_cam: %s: %s", what, hipGetErrorString(e));
     };
     chk(hipMemcpyAsync(buf.p, uv, 2 * n * sizeof(double), hipMemcpyHostToDevice, st), "copy in");
     if (rc == AMC_OK) chk(launch_project(buf.p, (uint32_t)n, cd, buf.p + 2 * n, st), "launch");
     if (rc == AMC_OK) chk(hipMemcpyAsync(xy, buf.p + 2 * n, 2 * n * sizeof(double), hipMemcpyDeviceToHost, st), "copy out");
     chk(hipStreamSynchronize(st), "sync");
-    buf.release();
     return rc;
 }
 
@@ -1807,24 +1734,6 @@ static void fill_tvg_images(const amc_ctx* c, std::vector<TvgImage>& timgs) {
 
 namespace {
 
-// RANSAC::ComputeNumTrials (colmap/optim/ransac.h) with the HOST libm, as COLMAP evaluates it
-size_t compute_num_trials_host(size_t num_inliers, size_t num_samples, double confidence,
-                               double multiplier, int kmin) {
-    const double inlier_ratio = num_inliers / static_cast<double>(num_samples);
-    const double nom = 1 - confidence;
-    if (nom <= 0) return std::numeric_limits<size_t>::max();
-    const double denom = 1 - std::pow(inlier_ratio, kmin);
-    if (denom <= 0) return 1;
-    if (denom == 1.0) return std::numeric_limits<size_t>::max();
-    return static_cast<size_t>(std::ceil(std::log(nom) / std::log(denom) * multiplier));
-}
-size_t ransac_max_trials_host(const amc_ransac_opts& o, double min_inlier_ratio, int kmin) {
-    const size_t kNumSamples = 100000;
-    const size_t dyn = compute_num_trials_host(static_cast<size_t>(min_inlier_ratio * kNumSamples), kNumSamples,
-                                               o.confidence, o.dyn_num_trials_multiplier, kmin);
-    return std::min<size_t>(static_cast<size_t>(o.max_num_trials), dyn);
-}
-
 struct VerifyPriv {
     std::vector<amc_tvg> tvg;
     std::vector<uint8_t> mask;
@@ -1839,8 +1748,8 @@ struct VerifyPriv {
     PinBuf<uint32_t> tvg_pin, mask_pin;
     ~VerifyPriv() {
         if (pool) {
-            pool->give_back(tvg_pin);
-            pool->give_back(mask_pin);
+            pool->give_back(std::move(tvg_pin));
+            pool->give_back(std::move(mask_pin));
         }
     }
 };
@@ -1866,13 +1775,13 @@ static int pose_impl(amc_ctx* c, const char* who, const uint32_t* slot1, const u
     // is uploaded again and the kernel takes the rows whose byte is set.  Their indices have been checked.
     const bool resident = resident_mask_off != nullptr;
     if (kernel_ms) *kernel_ms = 0.0;
-    if (!c) return fail(AMC_E_INVALID, "%s: NULL ctx", who);
+    if (!c) return api_fail(AMC_E_INVALID, "%s: NULL ctx", who);
     if (npairs == 0) return AMC_OK;
     if (!slot1 || !slot2 || !match_offsets || !geoms || !out)
-        return fail(AMC_E_INVALID, "%s: NULL pair arrays", who);
+        return api_fail(AMC_E_INVALID, "%s: NULL pair arrays", who);
     const uint64_t total = match_offsets[npairs];
-    if (total > 0 && !inlier_matches && !resident) return fail(AMC_E_INVALID, "%s: NULL matches", who);
-    if (npairs > 0xFFFFFFFFull) return fail(AMC_E_INVALID, "%s: too many pairs", who);
+    if (total > 0 && !inlier_matches && !resident) return api_fail(AMC_E_INVALID, "%s: NULL matches", who);
+    if (npairs > 0xFFFFFFFFull) return api_fail(AMC_E_INVALID, "%s: too many pairs", who);
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));  // (an earlier call's upload of the staging buffer is over: every entry point blocks)
     HIPCHK(c->h_ppairs.ensure(npairs));
@@ -1880,15 +1789,15 @@ static int pose_impl(amc_ctx* c, const char* who, const uint32_t* slot1, const u
     std::vector<uint8_t> need_lift(c->slots.size(), 0);
     for (size_t p = 0; p < npairs; ++p) {
         if (slot1[p] >= c->slots.size() || slot2[p] >= c->slots.size())
-            return fail(AMC_E_INVALID, "%s: pair %zu references slot out of range", who, p);
+            return api_fail(AMC_E_INVALID, "%s: pair %zu references slot out of range", who, p);
         const Slot& a = c->slots[slot1[p]];
         const Slot& b = c->slots[slot2[p]];
         if (!a.has_kp || !b.has_kp || !a.has_cam || !b.has_cam)
-            return fail(AMC_E_STATE, "%s: pair %zu: keypoints/camera not uploaded", who, p);
+            return api_fail(AMC_E_STATE, "%s: pair %zu: keypoints/camera not uploaded", who, p);
         if (match_offsets[p + 1] < match_offsets[p])
-            return fail(AMC_E_INVALID, "%s: match_offsets not monotone at %zu", who, p);
+            return api_fail(AMC_E_INVALID, "%s: match_offsets not monotone at %zu", who, p);
         const uint64_t M = match_offsets[p + 1] - match_offsets[p];
-        if (M > 0xFFFFFFFFull) return fail(AMC_E_INVALID, "%s: pair %zu has too many matches", who, p);
+        if (M > 0xFFFFFFFFull) return api_fail(AMC_E_INVALID, "%s: pair %zu has too many matches", who, p);
         const int32_t cfg = geoms[p].config;
         const bool has_geometry = cfg == AMC_TVG_CALIBRATED || cfg == AMC_TVG_UNCALIBRATED || cfg == AMC_TVG_PLANAR ||
                                   cfg == AMC_TVG_PANORAMIC || cfg == AMC_TVG_PLANAR_OR_PANORAMIC;
@@ -1896,8 +1805,8 @@ static int pose_impl(amc_ctx* c, const char* who, const uint32_t* slot1, const u
         if (!resident)
             for (uint64_t k = match_offsets[p]; k < match_offsets[p + 1]; ++k)
                 if (inlier_matches[2 * k] >= a.kp_rows || inlier_matches[2 * k + 1] >= b.kp_rows)
-                    return fail(AMC_E_INVALID, "%s: pair %zu match %llu indexes past the keypoints", who, p,
-                                (unsigned long long)(k - match_offsets[p]));
+                    return api_fail(AMC_E_INVALID, "%s: pair %zu match %llu indexes past the keypoints", who, p,
+                                    (unsigned long long)(k - match_offsets[p]));
         pp[p].slot1 = slot1[p];
         pp[p].slot2 = slot2[p];
         pp[p].match_off = (resident && resident_match_off) ? resident_match_off[p] : match_offsets[p];
@@ -2089,20 +1998,20 @@ struct VerifyRun {
 
 int VerifyRun::begin(size_t) {
     if (o.compute_relative_pose && mode != 0)
-        return fail(AMC_E_INVALID, "amc_verify_pairs: internal: compute_relative_pose outside mode 0");
+        return api_fail(AMC_E_INVALID, "amc_verify_pairs: internal: compute_relative_pose outside mode 0");
     if (o.multiple_models)
-        return fail(AMC_E_INVALID, "amc_verify_pairs: internal: multiple_models reaches verify_impl");
+        return api_fail(AMC_E_INVALID, "amc_verify_pairs: internal: multiple_models reaches verify_impl");
     if (o.ransac.max_num_trials < 0 || o.ransac.min_num_trials < 0 || o.ransac.max_num_trials > (1 << 30))
-        return fail(AMC_E_INVALID, "amc_verify_pairs: bad trial limits");
+        return api_fail(AMC_E_INVALID, "amc_verify_pairs: bad trial limits");
     std::vector<uint8_t> need_lift(c->slots.size(), 0);
     for (size_t p = 0; p < npairs; ++p) {
         if (slot1[p] >= c->slots.size() || slot2[p] >= c->slots.size())
-            return fail(AMC_E_INVALID, "amc_verify_pairs: pair %zu references slot out of range", p);
+            return api_fail(AMC_E_INVALID, "amc_verify_pairs: pair %zu references slot out of range", p);
         const Slot& a = c->slots[slot1[p]];
         const Slot& b = c->slots[slot2[p]];
         const bool need_cam = mode == 0 || mode == 3;
         if (!a.has_kp || !b.has_kp || (need_cam && (!a.has_cam || !b.has_cam)))
-            return fail(AMC_E_STATE, "amc_verify_pairs: pair %zu: keypoints/camera not uploaded", p);
+            return api_fail(AMC_E_STATE, "amc_verify_pairs: pair %zu: keypoints/camera not uploaded", p);
         const bool e = mode == 0 ? (!o.force_H_use && a.cam.has_prior && b.cam.has_prior) : mode == 3;
         if (e) need_lift[slot1[p]] = need_lift[slot2[p]] = 1;
     }
@@ -2110,10 +2019,11 @@ int VerifyRun::begin(size_t) {
     P.detect_watermark = o.detect_watermark;
     P.force_H_use = o.force_H_use;
     P.min_num_trials = (int32_t)std::min<int64_t>(o.ransac.min_num_trials, 1 << 30);
-    P.max_trials[0] = (int32_t)ransac_max_trials_host(o.ransac, o.ransac.min_inlier_ratio, 5);
-    P.max_trials[1] = (int32_t)ransac_max_trials_host(o.ransac, o.ransac.min_inlier_ratio, 7);
-    P.max_trials[2] = (int32_t)ransac_max_trials_host(o.ransac, o.ransac.min_inlier_ratio, 4);
-    P.max_trials[3] = (int32_t)ransac_max_trials_host(o.ransac, o.watermark_min_inlier_ratio, 1);
+    const double conf = o.ransac.confidence, mult = o.ransac.dyn_num_trials_multiplier;
+    P.max_trials[0] = (int32_t)tvg::ransac_max_trials(o.ransac.max_num_trials, o.ransac.min_inlier_ratio, conf, mult, 5);
+    P.max_trials[1] = (int32_t)tvg::ransac_max_trials(o.ransac.max_num_trials, o.ransac.min_inlier_ratio, conf, mult, 7);
+    P.max_trials[2] = (int32_t)tvg::ransac_max_trials(o.ransac.max_num_trials, o.ransac.min_inlier_ratio, conf, mult, 4);
+    P.max_trials[3] = (int32_t)tvg::ransac_max_trials(o.ransac.max_num_trials, o.watermark_min_inlier_ratio, conf, mult, 1);
     P.min_E_F_inlier_ratio = o.min_E_F_inlier_ratio;
     P.max_H_inlier_ratio = o.max_H_inlier_ratio;
     P.watermark_min_inlier_ratio = o.watermark_min_inlier_ratio;
@@ -2132,12 +2042,7 @@ int VerifyRun::begin(size_t) {
     // inlier-ratio cut-offs of the watermark RANSAC's dynamic trial count (TvgParams::wm_cut)
     if (mode == 0 && o.detect_watermark) {
         auto dyn_of_ratio = [&](double r) -> size_t {  // ComputeNumTrials with inlier_ratio = r, kMinNumSamples = 1
-            const double nom = 1 - o.ransac.confidence;
-            if (nom <= 0) return std::numeric_limits<size_t>::max();
-            const double denom = 1 - std::pow(r, 1);
-            if (denom <= 0) return 1;
-            if (denom == 1.0) return std::numeric_limits<size_t>::max();
-            return static_cast<size_t>(std::ceil(std::log(nom) / std::log(denom) * o.ransac.dyn_num_trials_multiplier));
+            return tvg::num_trials_of_ratio(r, conf, mult, 1);
         };
         const int nT = std::max(P.max_trials[3], 0);
         // (the cut-offs depend on (confidence, multiplier, max_trials) only: kept across calls)
@@ -2189,8 +2094,8 @@ int VerifyRun::begin(size_t) {
     // a table twice as long - is exercised; production tables only ever overrun by a Lemire rejection streak)
     if (std::getenv("AMC_TVG_STREAM_SHORT")) stream_need = std::max<size_t>(8192, stream_need / 4);
     if (stream_need > kMaxStreamWords)
-        return fail(AMC_E_INVALID, "amc_verify_pairs: ransac.max_num_trials / min_inlier_ratio allow %zu draws per pair: "
-                    "more than the sample-stream table holds (%zu)", stream_need, kMaxStreamWords);
+        return api_fail(AMC_E_INVALID, "amc_verify_pairs: ransac.max_num_trials / min_inlier_ratio allow %zu draws per pair: "
+                        "more than the sample-stream table holds (%zu)", stream_need, kMaxStreamWords);
     HIPCHK(ensure_sample_stream(c, seed, stream_need));
     HIPCHK(c->d_timgs.ensure(timgs.size()));
     HIPCHK(c->d_estate.ensure(npairs));
@@ -2234,7 +2139,7 @@ int VerifyRun::begin(size_t) {
 // add_pairs: pairs [begin, end) join the OPEN slice - checks, pair records, trial tables, size classes (host only).
 int VerifyRun::add_pairs(size_t begin, size_t end, const uint64_t* offs, const uint64_t* dev_off, const uint32_t* matches_dev,
                          const uint32_t* matches_host) {
-    if (begin != submitted || end < begin || end > npairs) return fail(AMC_E_INVALID, "amc_verify_pairs: internal: slices out of order");
+    if (begin != submitted || end < begin || end > npairs) return api_fail(AMC_E_INVALID, "amc_verify_pairs: internal: slices out of order");
     if (end == begin) return AMC_OK;
     kernel_matches = matches_dev;
     const auto t0 = std::chrono::steady_clock::now();
@@ -2245,9 +2150,9 @@ int VerifyRun::add_pairs(size_t begin, size_t end, const uint64_t* offs, const u
     }
     uint32_t add_maxM = 0;
     for (size_t p = begin; p < end; ++p) {
-        if (offs[p + 1] < offs[p]) return fail(AMC_E_INVALID, "amc_verify_pairs: match_offsets not monotone at %zu", p);
+        if (offs[p + 1] < offs[p]) return api_fail(AMC_E_INVALID, "amc_verify_pairs: match_offsets not monotone at %zu", p);
         const uint64_t M = offs[p + 1] - offs[p];
-        if (M > 65535) return fail(AMC_E_INVALID, "amc_verify_pairs: pair %zu has %llu matches (> 65535)", p, (unsigned long long)M);
+        if (M > 65535) return api_fail(AMC_E_INVALID, "amc_verify_pairs: pair %zu has %llu matches (> 65535)", p, (unsigned long long)M);
         add_maxM = std::max<uint32_t>(add_maxM, (uint32_t)M);
         // Match indices are checked by the kernel where it gathers the points (bad_index_count); only the pairs no
         // kernel looks at - fewer matches than min_num_inliers - are checked here.
@@ -2257,7 +2162,7 @@ int VerifyRun::add_pairs(size_t begin, size_t end, const uint64_t* offs, const u
             const uint32_t* mm = matches_host + 2 * offs[p];
             for (uint64_t k = 0; k < M; ++k)
                 if (mm[2 * k] >= a.kp_rows || mm[2 * k + 1] >= b.kp_rows)
-                    return fail(AMC_E_INVALID, "amc_verify_pairs: pair %zu match %llu indexes past the keypoints", p, (unsigned long long)k);
+                    return api_fail(AMC_E_INVALID, "amc_verify_pairs: pair %zu match %llu indexes past the keypoints", p, (unsigned long long)k);
         }
     }
     maxM = std::max(maxM, add_maxM);
@@ -2269,7 +2174,7 @@ int VerifyRun::add_pairs(size_t begin, size_t end, const uint64_t* offs, const u
         t3.reserve(3 * ((size_t)M + 1));
         for (int t = 0; t < 3; ++t)
             for (uint32_t i = 0; i <= M; ++i) {
-                const size_t v = M ? compute_num_trials_host(i, M, o.ransac.confidence, o.ransac.dyn_num_trials_multiplier, kmins[t]) : 0;
+                const size_t v = M ? tvg::compute_num_trials(i, M, o.ransac.confidence, o.ransac.dyn_num_trials_multiplier, kmins[t]) : 0;
                 t3.push_back(v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)v);
             }
         return t3;
@@ -2363,7 +2268,7 @@ int VerifyRun::add_pairs(size_t begin, size_t end, const uint64_t* offs, const u
 // close_slice: the open slice's class lists (largest pairs first), its uploads and - unless deferred - its launches
 int VerifyRun::close_slice(hipEvent_t ready) {
     if (!open.active) return AMC_OK;
-    if (slices.size() >= (size_t)kMaxVerifySlices) return fail(AMC_E_INVALID, "amc_verify_pairs: internal: too many slices");
+    if (slices.size() >= (size_t)kMaxVerifySlices) return api_fail(AMC_E_INVALID, "amc_verify_pairs: internal: too many slices");
     const auto t1 = std::chrono::steady_clock::now();
     VerifySliceInfo sl;
     sl.begin = open.begin;
@@ -2372,7 +2277,7 @@ int VerifyRun::close_slice(hipEvent_t ready) {
     const size_t si = slices.size();
     if (c->vslices.size() <= si) c->vslices.resize(si + 1);
     if (!c->vslices[si]) c->vslices[si].reset(new (std::nothrow) VerifySliceBufs());
-    if (!c->vslices[si]) return fail(AMC_E_NOMEM, "amc_verify_pairs: out of host memory");
+    if (!c->vslices[si]) return api_fail(AMC_E_NOMEM, "amc_verify_pairs: out of host memory");
     VerifySliceBufs& B = *c->vslices[si];
     const std::vector<uint32_t>& tabs = open.tabs;
     const uint32_t slice_maxM = open.maxM;
@@ -2469,12 +2374,14 @@ int VerifyRun::launch_slice(size_t si, hipEvent_t ready) {
     // side would want twice the CUs the scan left)
     const bool one = !sl.launches.empty() && sl.launches[0].one_stream;
     hipStream_t st_fh = one ? st_e : this->st_fh;
-    if (!B.ev[0]) {
-        for (auto& e : B.ev)
-            if (hipEventCreate(&e) != hipSuccess) return fail(AMC_E_HIP, "amc_verify_pairs: hipEventCreate failed");
-        if (hipEventCreateWithFlags(&B.ev_e_done, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&B.ev_aux_done, hipEventDisableTiming) != hipSuccess)
-            return fail(AMC_E_HIP, "amc_verify_pairs: hipEventCreate failed");
+    if (!B.ev[0]) {  // the slice's six events: all of them, or none and the call fails
+        const unsigned flags[6] = {hipEventDefault, hipEventDefault, hipEventDefault, hipEventDefault,
+                                   hipEventDisableTiming, hipEventDisableTiming};
+        hipEvent_t e[6];
+        if (create_events(e, 6, flags) != hipSuccess) return api_fail(AMC_E_HIP, "amc_verify_pairs: hipEventCreate failed");
+        std::copy(e, e + 4, B.ev);
+        B.ev_e_done = e[4];
+        B.ev_aux_done = e[5];
     }
     auto wait_inputs = [&](hipStream_t s) -> hipError_t {
         hipError_t e = s == c->stream ? hipSuccess : hipStreamWaitEvent(s, c->vev_setup, 0);
@@ -2584,11 +2491,11 @@ static int verify_impl(amc_ctx* c, int mode, const uint32_t* slot1, const uint32
                        const uint64_t* match_offsets, const uint32_t* matches,
                        const amc_tvg_opts* opts_in, uint32_t seed, amc_verify_result* out,
                        const uint32_t* dev_matches = nullptr, const uint64_t* dev_off = nullptr) {
-    if (!c || !out) return fail(AMC_E_INVALID, "amc_verify_pairs: NULL ctx/out");
+    if (!c || !out) return api_fail(AMC_E_INVALID, "amc_verify_pairs: NULL ctx/out");
     std::memset(out, 0, sizeof *out);
     c->vres = amc::VerifyResident{};
     if (npairs > 0 && (!slot1 || !slot2 || !match_offsets))
-        return fail(AMC_E_INVALID, "amc_verify_pairs: NULL pair arrays");
+        return api_fail(AMC_E_INVALID, "amc_verify_pairs: NULL pair arrays");
     const auto wall0 = std::chrono::steady_clock::now();
     VerifyRun run{};
     run.c = c;
@@ -2599,14 +2506,14 @@ static int verify_impl(amc_ctx* c, int mode, const uint32_t* slot1, const uint32
     if (opts_in) run.o = *opts_in; else amc_tvg_opts_default(&run.o);
     run.seed = seed;
     const uint64_t total = npairs ? match_offsets[npairs] : 0;
-    if (total > 0 && !matches && !dev_matches) return fail(AMC_E_INVALID, "amc_verify_pairs: NULL matches");
+    if (total > 0 && !matches && !dev_matches) return api_fail(AMC_E_INVALID, "amc_verify_pairs: NULL matches");
     for (size_t p = 0; p < npairs; ++p)
         if (match_offsets[p + 1] < match_offsets[p])
-            return fail(AMC_E_INVALID, "amc_verify_pairs: match_offsets not monotone at %zu", p);
+            return api_fail(AMC_E_INVALID, "amc_verify_pairs: match_offsets not monotone at %zu", p);
     int rc = run.begin(total);
     if (rc != AMC_OK) return rc;
     VerifyPriv* priv = new (std::nothrow) VerifyPriv();
-    if (!priv) return fail(AMC_E_NOMEM, "amc_verify_pairs: out of host memory");
+    if (!priv) return api_fail(AMC_E_NOMEM, "amc_verify_pairs: out of host memory");
     // every failure below (HIPCHK returns included) frees the result's storage and hands back a zeroed struct
     // - after nothing of the call is left in flight: launches on the other streams still run when an error returns, and
     // the next call would rewrite their lists and workspaces under them
@@ -2686,13 +2593,13 @@ static int verify_finish(amc_ctx* c, VerifyRun& run, const uint64_t* match_offse
     priv->mask_pin = c->verify_pool->acquire((size_t)(std::max<uint64_t>(total, 1) + 3) / 4);
     if (priv->tvg_pin.ensure((std::max<size_t>(npairs, 1) * sizeof(amc_tvg) + 3) / 4) != hipSuccess ||
         priv->mask_pin.ensure((size_t)(std::max<uint64_t>(total, 1) + 3) / 4) != hipSuccess)
-        return fail(AMC_E_NOMEM, "amc_verify_pairs: out of pinned host memory");
+        return api_fail(AMC_E_NOMEM, "amc_verify_pairs: out of pinned host memory");
     out->npairs = npairs;
     out->_priv = priv;
     out->tvg = reinterpret_cast<amc_tvg*>(priv->tvg_pin.p);
     out->inlier_mask = reinterpret_cast<uint8_t*>(priv->mask_pin.p);
     if (npairs == 0) return AMC_OK;
-    if (run.submitted != npairs) return fail(AMC_E_INVALID, "amc_verify_pairs: internal: %zu of %zu pairs submitted", run.submitted, npairs);
+    if (run.submitted != npairs) return api_fail(AMC_E_INVALID, "amc_verify_pairs: internal: %zu of %zu pairs submitted", run.submitted, npairs);
     double kernel_ms = 0.0;
     for (int attempt = 0;; ++attempt) {
         {
@@ -2726,7 +2633,7 @@ static int verify_finish(amc_ctx* c, VerifyRun& run, const uint64_t* match_offse
         // a Lemire rejection loop ran past the table (probability ~1e-6 per 4096 spare words): lay out more, redo -
         // every slice again (the lists are still on the device), behind each other
         if (attempt >= 4 || c->stream_len * 2 > kMaxStreamWords)
-            return fail(AMC_E_HIP, "amc_verify_pairs: the sample stream table was exhausted %d times", attempt + 1);
+            return api_fail(AMC_E_HIP, "amc_verify_pairs: the sample stream table was exhausted %d times", attempt + 1);
         HIPCHK(ensure_sample_stream(c, run.seed, c->stream_len * 2));
         run.P.stream = c->d_stream.p;
         run.P.stream_len = (uint32_t)std::min<size_t>(c->stream_len, 0xFFFFFFFFu);
@@ -2778,10 +2685,10 @@ static int verify_finish(amc_ctx* c, VerifyRun& run, const uint64_t* match_offse
             const Slot& b = c->slots[run.slot2[p]];
             for (uint64_t k = match_offsets[p]; k < match_offsets[p + 1]; ++k)
                 if (matches[2 * k] >= a.kp_rows || matches[2 * k + 1] >= b.kp_rows)
-                    return fail(AMC_E_INVALID, "amc_verify_pairs: pair %zu match %llu indexes past the keypoints", p,
-                                (unsigned long long)(k - match_offsets[p]));
+                    return api_fail(AMC_E_INVALID, "amc_verify_pairs: pair %zu match %llu indexes past the keypoints", p,
+                                    (unsigned long long)(k - match_offsets[p]));
         }
-        return fail(AMC_E_INVALID, "amc_verify_pairs: %u pairs index past the keypoints", bad_pairs);
+        return api_fail(AMC_E_INVALID, "amc_verify_pairs: %u pairs index past the keypoints", bad_pairs);
     }
     if (want_prof) {
         const TvgOut* h_out = c->h_tout.p;
@@ -2850,16 +2757,16 @@ static int verify_multiple(amc_ctx* c, const uint32_t* slot1, const uint32_t* sl
                            uint32_t seed, amc_verify_result* out) {
     std::memset(out, 0, sizeof *out);
     if (npairs > 0 && (!slot1 || !slot2 || !match_offsets))
-        return fail(AMC_E_INVALID, "amc_verify_pairs: NULL pair arrays");
+        return api_fail(AMC_E_INVALID, "amc_verify_pairs: NULL pair arrays");
     const uint64_t total = npairs ? match_offsets[npairs] : 0;
-    if (total > 0 && !matches) return fail(AMC_E_INVALID, "amc_verify_pairs: NULL matches");
+    if (total > 0 && !matches) return api_fail(AMC_E_INVALID, "amc_verify_pairs: NULL matches");
     for (size_t p = 0; p < npairs; ++p)
         if (match_offsets[p + 1] < match_offsets[p])
-            return fail(AMC_E_INVALID, "amc_verify_pairs: match_offsets not monotone at %zu", p);
+            return api_fail(AMC_E_INVALID, "amc_verify_pairs: match_offsets not monotone at %zu", p);
     amc_tvg_opts single = o;
     single.multiple_models = 0;
     VerifyPriv* priv = new (std::nothrow) VerifyPriv();
-    if (!priv) return fail(AMC_E_NOMEM, "amc_verify_pairs: out of host memory");
+    if (!priv) return api_fail(AMC_E_NOMEM, "amc_verify_pairs: out of host memory");
     priv->tvg.resize(npairs);
     priv->mask.assign(total, 0);
     std::vector<std::vector<uint32_t>> remaining(npairs);  // indices into the pair's original matches
@@ -2968,12 +2875,12 @@ int amc_verify_pairs(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, s
         // the resident match table (amc_upload_matches, or the last match call's rows) instead of rows over PCIe
         if (opts_in && opts_in->multiple_models) {
             std::memset(out, 0, sizeof *out);
-            return fail(AMC_E_INVALID, "amc_verify_pairs: multiple_models needs the match rows on the host (matches is NULL)");
+            return api_fail(AMC_E_INVALID, "amc_verify_pairs: multiple_models needs the match rows on the host (matches is NULL)");
         }
         if (c->resident_matches != total) {
             std::memset(out, 0, sizeof *out);
-            return fail(AMC_E_STATE, "amc_verify_pairs: matches is NULL and the resident match table holds %llu rows, not the "
-                        "%llu of match_offsets", (unsigned long long)c->resident_matches, (unsigned long long)total);
+            return api_fail(AMC_E_STATE, "amc_verify_pairs: matches is NULL and the resident match table holds %llu rows, not the "
+                            "%llu of match_offsets", (unsigned long long)c->resident_matches, (unsigned long long)total);
         }
         const uint64_t keep = c->resident_matches;  // (verify_impl drops a resident verification result, not the match table)
         const int rc = verify_impl(c, 0, slot1, slot2, npairs, match_offsets, nullptr, opts_in, seed, out, c->d_keep.p, match_offsets);
@@ -2988,7 +2895,7 @@ int amc_verify_pairs(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, s
 int amc_match_verify_pairs(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, size_t npairs,
                            const amc_match_opts* match_opts, const amc_tvg_opts* tvg_opts, uint32_t seed,
                            amc_match_result* match_out, amc_verify_result* verify_out) {
-    if (!c || !match_out || !verify_out) return fail(AMC_E_INVALID, "amc_match_verify_pairs: NULL ctx/out");
+    if (!c || !match_out || !verify_out) return api_fail(AMC_E_INVALID, "amc_match_verify_pairs: NULL ctx/out");
     std::memset(verify_out, 0, sizeof *verify_out);
     if (tvg_opts && tvg_opts->multiple_models) {
         // EstimateMultipleTwoViewGeometries shrinks the match lists on the host between rounds: no resident path
@@ -3016,7 +2923,7 @@ int amc_match_verify_pairs(amc_ctx* c, const uint32_t* slot1, const uint32_t* sl
     // leaving 24 .. 96 CUs to the verification of the batch before, 3 .. 8 batches, all within 1 % of the serial order).
     // AMC_PIPELINE_INTERLEAVE=1 keeps that variant reachable for the A/B.
     std::memset(match_out, 0, sizeof *match_out);
-    if (npairs > 0 && (!slot1 || !slot2)) return fail(AMC_E_INVALID, "amc_match_verify_pairs: NULL pair arrays");
+    if (npairs > 0 && (!slot1 || !slot2)) return api_fail(AMC_E_INVALID, "amc_match_verify_pairs: NULL pair arrays");
     c->vres = amc::VerifyResident{};
     const auto wall0 = std::chrono::steady_clock::now();
     VerifyRun run{};
@@ -3030,14 +2937,14 @@ int amc_match_verify_pairs(amc_ctx* c, const uint32_t* slot1, const uint32_t* sl
     run.beside_match = true;
     for (size_t p = 0; p < npairs; ++p)  // (the match call checks this too; the verification set-up reads the slots first)
         if (slot1[p] >= c->slots.size() || slot2[p] >= c->slots.size())
-            return fail(AMC_E_INVALID, "amc_match_verify_pairs: pair %zu references slot out of range", p);
+            return api_fail(AMC_E_INVALID, "amc_match_verify_pairs: pair %zu references slot out of range", p);
     int rc = run.begin(0);
     if (rc != AMC_OK) return rc;
     const double t_setup = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     run.st_e = c->vstream[0] ? c->vstream[0] : c->stream;
     run.st_fh = c->vstream[1] ? c->vstream[1] : run.st_e;
     VerifyPriv* priv = new (std::nothrow) VerifyPriv();
-    if (!priv) return fail(AMC_E_NOMEM, "amc_match_verify_pairs: out of host memory");
+    if (!priv) return api_fail(AMC_E_NOMEM, "amc_match_verify_pairs: out of host memory");
     struct Guard {  // every failure: nothing left in flight, both results zeroed
         amc_ctx* c;
         VerifyPriv* p;
@@ -3109,7 +3016,7 @@ int amc_match_verify_pairs(amc_ctx* c, const uint32_t* slot1, const uint32_t* sl
 }
 
 int amc_ctx_last_timeline(amc_ctx* c, double out_ms[8]) {
-    if (!c || !out_ms) return fail(AMC_E_INVALID, "amc_ctx_last_timeline: NULL argument");
+    if (!c || !out_ms) return api_fail(AMC_E_INVALID, "amc_ctx_last_timeline: NULL argument");
     std::memcpy(out_ms, c->timeline, sizeof c->timeline);
     return AMC_OK;
 }
@@ -3130,10 +3037,10 @@ struct RansacPriv {
 int amc_ransac_pairs(amc_ctx* c, int kind, const uint32_t* slot1, const uint32_t* slot2, size_t npairs,
                      const uint64_t* match_offsets, const uint32_t* matches,
                      const amc_ransac_opts* ropts, uint32_t seed, amc_ransac_result* out) {
-    if (!c || !out) return fail(AMC_E_INVALID, "amc_ransac_pairs: NULL ctx/out");
+    if (!c || !out) return api_fail(AMC_E_INVALID, "amc_ransac_pairs: NULL ctx/out");
     std::memset(out, 0, sizeof *out);
     if (kind != AMC_RANSAC_F && kind != AMC_RANSAC_H && kind != AMC_RANSAC_E)
-        return fail(AMC_E_INVALID, "amc_ransac_pairs: unknown estimator kind %d", kind);
+        return api_fail(AMC_E_INVALID, "amc_ransac_pairs: unknown estimator kind %d", kind);
     amc_tvg_opts o;
     amc_tvg_opts_default(&o);
     if (ropts) o.ransac = *ropts;
@@ -3145,7 +3052,7 @@ int amc_ransac_pairs(amc_ctx* c, int kind, const uint32_t* slot1, const uint32_t
     RansacPriv* priv = new (std::nothrow) RansacPriv();
     if (!priv) {
         amc_verify_result_free(&v);
-        return fail(AMC_E_NOMEM, "amc_ransac_pairs: out of host memory");
+        return api_fail(AMC_E_NOMEM, "amc_ransac_pairs: out of host memory");
     }
     const uint64_t total = npairs ? match_offsets[npairs] : 0;
     priv->reports.resize(npairs);
@@ -3177,9 +3084,9 @@ void amc_ransac_result_free(amc_ransac_result* r) {
 
 int amc_squared_sampson_error(amc_ctx* c, const double* points1, const double* points2, size_t n,
                               const double E[9], double* out) {
-    if (!c) return fail(AMC_E_INVALID, "amc_squared_sampson_error: ctx is NULL");
+    if (!c) return api_fail(AMC_E_INVALID, "amc_squared_sampson_error: ctx is NULL");
     if (n == 0) return AMC_OK;
-    if (!points1 || !points2 || !E || !out) return fail(AMC_E_INVALID, "amc_squared_sampson_error: NULL argument");
+    if (!points1 || !points2 || !E || !out) return api_fail(AMC_E_INVALID, "amc_squared_sampson_error: NULL argument");
     HIPCHK(hipSetDevice(c->device));
     DevBuf<double> buf;
     HIPCHK(buf.ensure(5 * n + 16));
@@ -3190,7 +3097,7 @@ int amc_squared_sampson_error(amc_ctx* c, const double* points1, const double* p
     hipStream_t st = c->stream;
     int rc = AMC_OK;
     auto chk = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == AMC_OK) rc = fail(AMC_E_HIP, "amc_squared_sampson_error: %s: %s", what, hipGetErrorString(e));
+        if (e != hipSuccess && rc == AMC_OK) rc = api_fail(AMC_E_HIP, "amc_squared_sampson_error: %s: %s", what, hipGetErrorString(e));
     };
     chk(hipMemcpyAsync(d1, points1, 2 * n * sizeof(double), hipMemcpyHostToDevice, st), "copy points1");
     chk(hipMemcpyAsync(d2, points2, 2 * n * sizeof(double), hipMemcpyHostToDevice, st), "copy points2");
@@ -3198,17 +3105,16 @@ int amc_squared_sampson_error(amc_ctx* c, const double* points1, const double* p
     if (rc == AMC_OK) chk(launch_sampson(d1, d2, n, dE, dout, st), "launch");
     if (rc == AMC_OK) chk(hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, st), "copy out");
     chk(hipStreamSynchronize(st), "sync");
-    buf.release();
     return rc;
 }
 
 int amc_homography_decomposition(amc_ctx* c, const double H[9], const double K1[9], const double K2[9],
                                  const double* points1, const double* points2, size_t n, double R[9], double t[3],
                                  double normal[3], double* points3D, uint64_t* num_points3D) {
-    if (!c) return fail(AMC_E_INVALID, "amc_homography_decomposition: ctx is NULL");
+    if (!c) return api_fail(AMC_E_INVALID, "amc_homography_decomposition: ctx is NULL");
     if (!H || !K1 || !K2 || !R || !t || !normal || !num_points3D || (n > 0 && (!points1 || !points2 || !points3D)))
-        return fail(AMC_E_INVALID, "amc_homography_decomposition: NULL argument");
-    if (n > 0xFFFFFFFFull / 4) return fail(AMC_E_INVALID, "amc_homography_decomposition: too many points");
+        return api_fail(AMC_E_INVALID, "amc_homography_decomposition: NULL argument");
+    if (n > 0xFFFFFFFFull / 4) return api_fail(AMC_E_INVALID, "amc_homography_decomposition: too many points");
     HIPCHK(hipSetDevice(c->device));
     DevBuf<double> buf;
     HIPCHK(buf.ensure(7 * n + 27 + 16 + 8));
@@ -3220,7 +3126,7 @@ int amc_homography_decomposition(amc_ctx* c, const double H[9], const double K1[
     hipStream_t st = c->stream;
     int rc = AMC_OK;
     auto chk = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == AMC_OK) rc = fail(AMC_E_HIP, "amc_homography_decomposition: %s: %s", what, hipGetErrorString(e));
+        if (e != hipSuccess && rc == AMC_OK) rc = api_fail(AMC_E_HIP, "amc_homography_decomposition: %s: %s", what, hipGetErrorString(e));
     };
     double in[27], o[16];
     std::memcpy(in, H, 9 * sizeof(double));
@@ -3245,7 +3151,6 @@ int amc_homography_decomposition(amc_ctx* c, const double H[9], const double K1[
             chk(hipStreamSynchronize(st), "sync");
         }
     }
-    buf.release();
     return rc;
 }
 

@@ -134,46 +134,6 @@ const Rccl* rccl(std::string* why) {
     return &r;
 }
 
-// grow-only device / pinned buffers of a communicator (freed with it)
-struct DBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(bytes, 256);
-        const hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-struct HBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(bytes, 256);
-        const hipError_t e = hipHostMalloc(&p, want, 0);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 // One wave per pair: the pair's rows from the rank-major receive buffer to their place in the global CSR.
 __global__ __launch_bounds__(256) void gather_reorder_kernel(const uint64_t* __restrict__ src_off,
                                                              const uint64_t* __restrict__ dst_off,
@@ -270,9 +230,10 @@ struct amc_comm {
     ncclComm_t comm = nullptr;
     int world = 1, rank = 0, device = 0;
     bool broken = false;  // a transfer failed half way: the communicator was aborted, every later call returns AMC_E_STATE
-    amc::DBuf d_sizes, d_meta_send, d_meta_all, d_rows_send, d_rows_all, d_global, d_src_off, d_dst_off, d_cnt;
-    amc::DBuf d_rec_send, d_rec_all, d_rec_global, d_inl_cnt, d_inl_off, d_inl_rows;
-    amc::HBuf h_sizes, h_meta, h_rows, h_plan, h_rec, h_inl_cnt;
+    // grow-only device / pinned buffers (freed with the communicator)
+    amc::DevBuf<void> d_sizes, d_meta_send, d_meta_all, d_rows_send, d_rows_all, d_global, d_src_off, d_dst_off, d_cnt;
+    amc::DevBuf<void> d_rec_send, d_rec_all, d_rec_global, d_inl_cnt, d_inl_off, d_inl_rows;
+    amc::PinBuf<void> h_sizes, h_meta, h_rows, h_plan, h_rec, h_inl_cnt;
 };
 
 namespace amc {
@@ -396,6 +357,14 @@ struct Xchg {
         return AMC_OK;
     }
 };
+
+// a HIP call of an exchange whose failure is this rank's own (no collective is left to strand the peers): the call
+// fails through the exchange `x` in scope (Xchg::fail_hip, which drains the stream first)
+#define CHK_HIP(expr)                                                     \
+    do {                                                                  \
+        const hipError_t e_ = (expr);                                     \
+        if (e_ != hipSuccess) return x.fail_hip(#expr, e_);               \
+    } while (0)
 
 // The core of amc_allgather_match_tables / amc_allgather_inlier_tables: rows_dev = this rank's rows in device memory
 // (nullptr with rows_host given: uploaded first).  `bad` = what is wrong with this rank's arguments (the rank still
@@ -571,11 +540,6 @@ int gather_tables(const char* who, amc_ctx* ctx, amc_comm* c, const uint64_t* pa
         h_cnt[k] = (uint32_t)cnt;
         run += cnt;
     }
-#define CHK_HIP(expr)                                                     \
-    do {                                                                  \
-        const hipError_t e_ = (expr);                                     \
-        if (e_ != hipSuccess) return x.fail_hip(#expr, e_);               \
-    } while (0)
     if (total_pairs) {
         CHK_HIP(memcpy_async(c->d_src_off.p, h_src, total_pairs * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         CHK_HIP(memcpy_async(c->d_dst_off.p, h_dst, total_pairs * sizeof(uint64_t), hipMemcpyHostToDevice, st));
@@ -599,7 +563,6 @@ int gather_tables(const char* who, amc_ctx* ctx, amc_comm* c, const uint64_t* pa
         CHK_HIP(hipStreamSynchronize(st));
         out->matches = static_cast<const uint32_t*>(c->h_rows.p);
     }
-#undef CHK_HIP
     out->download_ms = ms_since(t0);
     out->total_ms = ms_since(t_all);
     out->npairs = (size_t)total_pairs;
@@ -736,11 +699,6 @@ int gather_records(const char* who, amc_ctx* ctx, amc_comm* c, const uint64_t* p
                             (unsigned long long)total_pairs);
         seen[hm[k]] = 1;
     }
-#define CHK_HIP(expr)                                                     \
-    do {                                                                  \
-        const hipError_t e_ = (expr);                                     \
-        if (e_ != hipSuccess) return x.fail_hip(#expr, e_);               \
-    } while (0)
     if (total_pairs) {
         hipLaunchKernelGGL(record_reorder_kernel, dim3((unsigned)((total_pairs + 3) / 4)), dim3(256), 0, st,
                            static_cast<const uint64_t*>(c->d_meta_all.p), (size_t)total_pairs, (uint32_t)words,
@@ -750,7 +708,6 @@ int gather_records(const char* who, amc_ctx* ctx, amc_comm* c, const uint64_t* p
             CHK_HIP(hipMemcpyAsync(c->h_rec.p, c->d_rec_global.p, total_pairs * record_bytes, hipMemcpyDeviceToHost, st));
         CHK_HIP(hipStreamSynchronize(st));
     }
-#undef CHK_HIP
     out->npairs = (size_t)total_pairs;
     out->record_bytes = record_bytes;
     out->records = (download && total_pairs) ? c->h_rec.p : nullptr;
@@ -848,12 +805,7 @@ void amc_comm_destroy(amc_comm* c) {
     } catch (...) {
     }
     if (R && c->comm) (void)R->CommDestroy(c->comm);
-    for (DBuf* b : {&c->d_sizes, &c->d_meta_send, &c->d_meta_all, &c->d_rows_send, &c->d_rows_all, &c->d_global,
-                    &c->d_src_off, &c->d_dst_off, &c->d_cnt, &c->d_rec_send, &c->d_rec_all, &c->d_rec_global,
-                    &c->d_inl_cnt, &c->d_inl_off, &c->d_inl_rows})
-        b->release();
-    for (HBuf* b : {&c->h_sizes, &c->h_meta, &c->h_rows, &c->h_plan, &c->h_rec, &c->h_inl_cnt}) b->release();
-    delete c;
+    delete c;  // (and its buffers)
 }
 
 void amc_gathered_tables_free(amc_gathered_tables* t) {

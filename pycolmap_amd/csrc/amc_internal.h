@@ -5,6 +5,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <type_traits>
+#include <vector>
+
 #include "../../include/amc.h"
 #include "guided_region.h"
 
@@ -120,9 +124,189 @@ struct FinalizeParams {
     int reserved;
 };
 
-// ----- for the translation units beside amc_api.hip that implement C-ABI entry points (amc_comm.hip) --------------
+// ----- host side of the C-ABI entry points (amc_api.hip and the translation units beside it) ------------------------
 // api_fail: sets the calling thread's amc_last_error() message and returns `code`.
 int api_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// HIPCHK(expr): the HIP call `expr` must succeed, else the enclosing function returns api_fail(AMC_E_HIP, ...) with
+// "file:line: expr -> HIP's error string".  A function that declares its own `const char* hipchk_who` (the entry
+// point's name) gets that name in front: "who: file:line: ...".
+constexpr const char* hipchk_who = nullptr;
+#define HIPCHK(expr)                                                                                                   \
+    do {                                                                                                               \
+        const hipError_t e_ = (expr);                                                                                  \
+        if (e_ != hipSuccess)                                                                                          \
+            return ::amc::api_fail(AMC_E_HIP, "%s%s%s:%d: %s -> %s", hipchk_who ? hipchk_who : "",                    \
+                                   hipchk_who ? ": " : "", __FILE__, __LINE__, #expr, hipGetErrorString(e_));        \
+    } while (0)
+
+// Grow-only device (DevBuf) or pinned host (PinBuf) buffer of T.  ensure(n) makes room for n elements, at least 16,
+// without keeping the old contents; release() frees it, and so does the destructor.  Move-only: a move empties the
+// source.  T = void: bytes behind a void* p, at least 256.  Pinned memory has the default flags, mapped and coherent:
+// kernels write it through the same pointer (the scan's copy parts, launch_host_copy) and the host sees the data once
+// the kernel's completion event has been waited for.
+template <typename T, bool kPinned>
+struct GrowBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+
+    GrowBuf() = default;
+    GrowBuf(GrowBuf&& o) noexcept : p(o.p), cap(o.cap) {
+        o.p = nullptr;
+        o.cap = 0;
+    }
+    GrowBuf& operator=(GrowBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p;
+            cap = o.cap;
+            o.p = nullptr;
+            o.cap = 0;
+        }
+        return *this;
+    }
+    ~GrowBuf() { release(); }
+
+    hipError_t ensure(size_t n) {
+        if (n <= cap) return hipSuccess;
+        release();
+        const size_t want = std::max(n, std::is_void<T>::value ? (size_t)256 : (size_t)16);
+        const size_t bytes = want * sizeof(typename std::conditional<std::is_void<T>::value, char, T>::type);
+        void* q = nullptr;
+        const hipError_t e = kPinned ? hipHostMalloc(&q, bytes, 0) : hipMalloc(&q, bytes);
+        if (e == hipSuccess) {
+            p = static_cast<T*>(q);
+            cap = want;
+        }
+        return e;
+    }
+    void release() {
+        if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+};
+template <typename T>
+using DevBuf = GrowBuf<T, false>;
+template <typename T>
+using PinBuf = GrowBuf<T, true>;
+
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// One device buffer cut into parts at 256-byte boundaries.  Name every part once, part(&ptr, n) for n elements of
+// *ptr's type; then carve(buf) has buf ensure() the parts' total size and points every ptr at its part.
+class DevParts {
+  public:
+    template <typename T>
+    DevParts& part(T** ptr, size_t n) {
+        parts_.push_back({ptr, align256(n * sizeof(T)), [](void* q, char* at) { *static_cast<T**>(q) = reinterpret_cast<T*>(at); }});
+        return *this;
+    }
+    hipError_t carve(DevBuf<void>& buf) const {
+        size_t total = 0;
+        for (const Part& q : parts_) total += q.bytes;
+        const hipError_t e = buf.ensure(total);
+        if (e != hipSuccess) return e;
+        char* at = static_cast<char*>(buf.p);
+        for (const Part& q : parts_) {
+            q.set(q.ptr, at);
+            at += q.bytes;
+        }
+        return hipSuccess;
+    }
+
+  private:
+    struct Part {
+        void* ptr;
+        size_t bytes;
+        void (*set)(void* ptr, char* at);
+    };
+    std::vector<Part> parts_;
+};
+
+// hipEventCreateWithFlags for the n events ev[0 .. n), flags[i] each (nullptr: default events), all or none: when one
+// cannot be made, those made are destroyed again, all n are left nullptr and the error is returned.
+inline hipError_t create_events(hipEvent_t* ev, int n, const unsigned* flags = nullptr) {
+    for (int i = 0; i < n; ++i) {
+        const hipError_t e = hipEventCreateWithFlags(&ev[i], flags ? flags[i] : hipEventDefault);
+        if (e != hipSuccess) {
+            for (int j = 0; j < i; ++j) (void)hipEventDestroy(ev[j]);
+            std::fill(ev, ev + n, nullptr);
+            return e;
+        }
+    }
+    return hipSuccess;
+}
+
+// Event timing on one stream.  start() .. stop() times a stretch of it, stop() waiting for the stretch's end; between
+// them, span_begin() / span_end() around launches mark spans whose times spans() adds up.  The events are destroyed
+// with the timer.  Every call returns the error of the first HIP call that fails.
+class StreamTimer {
+  public:
+    explicit StreamTimer(hipStream_t s) : s_(s), made_(create_events(ab_, 2)) {}
+    StreamTimer(const StreamTimer&) = delete;
+    StreamTimer& operator=(const StreamTimer&) = delete;
+    ~StreamTimer() {
+        for (hipEvent_t e : ab_)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : spans_) (void)hipEventDestroy(e);
+    }
+
+    hipError_t start() { return made_ != hipSuccess ? made_ : hipEventRecord(ab_[0], s_); }
+    // adds the milliseconds since start() to ms
+    hipError_t stop(double& ms) {
+        hipError_t e = hipEventRecord(ab_[1], s_);
+        if (e == hipSuccess) e = hipEventSynchronize(ab_[1]);
+        return e == hipSuccess ? add_elapsed(ab_[0], ab_[1], ms) : e;
+    }
+    hipError_t span_begin() {
+        hipEvent_t two[2];
+        if (const hipError_t e = create_events(two, 2)) return e;
+        spans_.insert(spans_.end(), two, two + 2);
+        return hipEventRecord(two[0], s_);
+    }
+    hipError_t span_end() { return hipEventRecord(spans_.back(), s_); }
+    // adds the spans' milliseconds to ms (after stop())
+    hipError_t spans(double& ms) const {
+        for (size_t i = 0; i + 1 < spans_.size(); i += 2)
+            if (const hipError_t e = add_elapsed(spans_[i], spans_[i + 1], ms)) return e;
+        return hipSuccess;
+    }
+
+  private:
+    static hipError_t add_elapsed(hipEvent_t a, hipEvent_t b, double& ms) {
+        float f = 0.f;
+        const hipError_t e = hipEventElapsedTime(&f, a, b);
+        if (e == hipSuccess) ms += f;
+        return e;
+    }
+    hipStream_t s_;
+    hipEvent_t ab_[2] = {nullptr, nullptr};
+    hipError_t made_;
+    std::vector<hipEvent_t> spans_;  // begin / end of each span
+};
+
+// Contiguous batches of the CSR `offsets` (n items, item i holds elements offsets[i] .. offsets[i + 1]): at most
+// max_items items and at most max_elems elements times `factor` per batch, greedily; a larger item is a batch of its own.
+struct Batches {
+    std::vector<size_t> start{0};  // first item of each batch, then n
+    uint64_t most_items = 0, most_elems = 0;  // the largest batch's items, elements (without the factor)
+    size_t count() const { return start.size() - 1; }
+};
+inline Batches split_batches(const uint64_t* offsets, size_t n, uint64_t max_items, uint64_t max_elems,
+                             uint64_t factor = 1) {
+    Batches b;
+    for (size_t i = 0; i < n;) {
+        size_t j = i + 1;
+        while (j < n && j - i < max_items && (offsets[j + 1] - offsets[i]) * factor <= max_elems) ++j;
+        b.most_items = std::max<uint64_t>(b.most_items, j - i);
+        b.most_elems = std::max<uint64_t>(b.most_elems, offsets[j] - offsets[i]);
+        b.start.push_back(j);
+        i = j;
+    }
+    return b;
+}
+
 struct CtxView {
     int device;
     hipStream_t stream;        // the stream the ctx launches on (its own, or the host's: amc_ctx_set_stream)

@@ -468,14 +468,6 @@ __global__ void __launch_bounds__(kWave) k_descr(const Kp* __restrict__ kps, con
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-#define SIFT_HIPCHK(expr)                                                                                  \
-    do {                                                                                                   \
-        hipError_t e_ = (expr);                                                                            \
-        if (e_ != hipSuccess)                                                                              \
-            return api_fail(AMC_E_HIP, "amc_sift_extract: %s:%d: %s -> %s", __FILE__, __LINE__, #expr,     \
-                            hipGetErrorString(e_));                                                        \
-    } while (0)
-
 std::vector<float> gauss_taps(double sigma) {  // ceil(4 sigma) taps each side, normalised in double
     const int W = (int)std::ceil(4.0 * sigma);
     std::vector<double> g(2 * W + 1);
@@ -504,47 +496,6 @@ std::vector<OctaveDims> octaves_of(int w, int h, const amc_sift_opts& op) {
     }
     return v;
 }
-
-// Device memory of one call, grow-only: the largest image's levels, DoGs and scratch
-struct Workspace {
-    void* p = nullptr;
-    size_t cap = 0;
-    ~Workspace() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-};
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Timer {
-    hipStream_t s;
-    hipEvent_t a = nullptr, b = nullptr;
-    explicit Timer(hipStream_t st) : s(st) {
-        (void)hipEventCreate(&a);
-        (void)hipEventCreate(&b);
-    }
-    ~Timer() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-    void start() { (void)hipEventRecord(a, s); }
-    double stop() {  // waits for the stream
-        float ms = 0.f;
-        (void)hipEventRecord(b, s);
-        (void)hipEventSynchronize(b);
-        (void)hipEventElapsedTime(&ms, a, b);
-        return ms;
-    }
-};
 
 struct HostResult {
     std::vector<float> kp;
@@ -579,6 +530,7 @@ void amc_sift_result_free(amc_sift_result* r) {
 
 int amc_sift_extract(amc_ctx* ctx, const amc_sift_image* images, size_t nimages, const amc_sift_opts* opts,
                      amc_sift_result* result) {
+    const char* const hipchk_who = "amc_sift_extract";
     if (!ctx || !opts || !result || (nimages && !images)) return api_fail(AMC_E_INVALID, "amc_sift_extract: NULL argument");
     std::memset(result, 0, sizeof *result);
     const amc_sift_opts op = *opts;
@@ -598,7 +550,7 @@ int amc_sift_extract(amc_ctx* ctx, const amc_sift_image* images, size_t nimages,
                             im.width, im.height, op.max_image_size);
     }
     const CtxView cv = ctx_view(ctx);
-    SIFT_HIPCHK(hipSetDevice(cv.device));
+    HIPCHK(hipSetDevice(cv.device));
     hipStream_t st = cv.stream;
     const int S = op.octave_resolution, nlev = S + 3;
     const double sigma0 = 1.6 * std::pow(2.0, 1.0 / S), sigman = 0.5;
@@ -633,32 +585,27 @@ int amc_sift_extract(amc_ctx* ctx, const amc_sift_image* images, size_t nimages,
         need = std::max(need, b);
     }
     const size_t const_bytes = align256(h_consts.size() * sizeof(float));
-    Workspace ws, kpbuf, outbuf, cntbuf;
-    SIFT_HIPCHK(ws.ensure(const_bytes + need));
+    DevBuf<void> ws, kpbuf, outbuf, cntbuf;  // device memory of the call, grow-only
+    HIPCHK(ws.ensure(const_bytes + need));
     char* wsb = static_cast<char*>(ws.p);
     float* d_consts = reinterpret_cast<float*>(wsb);
-    SIFT_HIPCHK(hipMemcpyAsync(d_consts, h_consts.data(), h_consts.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_consts, h_consts.data(), h_consts.size() * sizeof(float), hipMemcpyHostToDevice, st));
     const float* d_tab = d_consts;
 
     // the whole batch's pixels in one pinned staging buffer (packed rows), so that every upload is a DMA from pinned
     // memory; freed when the call returns
     std::vector<size_t> stage_off(nimages + 1, 0);
     for (size_t i = 0; i < nimages; ++i) stage_off[i + 1] = stage_off[i] + (size_t)images[i].width * images[i].height;
-    struct Pinned {
-        void* p = nullptr;
-        ~Pinned() {
-            if (p) (void)hipHostFree(p);
-        }
-    } pinned;
-    if (stage_off[nimages]) SIFT_HIPCHK(hipHostMalloc(&pinned.p, stage_off[nimages], hipHostMallocDefault));
+    PinBuf<uint8_t> pinned;
+    if (stage_off[nimages]) HIPCHK(pinned.ensure(stage_off[nimages]));
     for (size_t i = 0; i < nimages; ++i) {
-        uint8_t* dst = static_cast<uint8_t*>(pinned.p) + stage_off[i];
+        uint8_t* dst = pinned.p + stage_off[i];
         for (int y = 0; y < images[i].height; ++y)
             std::memcpy(dst + (size_t)y * images[i].width, images[i].pixels + (size_t)y * images[i].pitch, images[i].width);
     }
 
-    Timer total(st), stage(st);
-    total.start();
+    StreamTimer total(st), stage(st);
+    HIPCHK(total.start());
     double stage_ms[4] = {0, 0, 0, 0};
     std::vector<HostResult> res(nimages);
 
@@ -680,8 +627,8 @@ int amc_sift_extract(amc_ctx* ctx, const amc_sift_image* images, size_t nimages,
         }
         float* d_dog = reinterpret_cast<float*>(cur);
         if (oct.empty()) continue;  // too small for one octave: no features
-        SIFT_HIPCHK(hipMemcpyAsync(d_u8, static_cast<uint8_t*>(pinned.p) + stage_off[ii], stage_off[ii + 1] - stage_off[ii],
-                                   hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_u8, pinned.p + stage_off[ii], stage_off[ii + 1] - stage_off[ii], hipMemcpyHostToDevice,
+                              st));
 
         struct OctKps {
             int n = 0;
@@ -696,7 +643,7 @@ int amc_sift_extract(amc_ctx* ctx, const amc_sift_image* images, size_t nimages,
             const int w = oct[k].w, h = oct[k].h;
             const size_t plane = (size_t)w * h;
             float* G = d_lev[k];
-            stage.start();
+            HIPCHK(stage.start());
             const dim3 rows((w + 255) / 256, h);
             if (k == 0) {
                 k_base<<<rows, 256, 0, st>>>(d_u8, im.width, im.height, im.width, oct[0].o, taps[0].empty() ? G : d_base,
@@ -721,20 +668,20 @@ int amc_sift_extract(amc_ctx* ctx, const amc_sift_image* images, size_t nimages,
                                                                        d_dog + (L - 1) * plane, w, h,
                                                                        d_consts + tap_off[L], W);
             }
-            SIFT_HIPCHK(hipGetLastError());
-            stage_ms[0] += stage.stop();
+            HIPCHK(hipGetLastError());
+            HIPCHK(stage.stop(stage_ms[0]));
 
-            stage.start();
+            HIPCHK(stage.start());
             const DetectParams P{w, h, S, oct[k].o, (float)op.peak_threshold, (float)op.edge_threshold, (float)sigma0};
             const int nrows = S * (h - 2);
-            SIFT_HIPCHK(cntbuf.ensure(2 * (size_t)nrows * sizeof(int)));
+            HIPCHK(cntbuf.ensure(2 * (size_t)nrows * sizeof(int)));
             int* d_cnt = static_cast<int*>(cntbuf.p);
             int* d_off = d_cnt + nrows;
             k_detect<<<dim3(h - 2, S), kDetectThreads, 0, st>>>(d_dog, P, d_cnt, nullptr, nullptr);
-            SIFT_HIPCHK(hipGetLastError());
+            HIPCHK(hipGetLastError());
             row_cnt[k].resize(nrows);
-            SIFT_HIPCHK(hipMemcpyAsync(row_cnt[k].data(), d_cnt, nrows * sizeof(int), hipMemcpyDeviceToHost, st));
-            SIFT_HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipMemcpyAsync(row_cnt[k].data(), d_cnt, nrows * sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
             std::vector<int> off(nrows);
             int n = 0;
             for (int r = 0; r < nrows; ++r) {
@@ -743,37 +690,36 @@ int amc_sift_extract(amc_ctx* ctx, const amc_sift_image* images, size_t nimages,
             }
             ok[k].n = n;
             kp_base[k + 1] = kp_base[k] + n;
-            stage_ms[1] += stage.stop();
+            HIPCHK(stage.stop(stage_ms[1]));
             if (n == 0) continue;
             // keypoints of all octaves so far stay in kpbuf (Kp), followed by a scratch of 4 angles + 1 count each
             const size_t kp_bytes = align256(kp_base[k + 1] * sizeof(Kp));
             if (kpbuf.cap < kp_bytes + align256((size_t)n * 5 * sizeof(float))) {
-                Workspace grown;
-                SIFT_HIPCHK(grown.ensure(2 * (kp_bytes + align256((size_t)n * 5 * sizeof(float)))));
+                DevBuf<void> grown;
+                HIPCHK(grown.ensure(2 * (kp_bytes + align256((size_t)n * 5 * sizeof(float)))));
                 if (kp_base[k])
-                    SIFT_HIPCHK(hipMemcpyAsync(grown.p, kpbuf.p, kp_base[k] * sizeof(Kp), hipMemcpyDeviceToDevice, st));
-                SIFT_HIPCHK(hipStreamSynchronize(st));
-                std::swap(grown.p, kpbuf.p);
-                std::swap(grown.cap, kpbuf.cap);
+                    HIPCHK(hipMemcpyAsync(grown.p, kpbuf.p, kp_base[k] * sizeof(Kp), hipMemcpyDeviceToDevice, st));
+                HIPCHK(hipStreamSynchronize(st));
+                kpbuf = std::move(grown);
             }
             Kp* d_kps = static_cast<Kp*>(kpbuf.p) + kp_base[k];
-            stage.start();
-            SIFT_HIPCHK(hipMemcpyAsync(d_off, off.data(), nrows * sizeof(int), hipMemcpyHostToDevice, st));
+            HIPCHK(stage.start());
+            HIPCHK(hipMemcpyAsync(d_off, off.data(), nrows * sizeof(int), hipMemcpyHostToDevice, st));
             k_detect<<<dim3(h - 2, S), kDetectThreads, 0, st>>>(d_dog, P, d_cnt, d_off, d_kps);
-            SIFT_HIPCHK(hipGetLastError());
-            stage_ms[1] += stage.stop();
+            HIPCHK(hipGetLastError());
+            HIPCHK(stage.stop(stage_ms[1]));
             ok[k].nang.assign(n, 1);
             ok[k].angles.assign((size_t)n * 4, 0.0f);
             if (!op.upright) {
-                stage.start();
+                HIPCHK(stage.start());
                 float* d_ang = reinterpret_cast<float*>(static_cast<char*>(kpbuf.p) + kp_bytes);
                 int* d_nang = reinterpret_cast<int*>(d_ang + (size_t)n * 4);
                 k_orient<<<n, kWave, 0, st>>>(d_kps, G, w, h, d_tab, op.max_num_orientations, d_ang, d_nang);
-                SIFT_HIPCHK(hipGetLastError());
-                SIFT_HIPCHK(hipMemcpyAsync(ok[k].angles.data(), d_ang, (size_t)n * 4 * sizeof(float),
-                                           hipMemcpyDeviceToHost, st));
-                SIFT_HIPCHK(hipMemcpyAsync(ok[k].nang.data(), d_nang, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
-                stage_ms[2] += stage.stop();
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpyAsync(ok[k].angles.data(), d_ang, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost,
+                                      st));
+                HIPCHK(hipMemcpyAsync(ok[k].nang.data(), d_nang, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+                HIPCHK(stage.stop(stage_ms[2]));
             }
         }
         // the cut: whole octaves from the coarsest down; the octave that crosses the limit keeps its first features
@@ -804,16 +750,13 @@ int amc_sift_extract(amc_ctx* ctx, const amc_sift_image* images, size_t nimages,
         hr.kp.resize(nf * 4);
         hr.desc.resize(nf * 128);
         if (nf == 0) continue;
-        const size_t ob = align256(nf * sizeof(uint32_t)) + align256(nf * sizeof(float)) +
-                          align256(nf * 4 * sizeof(float)) + align256(nf * 128);
-        SIFT_HIPCHK(outbuf.ensure(ob));
-        uint32_t* d_fkp = static_cast<uint32_t*>(outbuf.p);
-        float* d_fth = reinterpret_cast<float*>(reinterpret_cast<char*>(d_fkp) + align256(nf * sizeof(uint32_t)));
-        float* d_kpo = reinterpret_cast<float*>(reinterpret_cast<char*>(d_fth) + align256(nf * sizeof(float)));
-        uint8_t* d_desc = reinterpret_cast<uint8_t*>(reinterpret_cast<char*>(d_kpo) + align256(nf * 4 * sizeof(float)));
-        stage.start();
-        SIFT_HIPCHK(hipMemcpyAsync(d_fkp, fkp.data(), nf * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        SIFT_HIPCHK(hipMemcpyAsync(d_fth, fth.data(), nf * sizeof(float), hipMemcpyHostToDevice, st));
+        uint32_t* d_fkp;
+        float *d_fth, *d_kpo;
+        uint8_t* d_desc;
+        HIPCHK(DevParts().part(&d_fkp, nf).part(&d_fth, nf).part(&d_kpo, 4 * nf).part(&d_desc, 128 * nf).carve(outbuf));
+        HIPCHK(stage.start());
+        HIPCHK(hipMemcpyAsync(d_fkp, fkp.data(), nf * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_fth, fth.data(), nf * sizeof(float), hipMemcpyHostToDevice, st));
         for (size_t k = 0; k < oct.size(); ++k) {
             const size_t m = fbase[k + 1] - fbase[k];
             if (!m) continue;
@@ -823,12 +766,12 @@ int amc_sift_extract(amc_ctx* ctx, const amc_sift_image* images, size_t nimages,
                                                    d_fth + fbase[k], d_lev[k], oct[k].w, oct[k].h, d_tab,
                                                    op.normalization, p2, d_kpo + fbase[k] * 4, d_desc + fbase[k] * 128);
         }
-        SIFT_HIPCHK(hipGetLastError());
-        SIFT_HIPCHK(hipMemcpyAsync(hr.kp.data(), d_kpo, nf * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
-        SIFT_HIPCHK(hipMemcpyAsync(hr.desc.data(), d_desc, nf * 128, hipMemcpyDeviceToHost, st));
-        stage_ms[3] += stage.stop();
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(hr.kp.data(), d_kpo, nf * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hr.desc.data(), d_desc, nf * 128, hipMemcpyDeviceToHost, st));
+        HIPCHK(stage.stop(stage_ms[3]));
     }
-    result->device_ms = total.stop();
+    HIPCHK(total.stop(result->device_ms));  // (result was zeroed on entry)
     for (int s = 0; s < 4; ++s) result->stage_ms[s] = stage_ms[s];
 
     size_t nf = 0;

@@ -317,44 +317,7 @@ __global__ __launch_bounds__(kBlock) void tri_kernel(TriParams p) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-#define TRI_HIPCHK(expr)                                                                                     \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess)                                                                                \
-            return api_fail(AMC_E_HIP, "amc_triangulate_tracks: %s:%d: %s -> %s", __FILE__, __LINE__, #expr,  \
-                            hipGetErrorString(e_));                                                          \
-    } while (0)
-
-struct DevMem {
-    void* p = nullptr;
-    ~DevMem() {
-        if (p) (void)hipFree(p);
-    }
-};
-
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    std::vector<hipEvent_t> k;  // around each batch's kernel
-    ~Events() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-        for (hipEvent_t e : k)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// colmap/optim/ransac.h ComputeNumTrials with kMinNumSamples = 2 (host libm, as oracle/tvg_oracle.cc has it)
-uint64_t compute_num_trials(uint64_t num_inliers, uint64_t num_samples, double confidence, double multiplier) {
-    const double inlier_ratio = num_inliers / static_cast<double>(num_samples);
-    const double nom = 1 - confidence;
-    if (nom <= 0) return ~(uint64_t)0;
-    const double denom = 1 - std::pow(inlier_ratio, 2);
-    if (denom <= 0) return 1;
-    if (denom == 1.0) return ~(uint64_t)0;
-    return static_cast<uint64_t>(std::ceil(std::log(nom) / std::log(denom) * multiplier));
-}
+constexpr int kMinSamples = 2;  // two views: ComputeNumTrials' kMinNumSamples (tvg_math.h)
 
 }  // namespace
 
@@ -384,6 +347,7 @@ void amc_tri_result_free(amc_tri_result* r) {
 static int triangulate_impl(amc_ctx* ctx, const double* poses, size_t nposes, const uint64_t* track_offsets,
                             size_t ntracks, const uint32_t* obs_pose, const double* obs_xy, const amc_tri_opts* opts,
                             amc_tri_result* result) {
+    const char* const hipchk_who = "amc_triangulate_tracks";
     if (!ctx || !opts || !result || !track_offsets || (nposes && !poses))
         return api_fail(AMC_E_INVALID, "amc_triangulate_tracks: NULL argument");
     std::memset(result, 0, sizeof *result);
@@ -428,11 +392,8 @@ static int triangulate_impl(amc_ctx* ctx, const double* poses, size_t nposes, co
         for (int c = 0; c < 3; ++c) q.C[c] = -(q.P[c] * q.P[3] + q.P[4 + c] * q.P[7] + q.P[8 + c] * q.P[11]);
         q.pad = 0.0;
     }
-    // the RANSAC constructor's clamp of max_num_trials by min_inlier_ratio
-    const uint64_t kNumSamples = 100000;
-    const uint64_t max_trials = std::min<uint64_t>(
-        (uint64_t)op.max_num_trials, compute_num_trials((uint64_t)(op.min_inlier_ratio * kNumSamples), kNumSamples,
-                                                        op.confidence, op.dyn_num_trials_multiplier));
+    const uint64_t max_trials = tvg::ransac_max_trials(op.max_num_trials, op.min_inlier_ratio, op.confidence,
+                                                       op.dyn_num_trials_multiplier, kMinSamples);
     const uint64_t min_trials = (uint64_t)op.min_num_trials;
 
     // dyn_max_num_trials rows for the track lengths whose RANSAC can stop early (more trials than min_num_trials)
@@ -446,64 +407,46 @@ static int triangulate_impl(amc_ctx* ctx, const double* poses, size_t nposes, co
         if (std::min(max_trials, combos) <= min_trials) continue;
         dyn_off[n] = dyn_tab.size();
         for (uint64_t c = 0; c <= n; ++c)
-            dyn_tab.push_back(compute_num_trials(c, n, op.confidence, op.dyn_num_trials_multiplier));
+            dyn_tab.push_back(tvg::compute_num_trials(c, n, op.confidence, op.dyn_num_trials_multiplier, kMinSamples));
     }
     if (dyn_tab.empty()) dyn_tab.push_back(0);
 
     // batches: contiguous track ranges of at most kMaxBatchTracks tracks and kMaxBatchObs observations (a longer track
     // is a batch of its own)
-    std::vector<size_t> bstart{0};
-    uint64_t max_bt = 0, max_bo = 0;
-    for (size_t i = 0; i < ntracks;) {
-        size_t j = i + 1;
-        while (j < ntracks && j - i < kMaxBatchTracks && track_offsets[j + 1] - track_offsets[i] <= kMaxBatchObs) ++j;
-        max_bt = std::max<uint64_t>(max_bt, j - i);
-        max_bo = std::max<uint64_t>(max_bo, track_offsets[j] - track_offsets[i]);
-        bstart.push_back(j);
-        i = j;
-    }
-    const size_t nbatch = bstart.size() - 1;
-    max_bo = std::max<uint64_t>(max_bo, 1);
+    const Batches batches = split_batches(track_offsets, ntracks, kMaxBatchTracks, kMaxBatchObs);
+    const std::vector<size_t>& bstart = batches.start;
+    const size_t nbatch = batches.count();
+    const uint64_t max_bt = batches.most_items, max_bo = std::max<uint64_t>(batches.most_elems, 1);
 
-    // one device allocation: constants, then the batch buffers
-    const size_t sz_pose = align256(tab.size() * sizeof(TriPose)), sz_doff = align256(dyn_off.size() * 8),
-                 sz_dtab = align256(dyn_tab.size() * 8), sz_off = align256((max_bt + 1) * 8),
-                 sz_ord = align256(max_bt * 4), sz_opose = align256(max_bo * 4), sz_xy = align256(max_bo * 16),
-                 sz_xyz = align256(max_bt * 24), sz_ninl = align256(max_bt * 4), sz_ntr = align256(max_bt * 8),
-                 sz_succ = align256(max_bt), sz_mask = align256(max_bo);
-    const size_t total = sz_pose + sz_doff + sz_dtab + sz_off + sz_ord + sz_opose + sz_xy + sz_xyz + sz_ninl + sz_ntr +
-                         sz_succ + sz_mask;
     const CtxView cv = ctx_view(ctx);
-    TRI_HIPCHK(hipSetDevice(cv.device));
+    HIPCHK(hipSetDevice(cv.device));
     hipStream_t st = cv.stream;
-    Events ev;
-    TRI_HIPCHK(hipEventCreate(&ev.a));
-    TRI_HIPCHK(hipEventCreate(&ev.b));
-    TRI_HIPCHK(hipEventRecord(ev.a, st));
-    DevMem mem;
-    TRI_HIPCHK(hipMalloc(&mem.p, total));
-    char* base = static_cast<char*>(mem.p);
-    size_t at = 0;
-    auto carve = [&](size_t bytes) {
-        char* q = base + at;
-        at += bytes;
-        return q;
-    };
-    TriPose* d_pose = reinterpret_cast<TriPose*>(carve(sz_pose));
-    uint64_t* d_doff = reinterpret_cast<uint64_t*>(carve(sz_doff));
-    uint64_t* d_dtab = reinterpret_cast<uint64_t*>(carve(sz_dtab));
-    uint64_t* d_off = reinterpret_cast<uint64_t*>(carve(sz_off));
-    uint32_t* d_ord = reinterpret_cast<uint32_t*>(carve(sz_ord));
-    uint32_t* d_opose = reinterpret_cast<uint32_t*>(carve(sz_opose));
-    double* d_xy = reinterpret_cast<double*>(carve(sz_xy));
-    double* d_xyz = reinterpret_cast<double*>(carve(sz_xyz));
-    uint32_t* d_ninl = reinterpret_cast<uint32_t*>(carve(sz_ninl));
-    uint64_t* d_ntr = reinterpret_cast<uint64_t*>(carve(sz_ntr));
-    uint8_t* d_succ = reinterpret_cast<uint8_t*>(carve(sz_succ));
-    uint8_t* d_mask = reinterpret_cast<uint8_t*>(carve(sz_mask));
-    TRI_HIPCHK(hipMemcpyAsync(d_pose, tab.data(), tab.size() * sizeof(TriPose), hipMemcpyHostToDevice, st));
-    TRI_HIPCHK(hipMemcpyAsync(d_doff, dyn_off.data(), dyn_off.size() * 8, hipMemcpyHostToDevice, st));
-    TRI_HIPCHK(hipMemcpyAsync(d_dtab, dyn_tab.data(), dyn_tab.size() * 8, hipMemcpyHostToDevice, st));
+    StreamTimer timer(st);
+    HIPCHK(timer.start());
+    // one device allocation: constants, then the batch buffers
+    TriPose* d_pose;
+    uint64_t *d_doff, *d_dtab, *d_off, *d_ntr;
+    uint32_t *d_ord, *d_opose, *d_ninl;
+    double *d_xy, *d_xyz;
+    uint8_t *d_succ, *d_mask;
+    DevBuf<void> mem;
+    HIPCHK(DevParts()
+               .part(&d_pose, tab.size())
+               .part(&d_doff, dyn_off.size())
+               .part(&d_dtab, dyn_tab.size())
+               .part(&d_off, max_bt + 1)
+               .part(&d_ord, max_bt)
+               .part(&d_opose, max_bo)
+               .part(&d_xy, 2 * max_bo)
+               .part(&d_xyz, 3 * max_bt)
+               .part(&d_ninl, max_bt)
+               .part(&d_ntr, max_bt)
+               .part(&d_succ, max_bt)
+               .part(&d_mask, max_bo)
+               .carve(mem));
+    HIPCHK(hipMemcpyAsync(d_pose, tab.data(), tab.size() * sizeof(TriPose), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_doff, dyn_off.data(), dyn_off.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_dtab, dyn_tab.data(), dyn_tab.size() * 8, hipMemcpyHostToDevice, st));
 
     std::vector<std::vector<uint32_t>> orders(nbatch);  // host copies stay alive until the stream is drained
     for (size_t bi = 0; bi < nbatch; ++bi) {
@@ -522,11 +465,11 @@ static int triangulate_impl(amc_ctx* ctx, const double* poses, size_t nposes, co
         ord.resize(nt);
         for (size_t t = t0; t < t1; ++t) ord[cnt[bin_of(t)]++] = (uint32_t)(t - t0);
 
-        TRI_HIPCHK(hipMemcpyAsync(d_off, track_offsets + t0, (nt + 1) * 8, hipMemcpyHostToDevice, st));
-        TRI_HIPCHK(hipMemcpyAsync(d_ord, ord.data(), nt * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_off, track_offsets + t0, (nt + 1) * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_ord, ord.data(), nt * 4, hipMemcpyHostToDevice, st));
         if (no) {
-            TRI_HIPCHK(hipMemcpyAsync(d_opose, obs_pose + ob, no * 4, hipMemcpyHostToDevice, st));
-            TRI_HIPCHK(hipMemcpyAsync(d_xy, obs_xy + 2 * ob, no * 16, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_opose, obs_pose + ob, no * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_xy, obs_xy + 2 * ob, no * 16, hipMemcpyHostToDevice, st));
         }
         TriParams p{};
         p.off = d_off;
@@ -548,30 +491,18 @@ static int triangulate_impl(amc_ctx* ctx, const double* poses, size_t nposes, co
         p.num_trials = d_ntr;
         p.success = d_succ;
         p.mask = d_mask;
-        ev.k.push_back(nullptr);
-        TRI_HIPCHK(hipEventCreate(&ev.k.back()));
-        ev.k.push_back(nullptr);
-        TRI_HIPCHK(hipEventCreate(&ev.k.back()));
-        TRI_HIPCHK(hipEventRecord(ev.k[2 * bi], st));
+        HIPCHK(timer.span_begin());
         hipLaunchKernelGGL(tri_kernel, dim3((unsigned)((nt + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, p);
-        TRI_HIPCHK(hipGetLastError());
-        TRI_HIPCHK(hipEventRecord(ev.k[2 * bi + 1], st));
-        TRI_HIPCHK(hipMemcpyAsync(result->xyz + 3 * t0, d_xyz, nt * 24, hipMemcpyDeviceToHost, st));
-        TRI_HIPCHK(hipMemcpyAsync(result->num_inliers + t0, d_ninl, nt * 4, hipMemcpyDeviceToHost, st));
-        TRI_HIPCHK(hipMemcpyAsync(result->num_trials + t0, d_ntr, nt * 8, hipMemcpyDeviceToHost, st));
-        TRI_HIPCHK(hipMemcpyAsync(result->success + t0, d_succ, nt, hipMemcpyDeviceToHost, st));
-        if (no) TRI_HIPCHK(hipMemcpyAsync(result->inlier_mask + ob, d_mask, no, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipGetLastError());
+        HIPCHK(timer.span_end());
+        HIPCHK(hipMemcpyAsync(result->xyz + 3 * t0, d_xyz, nt * 24, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(result->num_inliers + t0, d_ninl, nt * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(result->num_trials + t0, d_ntr, nt * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(result->success + t0, d_succ, nt, hipMemcpyDeviceToHost, st));
+        if (no) HIPCHK(hipMemcpyAsync(result->inlier_mask + ob, d_mask, no, hipMemcpyDeviceToHost, st));
     }
-    TRI_HIPCHK(hipEventRecord(ev.b, st));
-    TRI_HIPCHK(hipEventSynchronize(ev.b));
-    float ms = 0.f;
-    TRI_HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
-    result->device_ms = ms;
-    result->kernel_ms = 0.0;
-    for (size_t bi = 0; bi < nbatch; ++bi) {
-        TRI_HIPCHK(hipEventElapsedTime(&ms, ev.k[2 * bi], ev.k[2 * bi + 1]));
-        result->kernel_ms += ms;
-    }
+    HIPCHK(timer.stop(result->device_ms));  // (result was zeroed on entry)
+    HIPCHK(timer.spans(result->kernel_ms));
     result->num_batches = (uint32_t)nbatch;
     return AMC_OK;
 }

@@ -1181,5 +1181,33 @@ AMC_HD uint32_t mt_temper(uint32_t y) {
     return y;
 }
 
+// ---- RANSAC trial counts (colmap/optim/ransac.h) with the host libm, as COLMAP evaluates them ------------------------
+// Host functions (no AMC_HD): the kernels read them as tables.  Not behind a __HIP_DEVICE_COMPILE__ guard, because the
+// device pass of a .hip file parses its host code too.  Always inlined, so that a literal kmin folds as COLMAP's
+// constexpr kMinNumSamples does: std::pow(r, 2) is r * r there (and in tests/tri_ref), not a libm call.
+// ComputeNumTrials with kMinNumSamples = kmin, from the inlier ratio; ~0 stands for "no bound".  The trial tables by
+// inlier count are compute_num_trials rows; the watermark RANSAC's cut-offs (TvgParams::wm_cut) are found by ratio.
+inline __attribute__((always_inline)) uint64_t num_trials_of_ratio(double inlier_ratio, double confidence,
+                                                                   double multiplier, int kmin) {
+    const double nom = 1 - confidence;
+    if (nom <= 0) return ~(uint64_t)0;
+    const double denom = 1 - std::pow(inlier_ratio, kmin);
+    if (denom <= 0) return 1;
+    if (denom == 1.0) return ~(uint64_t)0;
+    return static_cast<uint64_t>(std::ceil(std::log(nom) / std::log(denom) * multiplier));
+}
+inline __attribute__((always_inline)) uint64_t compute_num_trials(uint64_t num_inliers, uint64_t num_samples,
+                                                                  double confidence, double multiplier, int kmin) {
+    return num_trials_of_ratio(num_inliers / static_cast<double>(num_samples), confidence, multiplier, kmin);
+}
+// the RANSAC constructor's clamp of max_num_trials by the trials min_inlier_ratio needs
+inline __attribute__((always_inline)) uint64_t ransac_max_trials(int64_t max_num_trials, double min_inlier_ratio,
+                                                                 double confidence, double multiplier, int kmin) {
+    const uint64_t kNumSamples = 100000;
+    const uint64_t dyn = compute_num_trials(static_cast<uint64_t>(min_inlier_ratio * kNumSamples), kNumSamples,
+                                            confidence, multiplier, kmin);
+    return static_cast<uint64_t>(max_num_trials) < dyn ? static_cast<uint64_t>(max_num_trials) : dyn;
+}
+
 }  // namespace tvg
 }  // namespace amc

@@ -31,6 +31,14 @@ void shim_residuals(int kind, const double* m, const double* p1, const double* p
                            : h_residual(m, p1[2 * i], p1[2 * i + 1], p2[2 * i], p2[2 * i + 1]);
 }
 unsigned shim_temper(unsigned y) { return mt_temper(y); }
+// ComputeNumTrials as the library's host code evaluates it (tvg_math.h), by count and by ratio
+uint64_t shim_compute_num_trials(uint64_t num_inliers, uint64_t num_samples, double confidence, double multiplier,
+                                 int kmin) {
+    return compute_num_trials(num_inliers, num_samples, confidence, multiplier, kmin);
+}
+uint64_t shim_num_trials_of_ratio(double inlier_ratio, double confidence, double multiplier, int kmin) {
+    return num_trials_of_ratio(inlier_ratio, confidence, multiplier, kmin);
+}
 // The counting loop's FP32 pre-filter for homographies (tvg_math.h h32_prepare / h32_point): per point 1 inlier,
 // 0 outlier, -1 undecided, with the operands prepared as the kernel prepares them (coordinates and scaled
 // coordinates rounded to float; C = largest |coordinate| of the set).

@@ -96,6 +96,31 @@ def test_roots_jacobi_residuals_temper_bit_exact(shim):
     assert shim.shim_temper(0) == 0
 
 
+def test_compute_num_trials_matches_the_oracle(shim):
+    """tvg_math.h's ComputeNumTrials - the one copy behind every trial table and trial cap of the library - against
+    the oracle's, by count and by ratio, for every minimal sample size the library uses.  The oracle's wrapper returns
+    int64 and stands in INT64_MAX for the unbounded ~0; the comparison is on uint64."""
+    shim.shim_compute_num_trials.restype = C.c_uint64
+    shim.shim_compute_num_trials.argtypes = [C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_int]
+    shim.shim_num_trials_of_ratio.restype = C.c_uint64
+    shim.shim_num_trials_of_ratio.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int]
+    unbounded = 2**64 - 1
+    seen = set()
+    for kmin in (1, 2, 3, 4, 5, 7):  # watermark, triangulation, P3P, H, E, F
+        for n in (1, 2, 3, 7, 10, 64, 100, 1000, 65535, 100000):
+            counts = range(n + 1) if n <= 100 else sorted({0, 1, 2, n // 100, n // 10, n // 3, n // 2, n - 1, n})
+            for c in counts:
+                for conf in (0.0, 0.5, 0.99, 0.999, 0.9999, 1.0):
+                    for mult in (0.5, 1.0, 3.0):
+                        want = o.compute_num_trials(c, n, conf, mult, kmin)
+                        want = unbounded if want == np.iinfo(np.int64).max else want
+                        assert shim.shim_compute_num_trials(c, n, conf, mult, kmin) == want, (c, n, conf, mult, kmin)
+                        # c / n: the same correctly rounded double as the C++ num_inliers / double(num_samples)
+                        assert shim.shim_num_trials_of_ratio(c / n, conf, mult, kmin) == want, (c, n, conf, mult, kmin)
+                        seen.add(want if want in (0, 1, unbounded) else "finite")
+    assert seen == {0, 1, unbounded, "finite"}  # every branch: nom <= 0, denom <= 0, denom == 1, the log ratio
+
+
 # ------------------------------------------------------------------ relative pose (pose_math.h) ----
 def _shim_pose(shim, cam1, cam2, p1, p2, config, E, H):
     iout = np.zeros(3, dtype=np.int32)

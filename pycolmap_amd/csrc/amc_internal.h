@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <type_traits>
 #include <vector>
 
@@ -139,6 +140,15 @@ constexpr const char* hipchk_who = nullptr;
             return ::amc::api_fail(AMC_E_HIP, "%s%s%s:%d: %s -> %s", hipchk_who ? hipchk_who : "",                    \
                                    hipchk_who ? ": " : "", __FILE__, __LINE__, #expr, hipGetErrorString(e_));        \
     } while (0)
+
+// Environment switches (test hooks, A/B and profile switches; README.md lists them).  An entry point reads each of its
+// switches once per call, at its top: the tests change them between calls on one context.
+inline bool env_flag(const char* name) { return std::getenv(name) != nullptr; }
+// the variable's integer value clamped to [lo, hi]; dflt when it is not set
+inline long long env_int(const char* name, long long dflt, long long lo, long long hi) {
+    const char* e = std::getenv(name);
+    return e ? std::min(hi, std::max(lo, std::atoll(e))) : dflt;
+}
 
 // Grow-only device (DevBuf) or pinned host (PinBuf) buffer of T.  ensure(n) makes room for n elements, at least 16,
 // without keeping the old contents; release() frees it, and so does the destructor.  Move-only: a move empties the
@@ -414,9 +424,7 @@ struct CopyJob {
 };
 hipError_t launch_match_mfma(int mode, const SegDesc* segs, const uint32_t* nitems_dev, uint32_t max_items,
                        uint32_t* queue_head, uint32_t* accmask, const ScanAccept* accept_dev, hipStream_t s,
-                       const CopyJob& job = CopyJob(), uint32_t* copy_head = nullptr, int leave_cus = 0);
-// leave_cus: launch that many workgroups fewer than the device has CUs (a workgroup owns its CU): the CUs stay free for
-// what runs beside the scan - amc_match_verify_pairs' verification of the batch before
+                       const CopyJob& job = CopyJob(), uint32_t* copy_head = nullptr);
 int match_mfma_shape();  // waves per workgroup in use (8 or 4)
 
 hipError_t launch_resolve_index(int side, const ImageDev* imgs, const PairDev* pairs, uint32_t npairs,
@@ -439,8 +447,6 @@ hipError_t launch_finalize(const ImageDev* imgs, const PairDev* pairs, uint32_t 
 
 // match_common.hip: device -> pinned host copy by a small-grid kernel that co-resides with the scan (bytes % 8 == 0)
 hipError_t launch_host_copy(void* dst_pinned, const void* src_dev, size_t bytes, hipStream_t s);
-// a small copy as a kernel on the stream (pinned host or device memory on either side, 4-byte units): match_common.hip
-hipError_t launch_copy_words(void* dst, const void* src, size_t bytes, hipStream_t s);
 hipError_t launch_reorder_matches(const uint32_t* src_off, const uint32_t* cnt, const uint64_t* dst_off, uint32_t npairs,
                             const uint32_t* src, uint32_t* dst, hipStream_t s);
 

@@ -1,5 +1,5 @@
 // guided_region.h — the geometry of guided matching's candidate generation (match_guided.hip), shared between the
-// kernel and the host (amc_api.hip's per-pair setup; tests/shim/guided_shim.cc, which checks on the CPU that the
+// kernel and the host (amc_match.hip's per-pair setup; tests/shim/guided_shim.cc, which checks on the CPU that the
 // regions computed here contain every pairing the float32 filter accepts).
 //
 // A pair's filter model is F (Sampson error) or H (forward transfer error); `dir` 0 searches image 2 for the

@@ -22,7 +22,7 @@
 // The result is the dense kernel's, bit for bit: the superset only has to contain every entry the float32
 // filter accepts (the slack - 2 % and one pixel - is orders above float32 rounding of the filter for image
 // coordinates; rows whose geometry degenerates scan the whole grid; pairs whose model could make the filter
-// return NaN = "not rejected" never come here: GuidedDev::grid_ok, amc_api.hip).
+// return NaN = "not rejected" never come here: GuidedDev::grid_ok, amc_match.hip).
 #include "amc_internal.h"
 
 namespace amc {

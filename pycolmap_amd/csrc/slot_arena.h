@@ -1,4 +1,4 @@
-// slot_arena.h - the sub-allocator behind the image slots' device memory (amc_api.hip instantiates it over hipMalloc /
+// slot_arena.h - the sub-allocator behind the image slots' device memory (amc_ctx.h instantiates it over hipMalloc /
 // hipFree; tests/shim/slot_arena_fuzz.cc over malloc, to fuzz the block bookkeeping on the CPU).
 #pragma once
 

@@ -405,17 +405,14 @@ def test_fused_match_verify_equals_the_two_calls(amc_ctx, monkeypatch, pose):
     tvg, mask, st = amc_ctx.verify_pairs(s1, s2, off, m, opts, seed=0)
     assert (tvg["config"] == 1).any() and (tvg["config"] >= 2).sum() >= 6     # DEGENERATE (too few matches) and real ones
     # the shipped order (host sides interleaved, one slice behind the last batch), then with many small batches; the
-    # stages fully behind each other (AMC_PIPELINE_SERIAL); the device-interleaved variant kept for the A/B - slices
-    # beside the next batch's scan, more batches than slice slots (the rest joins the last slice), the scan leaving 16
-    # CUs to them
+    # stages fully behind each other (AMC_PIPELINE_SERIAL); the shipped order again with another batch cut
     # ... and a call that fits one batch cut in two (what calls of >= 4096 pairs get: AMC_HOOK_SPLIT=2 takes this small one there)
     for batch_entries, variant in ((None, {}), (None, {"AMC_HOOK_SPLIT": "2"}), (None, {"AMC_HOOK_SPLIT": "0"}),
                                    ("4096", {}), ("4096", {"AMC_PIPELINE_SERIAL": "1"}),
-                                   ("4096", {"AMC_PIPELINE_INTERLEAVE": "1"}),
-                                   ("20000", {"AMC_PIPELINE_INTERLEAVE": "1", "AMC_VERIFY_CUS": "16"})):
+                                   ("20000", {})):
         if batch_entries:
             monkeypatch.setenv("AMC_MATCH_BATCH_ENTRIES", batch_entries)
-        for k in ("AMC_PIPELINE_SERIAL", "AMC_PIPELINE_INTERLEAVE", "AMC_VERIFY_CUS", "AMC_HOOK_SPLIT"):
+        for k in ("AMC_PIPELINE_SERIAL", "AMC_HOOK_SPLIT"):
             monkeypatch.delenv(k, raising=False)
         for k, v in variant.items():
             monkeypatch.setenv(k, v)

@@ -4,8 +4,11 @@
 set -e
 cd "$(dirname "$0")/../pycolmap_amd/csrc"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -I../../include"
+STEMS=$(python -c "import sys; sys.path.insert(0, '../..'); from pycolmap_amd.build import HIP_SOURCES; print(' '.join(n[:-4] for n in HIP_SOURCES))")
 for n in "$@"; do
   /opt/rocm/bin/hipcc $FLAGS -DAMC_DIAG=$n -c match_mfma.hip -o _obj/match_mfma_diag$n.o
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o _obj/libamc_diag$n.so _obj/amc_api.o _obj/match_common.o _obj/match_dot4.o _obj/match_guided.o _obj/match_mfma_diag$n.o _obj/tvg_e.o _obj/tvg_fh.o _obj/tvg_e_big.o _obj/tvg_fh_big.o _obj/pose.o _obj/camera.o
+  OBJS=""
+  for o in $STEMS; do if [ $o = match_mfma ]; then OBJS="$OBJS _obj/match_mfma_diag$n.o"; else OBJS="$OBJS _obj/$o.o"; fi; done
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o _obj/libamc_diag$n.so $OBJS
 done
 ls -la _obj/*.so

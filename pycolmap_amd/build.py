@@ -140,9 +140,9 @@ def build_all(force: bool = False, verbose: bool = True) -> None:
 
 def clean_variants(verbose: bool = True) -> list[str]:
     """Remove what the A/B tools leave under csrc/_obj/ beside the product's own objects: variant libraries
-    (tools/variant_build_tvg.sh, tools/diag_build.sh: libamc_<name>.so), their objects (<file>_<name>.o), the previous
-    revision's source copies and library (tools/ab_prev_lib.sh: prev_src/, libamc_prev.so; tools/ab_build.sh: *_prev.hip).
-    They are git-ignored but ride to the GPU box with every `gpurun` push and confuse anyone grepping csrc/ - run this
+    (tools/variant_build_tvg.sh: libamc_<name>.so), their objects (<file>_<name>.o), the previous revision's source
+    copies and library (tools/ab_prev_lib.sh: prev_src/, libamc_prev.so; tools/ab_build.sh: *_prev.hip, *_prev.o).
+    They are git-ignored but travel with every copy of the tree to a GPU machine and confuse anyone grepping csrc/ - run this
     when an A/B is over (`python -m pycolmap_amd.build clean-variants`).  Returns the names it removed."""
     keep = {Path(n).stem + ".o" for n in HIP_SOURCES} | {Path(n).stem + ".o.inputs" for n in HIP_SOURCES}
     gone = []

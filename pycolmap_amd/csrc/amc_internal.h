@@ -381,9 +381,6 @@ struct alignas(64) SegDesc {
     uint32_t yrows;
     uint32_t pad_;
 };
-#ifndef AMC_MFMA_DEFAULT_WAVES
-#define AMC_MFMA_DEFAULT_WAVES 8   // waves per workgroup of the mfma scan: 8 (x 4 X tiles) or 4 (x 8); AMC_MFMA_SHAPE overrides
-#endif
 // COLMAP's per-row acceptance tests (FindBestMatchesOneWayBruteForce) on a (best,
 // second) pair.  acos thresholds: lut[d] = acosf(min(d/512^2, 1)) built on the HOST with the host
 // libm; (float)d * 2^-18 is exact for d < 2^24, so indexing by min(d, 262144) reproduces COLMAP's
@@ -425,7 +422,6 @@ struct CopyJob {
 hipError_t launch_match_mfma(int mode, const SegDesc* segs, const uint32_t* nitems_dev, uint32_t max_items,
                        uint32_t* queue_head, uint32_t* accmask, const ScanAccept* accept_dev, hipStream_t s,
                        const CopyJob& job = CopyJob(), uint32_t* copy_head = nullptr);
-int match_mfma_shape();  // waves per workgroup in use (8 or 4)
 
 hipError_t launch_resolve_index(int side, const ImageDev* imgs, const PairDev* pairs, uint32_t npairs,
                           Top2* table, uint32_t* accmask, const float* acos_lut, FinalizeParams fp,
@@ -562,14 +558,8 @@ size_t tvg_ws_mask_bytes_host(uint32_t mcap);
 // 7 x 9 matrix (126 VGPRs) spills at 4 waves, and with the scratch traffic those builds had (wave-uniform state and
 // models spilled around every chunk's calls) more waves only added to it (round 3: 4 -> 3 waves +2.4 %).  With that
 // traffic gone (tvg_core.h lo_ransac) the fourth wave hides what latency is left.
-#ifndef AMC_E_WAVES
-#define AMC_E_WAVES 2
-#endif
-#ifndef AMC_FH_WAVES
-#define AMC_FH_WAVES 4
-#endif
-constexpr int kTvgEWavesPerSimd = AMC_E_WAVES;
-constexpr int kTvgFhWavesPerSimd = AMC_FH_WAVES;
+constexpr int kTvgEWavesPerSimd = 2;
+constexpr int kTvgFhWavesPerSimd = 4;
 size_t tvg_lds_bytes(uint32_t mcap, int waves);    // F/H kernel
 size_t tvg_lds_bytes_e(uint32_t mcap, int waves);  // essential-matrix kernel (+ its root finder's scratch)
 // pose.hip: a verification call's records and masks in the caller's layout, work counters summed

@@ -47,14 +47,14 @@
 // Shape.  One workgroup per item (dynamic queue; items in Y order so co-resident workgroups stream
 // the same image out of L2; the next item's descriptor is fetched while the current one is
 // scanned).  <W, XT> = waves per workgroup x resident 32-row X tiles per wave, W * XT = 32:
-//   <8, 4>  512 threads, a segment per wave, 2 waves per SIMD (256 registers each)
+//   <8, 4>  512 threads, a segment per wave, 2 waves per SIMD (256 registers each): the shape that is built
 //   <4, 8>  256 threads, two segments per wave, 1 wave per SIMD (512 registers): half the LDS
-//           fragment traffic per MFMA, the wave's own VALU fills its own MFMA shadows
+//           fragment traffic per MFMA, the wave's own VALU fills its own MFMA shadows; 0.5-1 % slower in the
+//           kernel and no longer instantiated - the template still describes it
 // Y streams through LDS in 256-row chunks by direct-to-LDS DMA, three buffers, the pieces of chunk c+2
 // issued one per Y tile of chunk c, one barrier per chunk; the prepared arena is pre-swizzled so the linear DMA image is bank-conflict-free for
 // ds_read_b128.  Each wave software-pipelines: the 4 MFMAs of unit u+1 are interleaved with the
 // 12 VALU of unit u (unit = 32 Y rows x 32 X rows), two accumulator sets.
-#include <climits>
 #include <cstdlib>
 
 #include "amc_internal.h"
@@ -71,9 +71,6 @@ constexpr int kBN = 256;                // Y rows per LDS chunk (= kRowPad); 512
 constexpr int kYT = kBN / 32;           // Y tiles per chunk
 constexpr int kChunkBytes = kBN * kDim; // 32 KiB
 constexpr int kSegTiles = kSegRows / 32;  // 32-row X tiles per segment
-#ifndef AMC_KEY_INSERT
-#define AMC_KEY_INSERT 1   // 0: the four-instruction insertion with an explicit tile register (A/B)
-#endif
 constexpr int kKeyShift = 7, kKeyCarried = 127;
 
 // single LDS object (a second __shared__ object de-pipelines the DMA waits).  THREE chunk buffers: while chunk c is
@@ -144,8 +141,13 @@ struct YFrag {
 // with the scan's stream more often than not.  So the copy rides in the scan's own launch: the first `parts`
 // workgroups to arrive take one part each - 512 lanes with four 16-byte loads in flight per lane saturate PCIe from
 // a handful of workgroups - and then scan like the others; the scan loses parts x 10 ms of one workgroup's time.
-__device__ __noinline__ void copy_part(const uint4* __restrict__ src, uint4* __restrict__ dst, unsigned long long b,
-                                       unsigned long long e, int tid, int nthreads) {
+// Compiled as ONE general function of (tid, nthreads) for a workgroup of four or eight waves - the code the scan was
+// measured with.  `used` keeps the compiler from specialising it for its single caller's thread count (which also
+// moves that kernel's register allocation); the assumption states the ranges it may rely on.
+__device__ __noinline__ __attribute__((used)) void copy_part(const uint4* __restrict__ src, uint4* __restrict__ dst,
+                                                             unsigned long long b, unsigned long long e, int tid,
+                                                             int nthreads) {
+    __builtin_assume(tid >= 0 && tid < 1024 && nthreads >= 256 && nthreads <= 512);
     unsigned long long i = b + (unsigned long long)tid;
     const unsigned long long st = (unsigned long long)nthreads;
     for (; i + 3 * st < e; i += 4 * st) {
@@ -277,13 +279,8 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
             // acc = sum a'b' + 128*SY_j = v - (128*SX_i - 2^21)
             xterm[xt] = xrs[row] - (1 << 21);
             // COLMAP's floor best = second = 0  <=>  acc = -xterm
-#if AMC_KEY_INSERT
             best[xt] = ((-xterm[xt]) << kKeyShift) | kKeyCarried;  // a key: value << 7 | tile code (see `insert`)
             sec[xt] = best[xt];
-#else
-            best[xt] = -xterm[xt];
-            sec[xt] = -xterm[xt];
-#endif
             btile[xt] = -1;
         }
     };
@@ -316,10 +313,7 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
         // image's zero padding (rows_pad is a multiple of 256) - a zero row can never become a best nor raise a second,
         // so its tiles need not be scanned (round 6: an image of 4,000 rows paid for 4,096; n ~ U[2000, 6000]: 2.4 % of
         // the scan).  An image whose rows fill its last chunk scans all kYT tiles as before.
-#ifndef AMC_SKIP_PAD_TILES
-#define AMC_SKIP_PAD_TILES 1
-#endif
-        const int last_tiles = AMC_SKIP_PAD_TILES ? ((((yrows_item - (nchunks - 1) * kBN) + 31) / 32 + 1) & ~1) : kYT;
+        const int last_tiles = (((yrows_item - (nchunks - 1) * kBN) + 31) / 32 + 1) & ~1;
         const bool active = any_rows(dv);  // wave-uniform
         if (tid == 0) *s_q = atomicAdd(queue_head, 1u);  // the next item, behind the loads already in flight
 
@@ -343,7 +337,6 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
         // row's second is the larger of the two.
         // Insertion of a unit maximum into a lane's (best, second, tile) state, in place (no copies for the
         // register allocator to make).
-#if AMC_KEY_INSERT
         // Three instructions: the state holds KEYS, value << 7 | code, code = 126 - (tile mod 64).  The accumulators stay
         // below 2^24 in magnitude (|sum a'b'| <= 2^21, 128 SY < 2^22), so a key fits 32 bits; a larger value is a
         // larger key, equal values are ordered first tile first (strict '>' of the reference scan), and the second
@@ -366,48 +359,17 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
                 best[xt] |= kKeyCarried;
             }
         };
-#else
-        // The compare comes first: on gfx950 a VALU read of VCC needs two
-        // instructions between it and the VALU write.  Strict '>': the first tile wins ties.
-        auto insert = [&](int xt, int m, int tile) __attribute__((always_inline)) {
-            asm volatile(
-                "v_cmp_gt_i32 vcc, %3, %0\n\t"
-                "v_med3_i32 %1, %0, %1, %3\n\t"  // sec <= best always: the new second of the maxima
-                "v_max_i32 %0, %0, %3\n\t"
-                "v_cndmask_b32 %2, %2, %4, vcc"
-                : "+v"(best[xt]), "+v"(sec[xt]), "+v"(btile[xt])
-                : "v"(m), "v"(tile)
-                : "vcc");
-        };
-#endif
         // The insertion of a unit's maximum does not touch accumulators, so it is deferred into
         // the hazard slot of the NEXT phase (between its first two MFMAs): pm / ptile carry the
         // pending maximum (of X tile xtc - 1) from one phase to the next.
-#if AMC_KEY_INSERT
         int pm = -(1 << 24), ptile = 0;  // a pending "maximum" below every accumulator: its key is below every floor key
-#else
-        int pm = INT_MIN, ptile = 0;
-#endif
         auto phase = [&](i32x16& an, const YFrag& y, int xtn, const i32x16& ac, int xtc, int tile)
                          __attribute__((always_inline)) {
             mfma_first<BA>(an, y.f[0], xf[xtn][0], y.ci);
             __builtin_amdgcn_sched_barrier(0);
-#if defined(AMC_DIAG) && (AMC_DIAG & 2)
-            mfma_acc<BA>(an, y.f[1], xf[xtn][1]);
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_acc<BA>(an, y.f[2], xf[xtn][2]);
-            __builtin_amdgcn_sched_barrier(0);
-            pm = smax2(pm, ac[0]);  // timing diagnostic: one VALU per unit keeps the accumulators live
-            ptile = tile;
-            (void)insert;
-#else
-#if AMC_KEY_INSERT
             insert((xtc + XT - 1) % XT, pm, 126 - (ptile & 63));
             // the last unit of a 64-tile block has just gone in: settle the tiles before the next block reuses the codes
             if (xtc == 0 && tile != 0 && (tile & 63) == 0) flush((tile >> 6) - 1);
-#else
-            insert((xtc + XT - 1) % XT, pm, ptile);
-#endif
             __builtin_amdgcn_sched_barrier(0);
             mfma_acc<BA>(an, y.f[1], xf[xtn][1]);
             __builtin_amdgcn_sched_barrier(0);
@@ -435,7 +397,6 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
                 : "v"(t1), "v"(t2), "v"(ac[12]), "v"(ac[13]), "v"(ac[14]), "v"(ac[15]), "v"(t3));
             pm = t0;
             ptile = tile;
-#endif
             __builtin_amdgcn_sched_barrier(0);
             mfma_acc<BA>(an, y.f[3], xf[xtn][3]);
             __builtin_amdgcn_sched_barrier(0);
@@ -464,7 +425,6 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
             const bool lastt = (yt == kYT - 1);
             const bool cross = lastt && (c + 1 < nchunks);
             const bool fetch = c + 2 < nchunks;  // chunk c + 2 goes to the buffer chunk c - 1 left: (c + 2) % 3
-#if !(defined(AMC_DIAG) && (AMC_DIAG & 8))
             if (fetch) {
                 const int fb = cb == 0 ? 2 : cb - 1;
                 constexpr int kEvery = kYT / kPW;  // a piece every tile (one wave per SIMD) or every other tile
@@ -472,9 +432,7 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
                 else if (even) stage_piece(yprep, c + 2, fb, yt / 2);
                 if (yt == 0) stage_rs(yrs, c + 2, fb);
             }
-#endif
             if (cross) {
-#if !(defined(AMC_DIAG) && (AMC_DIAG & 4))
                 // chunk c + 1 must have landed: everything but this chunk's own kPW (+ 1) pieces of chunk c + 2
                 if (!fetch) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 else if (wid == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPW + 1) : "memory");
@@ -482,7 +440,6 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
                 // a bare barrier: __syncthreads() is a fence and would drain the pieces just issued (vmcnt(0)).
                 // Nothing is stored to LDS here by a wave itself; the DMA'd bytes are ordered by the waits above.
                 asm volatile("s_barrier" ::: "memory");
-#endif
             }
             if (active) {
                 // very last tile: re-read itself (result unused) to stay branch-free
@@ -514,7 +471,6 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
             }
             cb = nb;
         }
-#if AMC_KEY_INSERT
         if (active) {
             insert(XT - 1, pm, 126 - (ptile & 63));  // the last unit's maximum is still pending
             flush(ptile >> 6);
@@ -524,9 +480,6 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
                 sec[xt] >>= kKeyShift;
             }
         }
-#else
-        if (active) insert(XT - 1, pm, ptile);  // the last unit's maximum is still pending
-#endif
         __syncthreads();  // everyone is done with both LDS chunk buffers (and has read the queue slot)
 
         // ---- item done.  Start the next one's loads, then decode and store this one under them ----
@@ -565,11 +518,6 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
                     int row = kl;  // MODE 0: `out` points at the segment's first row
                     if (MODE == 1) row = (int)reinterpret_cast<const uint32_t*>(dptr(dv, h, kDList))[kl];
                     Top2 o;
-#if defined(AMC_DIAG) && (AMC_DIAG & 1)
-                    // timing diagnostic: every row "has no match" (the scan state only feeds the pad word)
-                    o.best_v = 0; o.best_idx = 0xFFFFFFFFu; o.second_v = 0; o.pad = (uint32_t)(b ^ s ^ t) & 0u;
-                    out[row] = o;
-#else
                     o.best_v = (uint32_t)(b + ex[xt]);
                     o.best_idx = o.best_v ? (uint32_t)t : 0xFFFFFFFFu;  // TILE of the best
                     o.second_v = (uint32_t)(s + ex[xt]);
@@ -578,7 +526,6 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
                     // a larger second only ever rejects: rows failing now can be forgotten
                     // (scan_accept.h: thresholds instead of acos; a superset of what the exact tests keep)
                     if (MODE == 0) acc_bit = scan_may_accept(sa, o.best_v, o.second_v);
-#endif
                 }
                 if (MODE == 0 && cnt > 0) {  // accept bits of the 32 rows of this X tile (lanes 0..31)
                     const uint32_t bits = (uint32_t)__ballot(acc_bit);
@@ -759,16 +706,6 @@ hipError_t launch_build_segments(int mode, const ImageDev* imgs, const PairDev* 
     return hipGetLastError();
 }
 
-int match_mfma_shape() {
-    static const int shape = [] {
-        const char* e = std::getenv("AMC_MFMA_SHAPE");  // A/B switch: "8x4" or "4x8"
-        if (e && e[0] == '4') return 4;
-        if (e && e[0] == '8') return 8;
-        return AMC_MFMA_DEFAULT_WAVES;
-    }();
-    return shape;
-}
-
 hipError_t launch_match_mfma(int mode, const SegDesc* segs, const uint32_t* nitems_dev, uint32_t max_items,
                              uint32_t* queue_head, uint32_t* accmask, const ScanAccept* accept_dev, hipStream_t s,
                              const CopyJob& job_in, uint32_t* copy_head) {
@@ -790,16 +727,13 @@ hipError_t launch_match_mfma(int mode, const SegDesc* segs, const uint32_t* nite
     const uint32_t grid = max_items < (uint32_t)cus ? max_items : (uint32_t)cus;
     if (job.parts > grid) job.parts = grid;  // every part needs a workgroup
     if ((e = memset_async(queue_head, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
-    const bool w4 = match_mfma_shape() == 4;
-#define AMC_LAUNCH(M, W, XT)                                                                             \
-    hipLaunchKernelGGL((match_mfma_kernel<M, W, XT>), dim3(grid), dim3(64 * W), 0, s, segs, nitems_dev, \
-                       queue_head, accmask, accept_dev, job, copy_head)
-    if (mode == 0) {
-        if (w4) AMC_LAUNCH(0, 4, 8); else AMC_LAUNCH(0, 8, 4);
-    } else {
-        if (w4) AMC_LAUNCH(1, 4, 8); else AMC_LAUNCH(1, 8, 4);
-    }
-#undef AMC_LAUNCH
+    constexpr int kW = 8, kXT = 4;  // eight waves x four X tiles (see "Shape" at the top)
+    if (mode == 0)
+        hipLaunchKernelGGL((match_mfma_kernel<0, kW, kXT>), dim3(grid), dim3(64 * kW), 0, s, segs, nitems_dev, queue_head,
+                           accmask, accept_dev, job, copy_head);
+    else
+        hipLaunchKernelGGL((match_mfma_kernel<1, kW, kXT>), dim3(grid), dim3(64 * kW), 0, s, segs, nitems_dev, queue_head,
+                           accmask, accept_dev, job, copy_head);
     return hipGetLastError();
 }
 

@@ -2,7 +2,7 @@
 // SURVEY.md A.3) on gfx950: one LO-RANSAC (LORANSAC<Est, LocalEst>::Estimate) by one wavefront.  Included by the two
 // kernels that run it, each with its own register budget and occupancy:
 //   tvg_e.hip   the essential-matrix RANSAC (5-point solver and its degree-10 root finder: 256 VGPRs, 2 waves per SIMD)
-//   tvg_fh.hip  the fundamental-matrix and homography RANSACs, model selection, watermark test (AMC_FH_WAVES = 3 per SIMD)
+//   tvg_fh.hip  the fundamental-matrix and homography RANSACs, model selection, watermark test (128 VGPRs, 4 waves per SIMD)
 // (one translation unit each: a device function shared by kernels with different occupancy attributes is compiled
 // for the loosest of them).
 //
@@ -57,11 +57,7 @@ constexpr int kModelDoubles = 64 * kMaxModels * 9;
 // 720 bytes of its own: a store instruction of the solving lanes touched 64 lines (5,760 partial-line writes per
 // 5-point chunk, and the wave waited for them before the counting loop could read the table); element-major a store
 // is 512 contiguous bytes.
-#if defined(AMC_MODELS_BY_TRIAL)   // (A/B hook: the round-5 layout)
-__device__ __forceinline__ constexpr size_t model_at(int m, int i, int t) { return ((size_t)t * kMaxModels + m) * 9 + i; }
-#else
 __device__ __forceinline__ constexpr size_t model_at(int m, int i, int t) { return (size_t)(m * 9 + i) * 64 + (size_t)t; }
-#endif
 
 // LDS objects are addressed through address-space-3 pointers so that every access is a ds_* instruction (a generic
 // pointer makes the compiler emit flat_* loads, which take the vector-memory path and cost several hundred cycles).
@@ -101,13 +97,8 @@ typedef lds_u16 idx_u16;
 // The waves' workspaces are global memory, but the pointers to them travel through structs and calls, where the compiler
 // loses the address space and emits flat_* accesses (64-bit address arithmetic on the vector unit, and a flat access
 // counts on the LDS counter too: every LDS wait then also waits for the outstanding loads from memory).  gptr() names
-// the address space where a workspace is touched: global_load / global_store with a scalar base (AMC_TVG_FLAT=1: the
-// round-6 code, for A/B runs).
-#if defined(AMC_TVG_FLAT)
-#define AMC_GLOBAL
-#else
+// the address space where a workspace is touched: global_load / global_store with a scalar base.
 #define AMC_GLOBAL __attribute__((address_space(1)))
-#endif
 template <class T>
 __device__ __forceinline__ AMC_GLOBAL T* gptr(T* p) { return (AMC_GLOBAL T*)p; }
 
@@ -536,11 +527,8 @@ __device__ __forceinline__ SamplerState sample_chunk_t(const uint32_t* stream, u
     return st;
 }
 
-#ifndef AMC_SAMPLE_INLINE
-#define AMC_SAMPLE_INLINE __noinline__
-#endif
 template <int kMin>
-__device__ AMC_SAMPLE_INLINE SamplerState sample_chunk(const uint32_t* stream_, uint32_t slen_, idx_u16* perm_, lds_u16* sidx_,
+__device__ __noinline__ SamplerState sample_chunk(const uint32_t* stream_, uint32_t slen_, idx_u16* perm_, lds_u16* sidx_,
                                                   lds_u32* rawcnt_, lds_u16* jt_, SamplerState st, int M_, int nT_, int lane,
                                                   int force_slow_, uint32_t* err_) {
     // everything but `lane` is wave-uniform: move it to scalar registers
@@ -598,16 +586,11 @@ __device__ __forceinline__ bool better(const Support a, const Support b) {
 // InlierSupportMeasurer::Evaluate.  The count comes from ballots (wave-uniform by construction);
 // the residual sum is only ever consulted when the count ties or beats the best so far
 // (Compare()), so its 64-way butterfly is skipped otherwise (`need_sum_from` = that count).
-// (A/B hooks, round 6, same box, kernels per 124,750 pairs: score() inlined into the replay loop 421.1 -> 417.1 / 419.8 ->
-// 415.5 ms - the caller's live registers are not spilled around ~50 calls per RANSAC; extract_inliers inlined 450 ms: no)
-#ifndef AMC_SCORE_INLINE
-#define AMC_SCORE_INLINE __forceinline__
-#endif
-#ifndef AMC_EXTRACT_INLINE
-#define AMC_EXTRACT_INLINE __noinline__
-#endif
+// (Round 6, same box, kernels per 124,750 pairs: score() inlined into the replay loop 421.1 -> 417.1 / 419.8 ->
+// 415.5 ms - the caller's live registers are not spilled around ~50 calls per RANSAC; extract_inliers inlined 450 ms:
+// it stays a call)
 template <int KIND>
-__device__ AMC_SCORE_INLINE Support score(const Model9 mv, const Pts P_, int M_, double max_res_, int lane, int need_sum_from) {
+__device__ __forceinline__ Support score(const Model9 mv, const Pts P_, int M_, double max_res_, int lane, int need_sum_from) {
     double m[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) m[i] = uni(mv.v[i]);
@@ -644,7 +627,7 @@ __device__ AMC_SCORE_INLINE Support score(const Model9 mv, const Pts P_, int M_,
 
 // ---- local optimisation over the ordered inlier list w.inl[0..K) ---------------------------------
 // ordered compaction of the inlier indices of `model` (kind); returns K
-__device__ AMC_EXTRACT_INLINE int extract_inliers(idx_u16* inl, int lane, int kind, const Model9 mv, const Pts P, int M,
+__device__ __noinline__ int extract_inliers(idx_u16* inl, int lane, int kind, const Model9 mv, const Pts P, int M,
                                             double max_res) {
     const double* model = mv.v;
     int base = 0;
@@ -673,10 +656,8 @@ __device__ AMC_EXTRACT_INLINE int extract_inliers(idx_u16* inl, int lane, int ki
 // CenterAndNormalizeImagePoints over the K listed points of image `img` (0: x1,y1; 1: x2,y2):
 // only the transform T is produced; the normalised coordinates are recomputed where they are
 // consumed (apply_T), with the operations of the reference loop, instead of being stored.
-// the steps of a local solve as calls (default) or inlined into local_estimate (-DAMC_LO_SUB=__forceinline__: A/B hook)
-#ifndef AMC_LO_SUB
-#define AMC_LO_SUB __noinline__
-#endif
+// The steps of a local solve (jacobi_eigen_wave, real_roots10_wave, e5_build_wave, e5_models_wave) are calls: inlined
+// into local_estimate they measured -0.3 %.
 struct LoCtx {  // what the local estimators need of the wave, passed by value (registers)
     idx_u16* inl;
     lds_f64* jacA;
@@ -690,32 +671,8 @@ struct LoCtx {  // what the local estimators need of the wave, passed by value (
 // double and store, written and read back across the solve's four calls - most of what the essential-matrix kernel
 // moved through the memory side.
 constexpr int kE5UniNsp = 0, kE5UniB = 36, kE5UniDet = 81, kE5UniRoots = 92, kE5UniDoubles = 102;
-__device__ __forceinline__ void center_T(const LoCtx& w, const Pts& P, int img, int K, double* T) {
-    const int lane = w.lane;
-    double ax = 0.0, ay = 0.0;
-    for (int k = lane; k < K; k += 64) {
-        double p[4];
-        load_pt(P, w.inl[k], p[0], p[1], p[2], p[3]);
-        ax += p[2 * img]; ay += p[2 * img + 1];
-    }
-    const double cx = butterfly(ax) / (double)K;
-    const double cy = butterfly(ay) / (double)K;
-    double ar = 0.0;
-    for (int k = lane; k < K; k += 64) {
-        double p[4];
-        load_pt(P, w.inl[k], p[0], p[1], p[2], p[3]);
-        const double ddx = p[2 * img] - cx, ddy = p[2 * img + 1] - cy;
-        ar += ddx * ddx + ddy * ddy;
-    }
-    double rms = butterfly(ar);
-    rms = dsqrt(rms / (double)K);
-    const double nf = dsqrt(2.0) / rms;
-    T[0] = nf; T[1] = 0; T[2] = -nf * cx;
-    T[3] = 0; T[4] = nf; T[5] = -nf * cy;
-    T[6] = 0; T[7] = 0; T[8] = 1;
-}
-// both images' transforms in two passes over the listed records instead of four (round 6): a record holds both
-// images' coordinates, and each image's sums see the addends center_T gives them, in the same order
+// both images' transforms in two passes over the listed records (round 6; four before, two per image): a record holds
+// both images' coordinates, and each image's sums see the addends a pass of its own gives them, in the same order
 __device__ __forceinline__ void center_T_both(const LoCtx& w, const Pts& P, int K, double* T1, double* T2) {
     const int lane = w.lane;
     double ax1 = 0.0, ay1 = 0.0, ax2 = 0.0, ay2 = 0.0;
@@ -827,7 +784,7 @@ __device__ __forceinline__ void jacobi_pair9(int r, int e, int& p, int& q) {
     p = x < y ? x : y;
     q = x < y ? y : x;
 }
-__device__ AMC_LO_SUB void jacobi_eigen_wave(lds_f64* A, lds_f64* V, int lane) {
+__device__ __noinline__ void jacobi_eigen_wave(lds_f64* A, lds_f64* V, int lane) {
     constexpr int n = 9, rounds = 9, np = 4;  // the only size the kernel decomposes as a wave
     for (int i = lane; i < n * n; i += 64) V[i] = ((i / n) == (i % n)) ? 1.0 : 0.0;
     wave_lds_sync();
@@ -996,7 +953,7 @@ struct WaveRootChain<DEG, 1> {
     }
 };
 // all real roots of a degree-10 polynomial (wave-uniform input), ascending; = real_roots_t<10>
-__device__ AMC_LO_SUB int real_roots10_wave(const lds_f64* c_in, lds_f64* roots_out, lds_f64* tmp, int lane) {
+__device__ __noinline__ int real_roots10_wave(const lds_f64* c_in, lds_f64* roots_out, lds_f64* tmp, int lane) {
     double c[11], roots[10];
 #pragma unroll
     for (int i = 0; i <= 10; ++i) c[i] = c_in[i];
@@ -1023,8 +980,7 @@ __device__ AMC_LO_SUB int real_roots10_wave(const lds_f64* c_in, lds_f64* roots_
 // row swap to its own column, and one multiply and nine multiply-subtracts finish the step.  Every element goes
 // through the operations e5_build applies to it, in the same order: the same bits.
 // sc: >= 162 doubles of LDS (jacA + jacV).  Layout while the rows are built: [0, 90) E E^T, [100, 136) E's basis.
-#if !defined(AMC_TVG_E5_ROWS_ALL_LANES)
-__device__ AMC_LO_SUB void e5_build_wave(const lds_f64* nsp, lds_f64* PB, lds_f64* Pdet, lds_f64* sc, int lane) {
+__device__ __noinline__ void e5_build_wave(const lds_f64* nsp, lds_f64* PB, lds_f64* Pdet, lds_f64* sc, int lane) {
     lds_f64* el = sc + 100;  // el[k * 4 + d] = e[k][d]
     if (lane < 36) {
         const int k = lane >> 2, d = lane & 3;
@@ -1122,83 +1078,6 @@ __device__ AMC_LO_SUB void e5_build_wave(const lds_f64* nsp, lds_f64* PB, lds_f6
 #pragma unroll
         for (int r = 1; r < 10; ++r) g[r] = 0.0;
     }
-#else
-__device__ AMC_LO_SUB void e5_build_wave(const lds_f64* nsp, lds_f64* PB, lds_f64* Pdet, lds_f64* sc, int lane) {
-    double e[9][4];
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-#pragma unroll
-        for (int d = 0; d < 4; ++d) e[k][d] = nsp[d * 9 + k];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double a[10], b[10], c[10];
-            e5_mul11(e[3 * i], e[3 * j], a);
-            e5_mul11(e[3 * i + 1], e[3 * j + 1], b);
-            e5_mul11(e[3 * i + 2], e[3 * j + 2], c);
-            if (lane == 0) {
-#pragma unroll
-                for (int t = 0; t < 10; ++t) sc[(3 * i + j) * 10 + t] = (a[t] + b[t]) + c[t];
-            }
-        }
-    wave_lds_sync();
-    if (lane == 0) {
-#pragma unroll
-        for (int t = 0; t < 10; ++t) sc[90 + t] = (sc[t] + sc[40 + t]) + sc[80 + t];
-    }
-    wave_lds_sync();
-    double g[10];  // this lane's column of G
-    auto keep = [&](double& dst, const double (&row)[20]) {
-        double x = row[19];
-#pragma unroll
-        for (int c = 18; c >= 0; --c) x = lane == c ? row[c] : x;
-        dst = x;
-    };
-    {   // det(E) -> row 0
-        double a[10], b[10], d[10], t0[20], t1[20], t2[20], row[20];
-        e5_mul11(e[4], e[8], a); e5_mul11(e[5], e[7], b);
-#pragma unroll
-        for (int i = 0; i < 10; ++i) d[i] = a[i] - b[i];
-        e5_mul21(d, e[0], t0);
-        e5_mul11(e[3], e[8], a); e5_mul11(e[5], e[6], b);
-#pragma unroll
-        for (int i = 0; i < 10; ++i) d[i] = a[i] - b[i];
-        e5_mul21(d, e[1], t1);
-        e5_mul11(e[3], e[7], a); e5_mul11(e[4], e[6], b);
-#pragma unroll
-        for (int i = 0; i < 10; ++i) d[i] = a[i] - b[i];
-        e5_mul21(d, e[2], t2);
-#pragma unroll
-        for (int i = 0; i < 20; ++i) row[i] = (t0[i] - t1[i]) + t2[i];
-        keep(g[0], row);
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double q[10], acc[20], tmp[20], row[20];
-#pragma unroll
-            for (int t = 0; t < 10; ++t) q[t] = sc[(3 * i) * 10 + t];
-            e5_mul21(q, e[j], acc);
-#pragma unroll
-            for (int t = 0; t < 10; ++t) q[t] = sc[(3 * i + 1) * 10 + t];
-            e5_mul21(q, e[3 + j], tmp);
-#pragma unroll
-            for (int t = 0; t < 20; ++t) acc[t] = acc[t] + tmp[t];
-#pragma unroll
-            for (int t = 0; t < 10; ++t) q[t] = sc[(3 * i + 2) * 10 + t];
-            e5_mul21(q, e[6 + j], tmp);
-#pragma unroll
-            for (int t = 0; t < 20; ++t) acc[t] = acc[t] + tmp[t];
-#pragma unroll
-            for (int t = 0; t < 10; ++t) q[t] = sc[90 + t];
-            e5_mul21(q, e[3 * i + j], tmp);
-#pragma unroll
-            for (int t = 0; t < 20; ++t) row[t] = acc[t] * 2.0 - tmp[t];
-            keep(g[1 + 3 * i + j], row);
-        }
-#endif
     // Gauss-Jordan with partial pivoting on the left 10 x 10 block, one column per lane
 #pragma unroll
     for (int col = 0; col < 10; ++col) {
@@ -1255,7 +1134,7 @@ __device__ AMC_LO_SUB void e5_build_wave(const lds_f64* nsp, lds_f64* PB, lds_f6
     wave_lds_sync();
 }
 // e5_models with root i on lane i; the models come back wave-uniform, in root order
-__device__ AMC_LO_SUB int e5_models_wave(const lds_f64* nsp_, const lds_f64* PB, const lds_f64* roots, int nr, lds_f64* models,
+__device__ __noinline__ int e5_models_wave(const lds_f64* nsp_, const lds_f64* PB, const lds_f64* roots, int nr, lds_f64* models,
                                            int lane) {
     const double z = roots[lane < 10 ? lane : 0];
     double nsp[36];
@@ -1329,9 +1208,6 @@ inline void lodiag_report_spans(const char* name) {
 #endif
 
 // local estimator on the K listed inlier correspondences -> models (uniform), count
-#ifndef AMC_LOCAL_INLINE
-#define AMC_LOCAL_INLINE __noinline__
-#endif
 // The models come back in LDS, at w.jacA (round 6: they are wave-uniform, and as a private array of the caller every
 // lane stored its copy to scratch - 46 KB per local 5-point solve - and read it back).
 __device__ __forceinline__ void put_models(lds_f64* dst, const double* m, int n, int lane) {
@@ -1340,7 +1216,7 @@ __device__ __forceinline__ void put_models(lds_f64* dst, const double* m, int n,
         for (int i = 0; i < n; ++i) dst[i] = m[i];
 }
 template <int LOCAL>
-__device__ AMC_LOCAL_INLINE int local_estimate(const LoCtx w, const Pts P, int K) {
+__device__ __noinline__ int local_estimate(const LoCtx w, const Pts P, int K) {
     const int lane = w.lane;
     lds_f64* out = w.jacA;
     double models[9];
@@ -1406,12 +1282,7 @@ __device__ AMC_LOCAL_INLINE int local_estimate(const LoCtx w, const Pts P, int K
         return 1;
     }
     double T1[9], T2[9];
-#if defined(AMC_TVG_CENTER_SEPARATE)   // (A/B hook: one image at a time, four passes)
-    center_T(w, P, 0, K, T1);
-    center_T(w, P, 1, K, T2);
-#else
     center_T_both(w, P, K, T1, T2);
-#endif
     LODIAG_T0();
     LODIAG_COUNT(LOCAL == K_F8 ? 8 : 12);
     if (LOCAL == K_F8) {
@@ -1558,14 +1429,9 @@ __device__ __noinline__ int real_roots10_lanes(const double* c_in, double* roots
 // only change the course of the sequential algorithm if its count reaches the best count so far, so all the replay
 // needs per trial is an upper bound of the largest count among its models; the few
 // trials that qualify are re-scored in full there.
-// (A/B hooks, round 6: the chunk's per-lane record crosses these two calls through memory - scratch, 64 lanes x 4 bytes per
-// dword and store - when they are not inlined; -DAMC_SOLVE_CHUNK_INLINE=__forceinline__ / -DAMC_COUNT_CHUNK_INLINE=...)
-#ifndef AMC_SOLVE_CHUNK_INLINE
-#define AMC_SOLVE_CHUNK_INLINE __noinline__
-#endif
-#ifndef AMC_COUNT_CHUNK_INLINE
-#define AMC_COUNT_CHUNK_INLINE __forceinline__   // (same box, kernels per 124,750 pairs: 419.6 / 421.7 ms as a call, 414.3 / 417.3 inlined)
-#endif
+// (Round 6: the chunk's per-lane record crosses a call through memory - scratch, 64 lanes x 4 bytes per dword and
+// store.  solve_chunk is a call all the same; count_chunk is inlined: same box, kernels per 124,750 pairs, 419.6 /
+// 421.7 ms as a call, 414.3 / 417.3 inlined.)
 struct ChunkModels {   // returned by value (registers); the models themselves are in the wave's model table
     int nmod;    // models of this lane's trial
     int maxcnt;  // max inlier count over them (-1: none)
@@ -1699,12 +1565,9 @@ __device__ __forceinline__ void f64_count1(const double (&m)[9], const F64Rec& r
 // correspondences [k0, k1) against the lane's model; ub (an upper bound of the inlier count) is carried from segment to segment.  The records
 // are requested a few 64-byte lines at a time (see count_lanes_h32 on why: one "all loads back" wait per batch).
 typedef double d8v __attribute__((ext_vector_type(8)));
-#ifndef AMC_F64_BATCH
-#define AMC_F64_BATCH 4   // 64-byte lines (2 correspondences each) requested together
-#endif
 __device__ __forceinline__ void count_lanes_f64(const double (&m)[9], const AMC_CONST double* tab, int k0, int k1, double T,
                                                 int& ub) {
-    constexpr int kB = AMC_F64_BATCH;
+    constexpr int kB = 4;  // 64-byte lines (2 correspondences each) requested together
     int k = k0;
     if ((k0 & 1) == 0) {  // (segments start on even correspondences: whole lines)
         const AMC_CONST d8v* tabq = reinterpret_cast<const AMC_CONST d8v*>(tab);
@@ -1797,9 +1660,6 @@ __device__ __forceinline__ H32Rec h32_rec_of(const f16v& q, int half) {  // reco
     else { r.a = (v2f){q[8], q[9]}; r.b = (v2f){q[10], q[11]}; r.cs = (v2f){q[12], q[13]}; r.ds = (v2f){q[14], q[15]}; }
     return r;
 }
-#ifndef AMC_H32_BATCH
-#define AMC_H32_BATCH 5   // 64-byte lines (4 correspondences each) requested together
-#endif
 // Upper bound of the lane's model's inlier count: M minus the correspondences that are outliers beyond doubt.
 // (Round 6: leaving the loop once no model of the chunk can reach the best count any more - ~80 % into the table of a
 // non-planar pair - measured: no gain, the look at the bound every 40 correspondences costs what the skipped tail saves.)
@@ -1810,9 +1670,9 @@ __device__ __forceinline__ int count_lanes_h32(const H32Lane& hl, const AMC_CONS
     const int np = M >> 1, last = ((M + 1) >> 1) - 1;  // full pairs; index of the table's last record
     // The table streams through the scalar cache once per chunk and misses it nearly always (every wave of the CU
     // walks a table of its own), and scalar loads return out of order - the only wait is "all of them".  So the
-    // requests go out in batches of AMC_H32_BATCH whole lines and the arithmetic of a batch follows in one piece:
-    // one exposed latency per 4 * AMC_H32_BATCH correspondences, covered by the other waves of the SIMD.
-    constexpr int kB = AMC_H32_BATCH;
+    // requests go out in batches of kB whole lines and the arithmetic of a batch follows in one piece:
+    // one exposed latency per 4 * kB correspondences, covered by the other waves of the SIMD.
+    constexpr int kB = 5;  // 64-byte lines (4 correspondences each) requested together
     const AMC_CONST f16v* tabq = reinterpret_cast<const AMC_CONST f16v*>(tab);
     int k = 0;
     for (; k + 2 * kB <= np; k += 2 * kB) {
@@ -1860,14 +1720,11 @@ __device__ __forceinline__ v2f s32_q_pk(const S32Splat& h, v2f a, v2f b, v2f c, 
     const v2f den = pk_fma(e0, e0, pk_fma(e1, e1, pk_fma(t0, t0, t1 * t1)));
     return pk_fma(cc, cc, pk_fma(h.qR, den, h.qK));
 }
-#ifndef AMC_S32_BATCH
-#define AMC_S32_BATCH 4
-#endif
 // correspondences [k0, k1) (k0 even) against the lane's model: ub += those that are not outliers beyond doubt
 __device__ __forceinline__ void count_lanes_s32(const S32Splat& h, const AMC_CONST v2f* tab, int k0, int k1, int& ub) {
     const v2f big = (v2f){0x1p100f, 0x1p100f};
     v2f nout = (v2f){0.0f, 0.0f};
-    constexpr int kB = AMC_S32_BATCH;
+    constexpr int kB = 4;  // 64-byte lines requested together (see count_lanes_h32)
     const AMC_CONST f16v* tabq = reinterpret_cast<const AMC_CONST f16v*>(tab);
     const int r1 = k1 >> 1;  // records [k0 / 2, r1) hold two counted correspondences each
     int r = k0 >> 1;
@@ -1933,13 +1790,7 @@ __device__ __forceinline__ int count_models_lanes(const double* models, int nmod
         // than to keep 64 lanes streaming for them.  A model that dropped out reports ub + (all it has not seen),
         // an upper bound below thr.
         int ub = 0;
-#ifndef AMC_CNT_SEG
-#define AMC_CNT_SEG 64
-#endif
-#ifndef AMC_CNT_FEW
-#define AMC_CNT_FEW 6
-#endif
-        constexpr int kSeg = AMC_CNT_SEG, kFewAlive = AMC_CNT_FEW;
+        constexpr int kSeg = 64, kFewAlive = 6;
         S32Splat hs;
         if (S32) hs = s32_splat(s32_prepare(mm, max_res, cmax));
         for (int k0 = 0; k0 < M; k0 += kSeg) {
@@ -2040,7 +1891,7 @@ __device__ __forceinline__ void e5_eliminate_quads(double* stg_, int nT, int lan
 }
 
 template <int EST>
-__device__ AMC_SOLVE_CHUNK_INLINE ChunkModels solve_chunk(const Pts P_, const lds_u16* sidx_, int nT_, int lane,
+__device__ __noinline__ ChunkModels solve_chunk(const Pts P_, const lds_u16* sidx_, int nT_, int lane,
                                                 double* models_, const RootScratch rootscr) {
     const unsigned long long c0 = prof_clock();
     const Pts P = uni(P_);
@@ -2171,7 +2022,7 @@ struct CountCtx {  // wave-uniform inputs of count_chunk
     double max_res, cmax;
 };
 template <int EST>
-__device__ AMC_COUNT_CHUNK_INLINE void count_chunk(ChunkModels* io, const CountCtx cc_, int lane) {
+__device__ __forceinline__ void count_chunk(ChunkModels* io, const CountCtx cc_, int lane) {
     const unsigned long long c1 = prof_clock();
     const Pts P = uni(cc_.P);
     const int M = uni(cc_.M), nT = uni(cc_.nT), thr = uni(cc_.thr);
@@ -2234,7 +2085,6 @@ template <int EST, int LOCAL>
 __device__ Report lo_ransac(Wave& w_io, const RansacCfg& cfg, const double* gx, uint32_t gstride, int M, uint8_t* mask) {
     Wave w = w_io;  // by-value copy: the fields live in registers, not behind a pointer
     const int lane = w.lane;
-#if !defined(AMC_TVG_NO_UNIFORM_STATE)
     // ... and, round 6, in SCALAR registers: every field is wave-uniform, but it arrives through memory (the Wave of
     // the kernel's frame), so the compiler kept ~40 vector registers of pointers and positions alive across the chunk
     // loop's calls and spilled them to scratch around each one (scratch traffic is most of what these kernels move
@@ -2247,10 +2097,6 @@ __device__ Report lo_ransac(Wave& w_io, const RansacCfg& cfg, const double* gx, 
     w.rootscr.coef = uni_lds(w.rootscr.coef); w.rootscr.lo = uni_lds(w.rootscr.lo); w.rootscr.hi = uni_lds(w.rootscr.hi);
     w.rootscr.flo = uni_lds(w.rootscr.flo); w.rootscr.src = uni_lds(w.rootscr.src);
     gx = uni_ptr(gx); gstride = uni(gstride); M = uni(M); mask = uni_ptr(mask);
-#define AMC_UNI(x) uni(x)
-#else
-#define AMC_UNI(x) (x)
-#endif
     // the trial limits as SCALAR values: kept in a vector register, max_trials was spilled and - round 6, when the
     // sampler changed the register allocation of the watermark RANSAC - reloaded by the compiler inside the final mask
     // loop's exit block, where EXEC is still zero: report.num_trials came back as whatever the loop had left in the
@@ -2350,9 +2196,9 @@ __device__ Report lo_ransac(Wave& w_io, const RansacCfg& cfg, const double* gx, 
         // (the transposed draws lie over jacA | jacV: the local optimisation's scratch holds nothing between two chunks)
         ss = sample_chunk<kMin>(w.stream, w.stream_len, w.perm, w.sidx, w.rawcnt, reinterpret_cast<lds_u16*>(w.jacA), ss, M, nT, lane,
                                 cfg.force_slow_sampler, w.err);
-        ss.off = AMC_UNI(ss.off);
+        ss.off = uni(ss.off);
 #pragma unroll
-        for (int i = 0; i < 7; ++i) ss.pr[i] = AMC_UNI(ss.pr[i]);
+        for (int i = 0; i < 7; ++i) ss.pr[i] = uni(ss.pr[i]);
         w.soff = ss.off;
         { const unsigned long long tp1 = prof_clock(); w.prof[0] += tp1 - tp0; tp0 = tp1; }
         // ---- 64 minimal problems + the inlier count of every model ---------
@@ -2402,8 +2248,8 @@ __device__ Report lo_ransac(Wave& w_io, const RansacCfg& cfg, const double* gx, 
 #endif
                 if (better(sup, best)) {
                     const unsigned long long tl0 = prof_clock();
-                    best.cnt = AMC_UNI(sup.cnt); best.sum = AMC_UNI(sup.sum);
-                    for (int i = 0; i < 9; ++i) best_model[i] = AMC_UNI(sm[i]);
+                    best.cnt = uni(sup.cnt); best.sum = uni(sup.sum);
+                    for (int i = 0; i < 9; ++i) best_model[i] = uni(sm[i]);
                     best_is_local = false;
                     if (sup.cnt > kMin && sup.cnt >= kLocalMin) {
                         // recursive local optimisation: inliers of the sample model first, then of
@@ -2416,7 +2262,7 @@ __device__ Report lo_ransac(Wave& w_io, const RansacCfg& cfg, const double* gx, 
                             exact_evals += (unsigned long long)M;
                             const lds_f64* lm = lo.jacA;   // the local models, wave-uniform, in LDS
                             const unsigned long long tle = prof_clock();
-                            const int nl = AMC_UNI(local_estimate<LOCAL>(lo, P, K));
+                            const int nl = uni(local_estimate<LOCAL>(lo, P, K));
                             wave_lds_sync();
                             if (lane == 0) {
                                 w.work[wk_residual_slot(LOCAL)] += (unsigned long long)nl * (unsigned long long)M;
@@ -2434,8 +2280,8 @@ __device__ Report lo_ransac(Wave& w_io, const RansacCfg& cfg, const double* gx, 
                                 const Support ls = score<(LOCAL == K_E5 || LOCAL == K_F8 ? K_F7 : LOCAL)>(lmv, P, M, cfg.max_res, lane, best.cnt);
                                 exact_evals += (unsigned long long)M;
                                 if (better(ls, best)) {
-                                    best.cnt = AMC_UNI(ls.cnt); best.sum = AMC_UNI(ls.sum);
-                                    for (int i = 0; i < 9; ++i) best_model[i] = AMC_UNI(lm[9 * q + i]);
+                                    best.cnt = uni(ls.cnt); best.sum = uni(ls.sum);
+                                    for (int i = 0; i < 9; ++i) best_model[i] = uni(lm[9 * q + i]);
                                     best_is_local = true;
                                 }
                             }

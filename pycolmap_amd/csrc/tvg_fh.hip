@@ -2,7 +2,7 @@
 // homography LO-RANSACs, COLMAP's model selection (EstimateCalibrated/UncalibratedTwoViewGeometry) and the watermark
 // test.  Calibrated pairs arrive with their essential-matrix RANSAC already run by tvg_e_kernel (tvg_e.hip): its report,
 // inlier mask and the position it left the sample stream at are read from the pair's TvgEState.  Nothing here needs the
-// 5-point solver's registers, so the kernel is built for AMC_FH_WAVES waves per SIMD.
+// 5-point solver's registers, so the kernel is built for four waves per SIMD (kTvgFhWavesPerSimd, amc_internal.h).
 #include "tvg_core.h"
 
 namespace amc {

@@ -1,4 +1,4 @@
-# A/B timing inside ONE gpurun call (box-to-box clock spread is ~3 %): builds one source file of
+# A/B timing of two revisions on one machine in one run (machine-to-machine clock spread is ~3 %): builds one source file of
 # pycolmap_amd/csrc as of git revision $1 and links it with the current objects into
 # pycolmap_amd/csrc/_obj/libamc_prev.so (select it with AMC_LIB_PATH; tools/diag_run.sh prev base ...).
 #   bash tools/ab_build.sh <rev> [file.hip]      default file: match_mfma.hip

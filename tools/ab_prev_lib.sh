@@ -1,4 +1,4 @@
-# A/B timing inside ONE gpurun call (box-to-box clock spread is ~3 %): builds the WHOLE library as of git revision $1
+# A/B timing of two revisions on one machine in one run (machine-to-machine clock spread is ~3 %): builds the WHOLE library as of git revision $1
 # into pycolmap_amd/csrc/_obj/libamc_prev.so (select it with AMC_LIB_PATH; tools/diag_run.sh prev base ...).
 # Unlike tools/ab_build.sh (one source file against the current objects) this survives changes of the internal
 # interfaces between the two revisions.

@@ -1,6 +1,7 @@
-# A/B builds of the verification kernels inside ONE gpurun call: libamc_<name>.so under pycolmap_amd/csrc/_obj/ with
-# extra -D flags on tvg_e.hip, tvg_fh.hip and amc_verify.hip (the host sizes the launches from the same constants);
-# select with AMC_LIB_PATH.   bash tools/variant_build_tvg.sh fh3 "-DAMC_FH_WAVES=3"
+# A second build of the verification kernels beside the product's: libamc_<name>.so under pycolmap_amd/csrc/_obj/ with
+# extra flags on tvg_e.hip, tvg_fh.hip and amc_verify.hip - the instrumented builds (-DAMC_TVG_PROF, -DAMC_TVG_LODIAG: the
+# counters AMC_TVG_PROFILE=1 prints) or an edited working tree against the built product; select with AMC_LIB_PATH.
+#   bash tools/variant_build_tvg.sh prof "-DAMC_TVG_PROF"
 set -e
 cd "$(dirname "$0")/../pycolmap_amd/csrc"
 NAME=$1; shift

@@ -24,11 +24,18 @@ constexpr int kDim = AMC_DESC_DIM;   // 128 bytes per descriptor
 constexpr int kRowPad = 256;         // = MFMA kernel's column chunk; multiple of every tile
 constexpr int kAcosLutSize = 262145; // d in [0, 512*512]
 
+// The prepared arena stores the eight 16-byte slots of a row XOR-swizzled: slot q of row r lies at q ^ arena_swizzle(r).
+// The scan's lanes read, per ds_read_b128 group of 16, rows that differ in bits 0, 1, 4 and 5 (match_mfma.hip: a lane
+// quarter's rows of a 64-row block are contiguous): bit 0 picks the half of the 64 banks, bits 1, 4, 5 the slot.
+__host__ __device__ __forceinline__ constexpr uint32_t arena_swizzle(uint32_t row) {
+    return ((row >> 1) & 1u) | (((row >> 4) & 3u) << 1);
+}
+
 // Device-side view of one image slot.
 struct ImageDev {
     const uint8_t* raw;    // rows_pad x 128 u8, row-major, zero padded (dot4 kernel)
     const uint8_t* prep;   // rows_pad x 128, bytes ^0x80 (= u8-128 as i8), 16-B slots of row r
-                           // stored at slot (q ^ ((r>>1)&7)) (LDS-bank swizzle), zero rows = 0x80
+                           // stored at slot (q ^ arena_swizzle(r)) (LDS-bank swizzle), zero rows = 0x80
     const int32_t* rs128;  // rows_pad: 128 * sum_k raw[r][k]
     const float* kp;       // kp_rows x 2 float32 keypoints (x, y), or nullptr (guided matching only)
     uint32_t rows;

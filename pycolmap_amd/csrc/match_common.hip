@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void prep_kernel(const uint8_t* __restrict__ r
         uint4 o;
         o.x = v.x ^ 0x80808080u; o.y = v.y ^ 0x80808080u;
         o.z = v.z ^ 0x80808080u; o.w = v.w ^ 0x80808080u;
-        const uint32_t qs = q ^ ((r >> 1) & 7u);
+        const uint32_t qs = q ^ arena_swizzle(r);
         *reinterpret_cast<uint4*>(prep + (size_t)r * kDim + qs * 16) = o;
     }
 #pragma unroll
@@ -685,7 +685,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             i32x4 xf[4];
             {
                 const char* rp = reinterpret_cast<const char*>(X.prep) + (size_t)xrow * kDim;
-                const uint32_t sw = (xrow >> 1) & 7u;
+                const uint32_t sw = arena_swizzle(xrow);
 #pragma unroll
                 for (int sl = 0; sl < 4; ++sl) xf[sl] = *reinterpret_cast<const i32x4*>(rp + (((2 * sl + half) ^ sw) * 16));
             }
@@ -710,7 +710,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 // A operand + C block of tile T (rows T*32 .. +31 < rows_pad: padding rows are zero descriptors)
                 const uint32_t yrow = T * 32 + l31;
                 const char* yp = reinterpret_cast<const char*>(Y.prep) + (size_t)yrow * kDim;
-                const uint32_t ysw = (yrow >> 1) & 7u;
+                const uint32_t ysw = arena_swizzle(yrow);
                 i32x4 yf[4];
 #pragma unroll
                 for (int sl = 0; sl < 4; ++sl) yf[sl] = *reinterpret_cast<const i32x4*>(yp + (((2 * sl + half) ^ ysw) * 16));

@@ -1,5 +1,5 @@
 // match_mfma.hip — the hot kernel: one-way top-2 scan of 128-D u8 descriptor dot products on
-// the int8 matrix cores (v_mfma_i32_32x32x32_i8).  gfx950 only.
+// the int8 matrix cores (v_mfma_i32_16x16x64_i8).  gfx950 only.
 //
 // "One way" = COLMAP's FindBestMatchesOneWayBruteForce: for every row of
 // image X, the best dot product against all rows of image Y (lowest index among ties) and the
@@ -14,28 +14,33 @@
 // by recomputing those 32 dot products, only for rows that can still pass COLMAP's acceptance
 // tests (a larger second only ever rejects).
 //
-// Why this shape (measured on MI355X, tools/ubench_ops.hip, tools/ubench_mix.hip, tools/ubench_ladder.hip):
-//   * every 32-bit min/max/med3/max3/shift/shift-add is HALF rate on gfx950 (4 clk / wave64);
-//   * on one SIMD an int8 MFMA (32 clk) hides only ~6 VALU instructions; each further one costs
-//     ~4.5 clk.  So the epilogue budget is 6 VALU per MFMA = 1.5 per output.
-// A values-only top-2 insertion (v_med3_i32 + v_max3_i32 + v_max_i32 per TWO candidates) is
-// exactly 1.5/output, i.e. VALU-bound.  The scan therefore does less: it reduces each lane's 16
-// outputs of a unit to their maximum (8 x v_max3/v_max) and keeps the top two of those maxima
-// plus the tile of the best, 12 VALU per 16 outputs, which leaves the matrix pipe as
-// the limiter.  The row's exact second-largest value is completed by resolve_index_kernel from
-// the winning tile (see `phase` below).  Everything else is moved off the VALU:
+// Why this shape (measured on MI355X, tools/ubench_ladder.hip, profiles/scan16/):
+//   * the scan is bound by the package power budget; v_mfma_i32_16x16x64_i8 costs a quarter less energy per
+//     MAC than v_mfma_i32_32x32x32_i8, the instruction this kernel used before;
+//   * every 32-bit min/max/med3/max3/shift-or is HALF rate on gfx950 (~4.5 clk / wave64) and a wave has room for
+//     about 14 of them per 8 MFMAs (16 outputs per lane).
+// A values-only top-2 insertion per output does not fit that.  The scan therefore does less: it reduces a
+// lane's 16 outputs of a UNIT to their maximum (8 x v_max3/v_max) and keeps the top two of those maxima plus the
+// unit of the best: 11 VALU per 16 outputs.  The row's exact second-largest value is completed by
+// resolve_index_kernel from the winning tile (see `phase` below).  Everything else is moved off the VALU:
 //   * zero point: the matrix core is signed, the arena holds a' = a - 128 (bytes ^ 0x80) and
 //         sum a*b = sum a'*b' + 128*SX_i + 128*SY_j - 2^21        (SX, SY = byte sums, int32 exact)
 //     The MFMA's A operand is the streamed Y tile and its B operand the resident X tile, so a
-//     lane owns ONE X row and its 16 accumulator registers are 16 different Y rows: the Y term
-//     128*SY_j is per register and rides in as the MFMA's C operand (16 ints per Y tile,
-//     read from LDS); the X term is constant per lane, dropped during the scan and restored
+//     lane owns ONE X row and its accumulator registers are different Y rows: the Y term
+//     128*SY_j is per register and rides in as the MFMA's C operand (four ints per MFMA, one ds_read_b128);
+//     the X term is constant per lane, dropped during the scan and restored
 //     (with the -2^21) when the row is decoded.  acc = v - 128*SX_i + 2^21, full int32 range:
 //     ANY u8 data, any size.
-//   * argmax: values only in the scan; the tile holding the best is tracked with one compare +
-//     select per 16 outputs ("did best change?", strict, so the first tile wins ties).
+//   * argmax: values only in the scan; the unit holding the best rides in the low bits of the value's key.
 //
-// Work items (round 4).  The unit of work is no longer a pair.  Every pair's X side is cut into
+// Units.  v_mfma_i32_16x16x64_i8: lane l supplies row (l & 15) of A and of B, k bytes 16 (l >> 4) .. + 15 of the
+// 64, and owns D rows 4 q + r (q = l >> 4, r = 0..3) of column (l & 15).  Which Y row is fed as A row m is the
+// kernel's choice (each lane picks the LDS address it reads): within a 64-row BLOCK of Y, row m of MFMA tile
+// t = 0..3 is Y row 16 (m >> 2) + 4 t + (m & 3).  Lane quarter q's 16 outputs of a block are then the contiguous
+// rows 16 q .. 16 q + 15 - one unit, inside the 32-row tile 2 block + (q >> 1) - and the C operand of a tile is
+// four consecutive ints.  A block is scanned in two STEPS of two MFMA tiles each (32 rows' worth of fragments).
+//
+// Work items.  Every pair's X side is cut into
 // SEGMENTS of 128 rows; the segments of all pairs that stream the same Y image are packed, eight to
 // an ITEM, by three small kernels (seg_count / seg_scan / seg_fill below) into 64-byte descriptors
 // that carry every pointer a wave needs.  A workgroup pops an item, streams that Y image once
@@ -46,15 +51,14 @@
 //
 // Shape.  One workgroup per item (dynamic queue; items in Y order so co-resident workgroups stream
 // the same image out of L2; the next item's descriptor is fetched while the current one is
-// scanned).  <W, XT> = waves per workgroup x resident 32-row X tiles per wave, W * XT = 32:
-//   <8, 4>  512 threads, a segment per wave, 2 waves per SIMD (256 registers each): the shape that is built
-//   <4, 8>  256 threads, two segments per wave, 1 wave per SIMD (512 registers): half the LDS
-//           fragment traffic per MFMA, the wave's own VALU fills its own MFMA shadows; 0.5-1 % slower in the
-//           kernel and no longer instantiated - the template still describes it
+// scanned): 512 threads, a segment (eight resident 16-row X tiles) per wave, 2 waves per SIMD.  MODE 0 compiles to
+// exactly 256 VGPRs, the most two waves per SIMD allow (MODE 1: 238), without scratch: anything added to the loop's
+// live state will spill - check -Rpass-analysis=kernel-resource-usage after every change.
 // Y streams through LDS in 256-row chunks by direct-to-LDS DMA, three buffers, the pieces of chunk c+2
-// issued one per Y tile of chunk c, one barrier per chunk; the prepared arena is pre-swizzled so the linear DMA image is bank-conflict-free for
-// ds_read_b128.  Each wave software-pipelines: the 4 MFMAs of unit u+1 are interleaved with the
-// 12 VALU of unit u (unit = 32 Y rows x 32 X rows), two accumulator sets.
+// issued one per two steps of chunk c, one barrier per chunk; the prepared arena is pre-swizzled
+// (arena_swizzle, amc_internal.h) so the linear DMA image is bank-conflict-free for
+// ds_read_b128.  Each wave software-pipelines: the 4 MFMAs of (step, X tile) u+1 are interleaved with the
+// VALU of u, two accumulator sets.
 #include <cstdlib>
 
 #include "amc_internal.h"
@@ -62,21 +66,25 @@
 
 namespace amc {
 
-typedef int i32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) const void gvoid_t;
 typedef __attribute__((address_space(3))) void lvoid_t;
 
 constexpr int kBN = 256;                // Y rows per LDS chunk (= kRowPad); 512 measured 2 % slower
-constexpr int kYT = kBN / 32;           // Y tiles per chunk
+constexpr int kYS = kBN / 32;           // 32-row steps per chunk
+constexpr int kUR = 64;                 // Y rows per block: two steps.  The width is built in, not a parameter: the
+                                        // row mapping, arena_swizzle, the six-read fragment schedule of a step, the
+                                        // two-step loop and the epilogue's tile of a lane quarter are those of 64 rows
+constexpr int kUPC = kBN / kUR;         // blocks per chunk
 constexpr int kChunkBytes = kBN * kDim; // 32 KiB
-constexpr int kSegTiles = kSegRows / 32;  // 32-row X tiles per segment
+constexpr int kW = kSegsPerItem;        // waves per workgroup: a segment each
+constexpr int kXT = kSegRows / 16;      // resident 16-row X tiles per wave
 constexpr int kKeyShift = 7, kKeyCarried = 127;
 
 // single LDS object (a second __shared__ object de-pipelines the DMA waits).  THREE chunk buffers: while chunk c is
 // scanned, chunk c+1 has landed (or is landing) and chunk c+2 is being fetched into the buffer chunk c-1 left -
-// so its DMA pieces need not wait for a barrier and are issued one per Y tile instead of all at the chunk
-// boundary, where they stalled the wave's MFMA stream (2.7 % of the scan at two waves per SIMD, 5 % at one).
+// so its DMA pieces need not wait for a barrier and are issued a few steps apart instead of all at the chunk
+// boundary, where they stalled the wave's MFMA stream (2.7 % of the scan).
 constexpr int kNB = 3;
 constexpr int kOffRs = 0;                        // kNB x rs128 chunks (kBN ints each)
 constexpr int kOffQ = kOffRs + kNB * kBN * 4;    // queue slot
@@ -87,52 +95,30 @@ static_assert(kRowPad % kSegRows == 0 && kSegRows % 32 == 0, "segments tile the 
 static_assert(kLdsBytes <= 160 * 1024, "LDS of one CU");
 static_assert(sizeof(SegDesc) == 64, "a descriptor is 16 dwords: one per lane of a quarter wave");
 
-// dword positions of the SegDesc fields (a wave holds its descriptors in ONE register: lane l has dword l)
+// dword positions of the SegDesc fields (a wave holds its descriptor in ONE register: lane l < 16 has dword l)
 enum : int { kDXprep = 0, kDXrs = 2, kDOut = 4, kDList = 6, kDYprep = 8, kDYrs = 10, kDCnt = 12, kDAccword = 13,
              kDYrows = 14 };
 
-// v_max3_i32 pinned by hand (hipcc pattern-matches it only some of the time).
-// These read MFMA results directly and hipcc does not pad hazards for inline asm, so the kernel
-// is structured so that an accumulator is only ever read one full phase (>= 2 MFMA issues)
-// after the MFMAs that produced it were issued; sched_barriers pin that order.
-__device__ __forceinline__ int smax3(int a, int b, int c) {
-    int d;
-    asm volatile("v_max3_i32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
+// The MFMAs and the VALU that reads their results are inline asm: hipcc pattern-matches v_max3 only some of the
+// time, selects the tied form for an MFMA with a C operand (and then copies the C registers into the accumulator
+// first, on the matrix pipe's critical path), and pads dependent asm statements with s_nops it cannot know to be
+// needless.  hipcc does not pad hazards for inline asm either, so the kernel is structured so that an accumulator
+// is only ever read by the VALU after four further MFMAs have issued behind the one that completed it (see `phase`);
+// sched_barriers pin that order.
+// First MFMA of an accumulator: C operand = four of the Y rows' 128*SY, destination = a free accumulator (early
+// clobber).  Operands come from LDS reads (the waitcnt pass tracks asm operands); the result is next read by the
+// dependent MFMA (same destination as C operand: no wait states needed).
+__device__ __forceinline__ void mfma_first(i32x4& d, const i32x4& a, const i32x4& b, const i32x4& c) {
+    asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c));
 }
-__device__ __forceinline__ int smax2(int a, int b) {
-    int d;
-    asm volatile("v_max_i32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-
-// First MFMA of a unit: C operand = the Y tile's 128*SY block, destination = a free accumulator.  Written as
-// inline asm with an early-clobber output: hipcc selects the TIED form for this one (destination = C operand)
-// and then copies the 16 C registers into the accumulator first - 8 v_mov_b64 and their wait states per Y tile,
-// on the matrix pipe's critical path.  Operands come from LDS reads (the waitcnt pass tracks asm operands) and
-// the result is next read by the dependent MFMA behind it (same destination: no wait states needed).
-// BA: the B operand (the resident X fragment) lives in the accumulation half of the register file (AGPRs) - the
-// one-wave-per-SIMD shape keeps its 128 fragment registers there, out of the way of everything the VALU touches
-// (hipcc on its own shuttles accumulators through v_accvgpr_read/write, 32 extra VALU per unit).
-template <bool BA>
-__device__ __forceinline__ void mfma_first(i32x16& d, const i32x4& a, const i32x4& b, const i32x16& c) {
-    if constexpr (BA)
-        asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "a"(b), "v"(c));
-    else
-        asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c));
-}
-// The other three MFMAs of a unit accumulate in place.
-template <bool BA>
-__device__ __forceinline__ void mfma_acc(i32x16& d, const i32x4& a, const i32x4& b) {
-    if constexpr (BA)
-        asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-    else
-        d = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, d, 0, 0, 0);
+// The second MFMA (k bytes 64..127) accumulates in place.
+__device__ __forceinline__ void mfma_acc(i32x4& d, const i32x4& a, const i32x4& b) {
+    asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
 }
 
 struct YFrag {
-    i32x4 f[4];  // 32 Y rows x four 32-deep k-slices (MFMA A operand)
-    i32x16 ci;   // 128*SY_j for this lane's 16 Y rows (MFMA C operand)
+    i32x4 f[2][2];  // one step: two MFMA tiles x two 64-deep k halves (MFMA A operand)
+    i32x4 ci[2];    // 128*SY_j for this lane's four Y rows of either tile (MFMA C operand)
 };
 
 // The previous batch's matches on their way to the host (CopyJob, amc_internal.h).  The runtime's own copy kernel
@@ -141,9 +127,9 @@ struct YFrag {
 // with the scan's stream more often than not.  So the copy rides in the scan's own launch: the first `parts`
 // workgroups to arrive take one part each - 512 lanes with four 16-byte loads in flight per lane saturate PCIe from
 // a handful of workgroups - and then scan like the others; the scan loses parts x 10 ms of one workgroup's time.
-// Compiled as ONE general function of (tid, nthreads) for a workgroup of four or eight waves - the code the scan was
-// measured with.  `used` keeps the compiler from specialising it for its single caller's thread count (which also
-// moves that kernel's register allocation); the assumption states the ranges it may rely on.
+// Compiled as ONE general function of (tid, nthreads).  `used` keeps the compiler from specialising it for its
+// single caller's thread count (which also moves that kernel's register allocation); the assumption states the
+// ranges it may rely on.
 __device__ __noinline__ __attribute__((used)) void copy_part(const uint4* __restrict__ src, uint4* __restrict__ dst,
                                                              unsigned long long b, unsigned long long e, int tid,
                                                              int nthreads) {
@@ -157,23 +143,20 @@ __device__ __noinline__ __attribute__((used)) void copy_part(const uint4* __rest
     for (; i < e; i += st) dst[i] = src[i];
 }
 
-template <int MODE, int W, int XT>
-__global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __restrict__ segs,
-                                                            const uint32_t* __restrict__ nitems_p,
-                                                            uint32_t* __restrict__ queue_head,
-                                                            uint32_t* __restrict__ accmask,
-                                                            const ScanAccept* __restrict__ accept,
-                                                            CopyJob job, uint32_t* __restrict__ copy_head) {
-    constexpr int SPW = XT / kSegTiles;  // segments per wave
-    constexpr bool BA = (W == 4);        // X fragments in AGPRs (one wave per SIMD: 512 registers)
-    static_assert(XT % kSegTiles == 0 && W * SPW == kSegsPerItem, "a workgroup takes one item");
-    static_assert((kChunkBytes / 1024) % W == 0 && kYT % (kChunkBytes / 1024 / W) == 0, "a chunk splits into 1 KiB DMA pieces per wave, dealt evenly over its Y tiles");
+template <int MODE>
+__global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __restrict__ segs,
+                                                             const uint32_t* __restrict__ nitems_p,
+                                                             uint32_t* __restrict__ queue_head,
+                                                             uint32_t* __restrict__ accmask,
+                                                             const ScanAccept* __restrict__ accept,
+                                                             CopyJob job, uint32_t* __restrict__ copy_head) {
+    static_assert((kChunkBytes / 1024) % kW == 0 && kYS % (kChunkBytes / 1024 / kW) == 0, "a chunk splits into 1 KiB DMA pieces per wave, dealt evenly over its steps");
     __shared__ __attribute__((aligned(16))) char smem[kLdsBytes];
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, lh = lane >> 5;
+    const int l15 = lane & 15, lq = lane >> 4;
     volatile uint32_t* s_q = reinterpret_cast<volatile uint32_t*>(smem + kOffQ);
     if constexpr (MODE == 0) {
         if (job.parts) {  // (wave-uniform: a kernel argument)
@@ -183,31 +166,30 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
             const uint32_t part = s_part;
             if (part < job.parts)
                 copy_part(static_cast<const uint4*>(job.src), static_cast<uint4*>(job.dst), job.n16 * part / job.parts,
-                          job.n16 * (part + 1) / job.parts, tid, 64 * W);
+                          job.n16 * (part + 1) / job.parts, tid, 64 * kW);
         }
     }
     const uint32_t nitems = *nitems_p;
     const ScanAccept sa = *accept;  // twelve scalar registers for the whole kernel (re-read per row block it is four dependent scalar-cache round trips per X tile)
 
-    // a wave's SPW descriptors of item q, one dword per lane (lanes 16*SPW.. hold 0)
+    // the wave's descriptor of item q, one dword per lane (lanes 16.. hold 0)
     auto load_desc = [&](uint32_t q) -> int {
         int v = 0;
-        if (q < nitems && lane < 16 * SPW)
-            v = reinterpret_cast<const int*>(segs + (size_t)q * kSegsPerItem + wid * SPW)[lane];
+        if (q < nitems && lane < 16) v = reinterpret_cast<const int*>(segs + (size_t)q * kSegsPerItem + wid)[lane];
         return v;
     };
-    auto dword = [&](int dv, int h, int f) -> int { return __builtin_amdgcn_readlane(dv, 16 * h + f); };
-    auto dptr = [&](int dv, int h, int f) -> const char* {
-        const uint64_t lo = (uint32_t)__builtin_amdgcn_readlane(dv, 16 * h + f);
-        const uint64_t hi = (uint32_t)__builtin_amdgcn_readlane(dv, 16 * h + f + 1);
+    auto dword = [&](int dv, int f) -> int { return __builtin_amdgcn_readlane(dv, f); };
+    auto dptr = [&](int dv, int f) -> const char* {
+        const uint64_t lo = (uint32_t)__builtin_amdgcn_readlane(dv, f);
+        const uint64_t hi = (uint32_t)__builtin_amdgcn_readlane(dv, f + 1);
         return reinterpret_cast<const char*>(lo | (hi << 32));
     };
 
     // chunk c of the Y image (prep / rs128 base pointers) -> LDS buffer `buf`, in 1 KiB pieces dealt to the waves
     // (dest = wave-uniform base + lane*16); a wave owns kPW pieces of a chunk, wave 0 also its rs128 block
-    constexpr int kPW = kChunkBytes / 1024 / W;
+    constexpr int kPW = kChunkBytes / 1024 / kW;
     auto stage_piece = [&](const char* yprep, int c, int buf, int ps) __attribute__((always_inline)) {
-        const int piece = ps * W + wid;
+        const int piece = ps * kW + wid;
         __builtin_amdgcn_global_load_lds((gvoid_t*)(yprep + (size_t)c * kChunkBytes + piece * 1024 + lane * 16),
                                          (lvoid_t*)(smem + kOffB + buf * kChunkBytes + piece * 1024), 16, 0, 0);
     };
@@ -222,73 +204,64 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
         stage_rs(yrs, c, buf);
     };
 
-    // A-operand fragments + C-init block of Y tile `yt` of the chunk in LDS buffer `buf`, as eight 16-byte reads:
-    // parts 0..3 = the C block (needed first), 4..7 = the four k-slices.  The scan spreads them over the phases
-    // of the previous tile, one or two behind each phase's last MFMA, so they never pile up in one MFMA shadow.
-    auto load_y_part = [&](YFrag& y, int buf, int yt, int part) __attribute__((always_inline)) {
-        if (part < 4) {
-            // accumulator register r <-> Y row (r&3) + 8*(r>>2) + 4*lh of the tile
-            const int* rsb = reinterpret_cast<const int*>(smem + kOffRs + buf * kBN * 4) + yt * 32 + 4 * lh;
-            const i32x4 v = *reinterpret_cast<const i32x4*>(rsb + 8 * part);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) y.ci[4 * part + e] = v[e];  // the -2^21 lives in xterm
+    // A-operand fragments + C blocks of step `ys` of the chunk in LDS buffer `buf`, as six 16-byte reads: parts 0, 1 =
+    // the C blocks (needed first), 2..5 = the two tiles' two k halves.  The scan spreads them over the phases of the
+    // previous step, one behind each phase's last MFMA, so they never pile up in one MFMA shadow.
+    // This lane's A row m = l15 of tile t of block b is row b*64 + 16 (m >> 2) + 4 t + (m & 3) of the chunk; its
+    // swizzle does not depend on b and t (arena_swizzle takes row bits 1, 4 and 5).
+    const int yrow_lane = (kUR / 4) * (l15 >> 2) + (l15 & 3);
+    const int ysw_lane = arena_swizzle(yrow_lane);
+    // per-lane byte offsets of the two k halves' slots and of the C block; what a step adds is wave-uniform
+    const int yoff0 = kOffB + yrow_lane * kDim + ((lq ^ ysw_lane) * 16);
+    const int yoff1 = kOffB + yrow_lane * kDim + (((4 + lq) ^ ysw_lane) * 16);
+    const int coff = kOffRs + (kUR / 4) * lq * 4;
+    auto load_y_part = [&](YFrag& y, int buf, int ys, int part) __attribute__((always_inline)) {
+        const int ub = (ys / 2) * kUR, sp = ys % 2;
+        if (part < 2) {
+            // accumulator register r of tile t <-> Y row 16 lq + 4 t + r of the block
+            const int so = buf * kBN * 4 + (ub + 8 * sp) * 4;
+            y.ci[part] = *reinterpret_cast<const i32x4*>(smem + (coff + so) + 16 * part);  // the -2^21 lives in xterm
         } else {
-            const int s = part - 4;
-            const int row = yt * 32 + l31;  // within chunk
-            const int sw = (row >> 1) & 7;
-            const char* cp = smem + kOffB + buf * kChunkBytes + row * kDim;
-            y.f[s] = *reinterpret_cast<const i32x4*>(cp + (((2 * s + lh) ^ sw) * 16));
+            const int tt = (part - 2) >> 1, s = (part - 2) & 1;
+            const int so = buf * kChunkBytes + (ub + 8 * sp) * kDim;  // tile 2 sp of the block
+            y.f[tt][s] = *reinterpret_cast<const i32x4*>(smem + ((s ? yoff1 : yoff0) + so) + tt * 4 * kDim);
         }
     };
-    auto load_y = [&](YFrag& y, int buf, int yt) __attribute__((always_inline)) {
+    auto load_y = [&](YFrag& y, int buf, int ys) __attribute__((always_inline)) {
 #pragma unroll
-        for (int part = 0; part < 8; ++part) load_y_part(y, buf, yt, part);
+        for (int part = 0; part < 6; ++part) load_y_part(y, buf, ys, part);
     };
 
-    // resident X state: B-operand fragments, one (best, second, tile) per lane and X tile
-    i32x4 xf[XT][4];
-    int best[XT], sec[XT], btile[XT], xterm[XT];
+    // resident X state: B-operand fragments, one (best, second, block) per lane and X tile; part = the running
+    // maximum of the unit being scanned
+    i32x4 xf[kXT][2];
+    int best[kXT], sec[kXT], btile[kXT], xterm[kXT], part[kXT];
     auto load_x = [&](int dv) __attribute__((always_inline)) {
+        const int cnt = dword(dv, kDCnt);
+        const char* xprep = dptr(dv, kDXprep);
+        const int* xrs = reinterpret_cast<const int*>(dptr(dv, kDXrs));
 #pragma unroll
-        for (int xt = 0; xt < XT; ++xt) {
-            const int h = xt / kSegTiles;
-            const int kl = (xt % kSegTiles) * 32 + l31;  // row within the segment
-            const int cnt = dword(dv, h, kDCnt);
-            const char* xprep = dptr(dv, h, kDXprep);
-            const int* xrs = reinterpret_cast<const int*>(dptr(dv, h, kDXrs));
+        for (int xt = 0; xt < kXT; ++xt) {
+            const int kl = xt * 16 + l15;  // row within the segment
             int row;
             if (MODE == 0) {
                 row = kl;  // xprep / xrs point at the segment's first row; rows past the image's end are zero padding
             } else {
                 // candidate rows; a segment's tail repeats its last row (results never stored), an empty one reads row 0
-                const uint32_t* list = reinterpret_cast<const uint32_t*>(dptr(dv, h, kDList));
+                const uint32_t* list = reinterpret_cast<const uint32_t*>(dptr(dv, kDList));
                 row = cnt > 0 ? (int)list[min(kl, cnt - 1)] : 0;
             }
             const char* rp = xprep + (size_t)row * kDim;
-            const int sw = (row >> 1) & 7;
+            const int sw = arena_swizzle(row);
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const char* fp = rp + (((2 * s + lh) ^ sw) * 16);
-                if constexpr (BA)
-                    // straight into the accumulation registers; hipcc does not count this load, the
-                    // s_waitcnt vmcnt(0) in front of the scan's first barrier covers it
-                    asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(xf[xt][s]) : "v"(fp) : "memory");
-                else
-                    xf[xt][s] = *reinterpret_cast<const i32x4*>(fp);
-            }
+            for (int s = 0; s < 2; ++s) xf[xt][s] = *reinterpret_cast<const i32x4*>(rp + (((4 * s + lq) ^ sw) * 16));
             // acc = sum a'b' + 128*SY_j = v - (128*SX_i - 2^21)
             xterm[xt] = xrs[row] - (1 << 21);
             // COLMAP's floor best = second = 0  <=>  acc = -xterm
-            best[xt] = ((-xterm[xt]) << kKeyShift) | kKeyCarried;  // a key: value << 7 | tile code (see `insert`)
+            best[xt] = ((-xterm[xt]) << kKeyShift) | kKeyCarried;  // a key: value << 7 | block code (see `insert`)
             sec[xt] = best[xt];
             btile[xt] = -1;
         }
-    };
-    auto any_rows = [&](int dv) -> bool {
-        bool a = false;
-#pragma unroll
-        for (int h = 0; h < SPW; ++h) a = a || dword(dv, h, kDCnt) > 0;
-        return a;
     };
 
     if (tid == 0) *s_q = atomicAdd(queue_head, 1u);
@@ -296,115 +269,106 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
     uint32_t q = *s_q;
     int dv = load_desc(q);
     if (q < nitems) {
-        stage(dptr(dv, 0, kDYprep), dptr(dv, 0, kDYrs), 0, 0);
-        if (dword(dv, 0, kDYrows) > kBN) stage(dptr(dv, 0, kDYprep), dptr(dv, 0, kDYrs), 1, 1);
-        if (any_rows(dv)) load_x(dv);
+        stage(dptr(dv, kDYprep), dptr(dv, kDYrs), 0, 0);
+        if (dword(dv, kDYrows) > kBN) stage(dptr(dv, kDYprep), dptr(dv, kDYrs), 1, 1);
+        if (dword(dv, kDCnt) > 0) load_x(dv);
     }
     __syncthreads();  // everyone has read the slot before it is rewritten
 
     while (q < nitems) {
         // chunks 0 and 1 of this item's Y image are on their way and the X fragments are being loaded (issued by
         // the previous iteration or the prologue)
-        const char* yprep = dptr(dv, 0, kDYprep);  // the same in every descriptor of the item
-        const char* yrs = dptr(dv, 0, kDYrs);
-        const int yrows_item = dword(dv, 0, kDYrows);
+        const char* yprep = dptr(dv, kDYprep);  // the same in every descriptor of the item
+        const char* yrs = dptr(dv, kDYrs);
+        const int yrows_item = dword(dv, kDYrows);
         const int nchunks = (yrows_item + kBN - 1) / kBN;
-        // Tiles of the LAST chunk that hold rows, rounded up to a pair of steps: what follows them in the chunk is the
+        // Steps of the LAST chunk that hold rows, rounded up to a block: what follows them in the chunk is the
         // image's zero padding (rows_pad is a multiple of 256) - a zero row can never become a best nor raise a second,
-        // so its tiles need not be scanned (round 6: an image of 4,000 rows paid for 4,096; n ~ U[2000, 6000]: 2.4 % of
-        // the scan).  An image whose rows fill its last chunk scans all kYT tiles as before.
-        const int last_tiles = (((yrows_item - (nchunks - 1) * kBN) + 31) / 32 + 1) & ~1;
-        const bool active = any_rows(dv);  // wave-uniform
+        // so its blocks need not be scanned (an image of 4,000 rows paid for 4,096; n ~ U[2000, 6000]: 2.4 % of
+        // the scan).  An image whose rows fill its last chunk scans all kYS steps.
+        const int last_steps = (((yrows_item - (nchunks - 1) * kBN) + 31) / 32 + 1) & ~1;
+        const bool active = dword(dv, kDCnt) > 0;  // wave-uniform
         if (tid == 0) *s_q = atomicAdd(queue_head, 1u);  // the next item, behind the loads already in flight
 
-        i32x16 acc[2];
-        auto mfma4 = [&](i32x16& a, const YFrag& y, int xt) __attribute__((always_inline)) {
-            mfma_first<BA>(a, y.f[0], xf[xt][0], y.ci);
-#pragma unroll
-            for (int s = 1; s < 4; ++s) mfma_acc<BA>(a, y.f[s], xf[xt][s]);
-        };
-        // One phase = the 4 MFMAs of the NEXT unit (into `an`) with the 12 VALU of the CURRENT
-        // unit (reading `ac`, completed by the previous phase) spread between them, 4/4/4/-.
-        // Interleaved, the matrix pipe stays fed (15.6 ns per MFMA in tools/ubench_mix.hip);
-        // "4 MFMAs, then the VALU" leaves it idle whenever every wave of the SIMD is in its VALU stretch.
-        //
-        // 12 VALU for 16 outputs: the scan only keeps, per lane, the top two of the per-unit
+        i32x4 acc[2][2];
+        // 11 VALU for 16 outputs: the scan only keeps, per lane, the top two of the per-unit
         // MAXIMA (8 v_max3/v_max for the maximum of the unit's 16 outputs, then one insertion)
-        // and the tile of the best.  The second-largest VALUE of the whole row is either the
+        // and the block of the best.  The second-largest VALUE of the whole row is either the
         // maximum of another unit - which the running `sec` then holds, ties included - or
         // sits inside the winning tile, where resolve_index_kernel recomputes the 32 dot
         // products anyway to find the index: it takes the second of those 32 as well and the
         // row's second is the larger of the two.
-        // Insertion of a unit maximum into a lane's (best, second, tile) state, in place (no copies for the
-        // register allocator to make).
-        // Three instructions: the state holds KEYS, value << 7 | code, code = 126 - (tile mod 64).  The accumulators stay
+        // Insertion of a unit maximum (part[xt], consumed) into a lane's (best, second) state, in place.
+        // Three instructions: the state holds KEYS, value << 7 | code, code = 126 - (block mod 64).  The accumulators stay
         // below 2^24 in magnitude (|sum a'b'| <= 2^21, 128 SY < 2^22), so a key fits 32 bits; a larger value is a
-        // larger key, equal values are ordered first tile first (strict '>' of the reference scan), and the second
-        // largest key carries the second largest value, equal ones included.  Every 64 tiles (and at the end of the
-        // item) `flush` moves the tile of a best found since the last flush to btile and marks the key "carried"
-        // (code 127: it beats equal values of later tiles).  The tile code is wave-uniform: a scalar operand.
-        auto insert = [&](int xt, int m, int code) __attribute__((always_inline)) {
+        // larger key, equal values are ordered first block first (strict '>' of the reference scan), and the second
+        // largest key carries the second largest value, equal ones included.  Every 64 blocks (and at the end of the
+        // item) `flush` moves the block of a best found since the last flush to btile and marks the key "carried"
+        // (code 127: it beats equal values of later blocks).  The block code is wave-uniform: a scalar operand.
+        auto insert = [&](int xt, int code) __attribute__((always_inline)) {
             asm volatile(
                 "v_lshl_or_b32 %2, %2, 7, %3\n\t"
                 "v_med3_i32 %1, %0, %1, %2\n\t"  // sec <= best always: the new second of the maxima
                 "v_max_i32 %0, %0, %2"
-                : "+v"(best[xt]), "+v"(sec[xt]), "+v"(m)
+                : "+v"(best[xt]), "+v"(sec[xt]), "+v"(part[xt])
                 : "s"(code));
         };
-        auto flush = [&](int sb) __attribute__((always_inline)) {  // sb: the 64-tile block that ends here
+        auto flush = [&](int sb) __attribute__((always_inline)) {  // sb: the 64-block group that ends here
 #pragma unroll
-            for (int xt = 0; xt < XT; ++xt) {
+            for (int xt = 0; xt < kXT; ++xt) {
                 const int c = best[xt] & 127;
                 btile[xt] = c != kKeyCarried ? sb * 64 + (126 - c) : btile[xt];
                 best[xt] |= kKeyCarried;
             }
         };
-        // The insertion of a unit's maximum does not touch accumulators, so it is deferred into
-        // the hazard slot of the NEXT phase (between its first two MFMAs): pm / ptile carry the
-        // pending maximum (of X tile xtc - 1) from one phase to the next.
-        int pm = -(1 << 24), ptile = 0;  // a pending "maximum" below every accumulator: its key is below every floor key
-        auto phase = [&](i32x16& an, const YFrag& y, int xtn, const i32x16& ac, int xtc, int tile)
+        // One phase = the 4 MFMAs of the NEXT (step, X tile) into `an` - two tiles x two k halves - with the VALU
+        // of the CURRENT one (reading `ac`, completed by the previous phase) behind them: four max ops that fold
+        // the step's 8 outputs into part[xtc] (the unit's first step starts it, sp == 0), and behind a unit's last
+        // step the insertion of the finished maximum, deferred by one phase (X tile xtc - 1; the last X tile's goes
+        // in with the first phase of the next step).  Interleaved, the matrix pipe stays fed; "the MFMAs, then the
+        // VALU" leaves it idle whenever every wave of the SIMD is in its VALU stretch.
+        // gb: the block this step belongs to, counted from the image's first.
+        auto phase = [&](i32x4 (&an)[2], const YFrag& y, int xtn, const i32x4 (&ac)[2], int xtc, int sp, int gb)
                          __attribute__((always_inline)) {
-            mfma_first<BA>(an, y.f[0], xf[xtn][0], y.ci);
+            mfma_first(an[0], y.f[0][0], xf[xtn][0], y.ci[0]);
+            mfma_first(an[1], y.f[1][0], xf[xtn][0], y.ci[1]);
             __builtin_amdgcn_sched_barrier(0);
-            insert((xtc + XT - 1) % XT, pm, 126 - (ptile & 63));
-            // the last unit of a 64-tile block has just gone in: settle the tiles before the next block reuses the codes
-            if (xtc == 0 && tile != 0 && (tile & 63) == 0) flush((tile >> 6) - 1);
+            if (xtc == 0 ? sp == 0 : sp == 1) {
+                insert((xtc + kXT - 1) % kXT, 126 - ((xtc == 0 ? gb - 1 : gb) & 63));
+                // the last unit of a 64-block group has just gone in: settle the blocks before the next group reuses the codes
+                if (xtc == 0 && gb != 0 && (gb & 63) == 0) flush((gb >> 6) - 1);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            mfma_acc(an[0], y.f[0][1], xf[xtn][1]);
+            mfma_acc(an[1], y.f[1][1], xf[xtn][1]);
             __builtin_amdgcn_sched_barrier(0);
-            mfma_acc<BA>(an, y.f[1], xf[xtn][1]);
-            __builtin_amdgcn_sched_barrier(0);
-            // first read of `ac`: two MFMAs have issued since the one that completed it.  One asm block per
-            // MFMA shadow (hipcc pads dependent asm statements with s_nops it cannot know to be needless)
-            int t0, t1, t2, t3;
-            asm volatile(
-                "v_max3_i32 %0, %4, %5, %6\n\t"
-                "v_max3_i32 %1, %7, %8, %9\n\t"
-                "v_max3_i32 %2, %10, %11, %12\n\t"
-                "v_max3_i32 %3, %13, %14, %15"
-                : "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)
-                : "v"(ac[0]), "v"(ac[1]), "v"(ac[2]), "v"(ac[3]), "v"(ac[4]), "v"(ac[5]), "v"(ac[6]), "v"(ac[7]),
-                  "v"(ac[8]), "v"(ac[9]), "v"(ac[10]), "v"(ac[11]));
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_acc<BA>(an, y.f[2], xf[xtn][2]);
-            __builtin_amdgcn_sched_barrier(0);
-            int m4;
-            asm volatile(
-                "v_max3_i32 %1, %4, %5, %6\n\t"  // m4 = max of outputs 12..14
-                "v_max3_i32 %0, %0, %2, %3\n\t"  // t0 = max(t0, t1, t2)
-                "v_max3_i32 %1, %8, %1, %7\n\t"  // m4 = max(t3, m4, output 15)
-                "v_max_i32 %0, %0, %1"
-                : "+v"(t0), "=&v"(m4)
-                : "v"(t1), "v"(t2), "v"(ac[12]), "v"(ac[13]), "v"(ac[14]), "v"(ac[15]), "v"(t3));
-            pm = t0;
-            ptile = tile;
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_acc<BA>(an, y.f[3], xf[xtn][3]);
+            // `ac` is read here: four MFMAs have issued since the one that completed it.  One asm block (hipcc pads
+            // dependent asm statements with s_nops it cannot know to be needless)
+            int t0, t1;
+            if (sp == 0)
+                asm volatile(
+                    "v_max3_i32 %0, %3, %4, %5\n\t"
+                    "v_max3_i32 %1, %6, %7, %8\n\t"
+                    "v_max3_i32 %0, %0, %9, %10\n\t"
+                    "v_max_i32 %2, %0, %1"
+                    : "=&v"(t0), "=&v"(t1), "=&v"(part[xtc])
+                    : "v"(ac[0][0]), "v"(ac[0][1]), "v"(ac[0][2]), "v"(ac[0][3]), "v"(ac[1][0]), "v"(ac[1][1]),
+                      "v"(ac[1][2]), "v"(ac[1][3]));
+            else
+                asm volatile(
+                    "v_max3_i32 %0, %3, %4, %5\n\t"
+                    "v_max3_i32 %1, %6, %7, %8\n\t"
+                    "v_max3_i32 %0, %0, %9, %10\n\t"
+                    "v_max3_i32 %2, %0, %1, %2"  // the unit's earlier steps folded in
+                    : "=&v"(t0), "=&v"(t1), "+v"(part[xtc])
+                    : "v"(ac[0][0]), "v"(ac[0][1]), "v"(ac[0][2]), "v"(ac[0][3]), "v"(ac[1][0]), "v"(ac[1][1]),
+                      "v"(ac[1][2]), "v"(ac[1][3]));
             __builtin_amdgcn_sched_barrier(0);
         };
 
         // ---- software-pipelined scan over all of Y -----------------------------------
-        // units in order (ytile, xt = 0..XT-1); acc[0] holds even xt, acc[1] odd xt.  Each phase
-        // issues the MFMAs of the NEXT unit, then runs the VALU of the current one.
+        // (step, xt = 0..kXT-1) in order; acc[0] holds even xt, acc[1] odd xt.  Each phase
+        // issues the MFMAs of the NEXT one, then runs the VALU of the current one.
         YFrag y0, y1;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // chunk 0 and this item's X rows landed
         __syncthreads();
@@ -412,25 +376,31 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
         const int dvn = load_desc(qn);  // in flight during the scan
         if (active) {
             load_y(y0, 0, 0);
-            mfma4(acc[0], y0, 0);
+            mfma_first(acc[0][0], y0.f[0][0], xf[0][0], y0.ci[0]);
+            mfma_first(acc[0][1], y0.f[1][0], xf[0][0], y0.ci[1]);
+            mfma_acc(acc[0][0], y0.f[0][1], xf[0][1]);
+            mfma_acc(acc[0][1], y0.f[1][1], xf[0][1]);
+            // the first phase inserts a pending maximum: one below every accumulator, its key is below every floor key
+            part[kXT - 1] = -(1 << 24);
             __builtin_amdgcn_sched_barrier(0);
         }
         // The sched_barriers pin the interleaving.  An accumulator is read (by inline asm, which
-        // hipcc does not hazard-check) only after TWO further MFMAs have issued behind the one
-        // that completed it - the matrix pipe runs MFMAs in order, 32 clk each, so the value
-        // has been written back for well over the 11 wait states an 8-pass MFMA needs.
-        // one step = one Y tile held in `yc`; prefetches the next tile into `yn`
+        // hipcc does not hazard-check) only after FOUR further MFMAs have issued behind the one
+        // that completed it - the matrix pipe runs MFMAs in order, 16 clk each (4 passes), so two of them
+        // have run to their end since: well over the 7 wait states a 4-pass MFMA's result needs before a VALU read
+        // (two further MFMAs would do; the rule the 8-pass instruction needed, 11 states, held with two as well).
+        // one step = 32 rows' worth of Y held in `yc`; prefetches the next step into `yn`
         // cb / nb: LDS buffers of chunk c and c + 1 (c % 3, (c + 1) % 3)
-        auto step = [&](YFrag& yc, YFrag& yn, int c, int cb, int nb, int yt, bool even) __attribute__((always_inline)) {
-            const bool lastt = (yt == kYT - 1);
+        auto step = [&](YFrag& yc, YFrag& yn, int c, int cb, int nb, int ys, int sp) __attribute__((always_inline)) {
+            const bool lastt = (ys == kYS - 1);
             const bool cross = lastt && (c + 1 < nchunks);
             const bool fetch = c + 2 < nchunks;  // chunk c + 2 goes to the buffer chunk c - 1 left: (c + 2) % 3
             if (fetch) {
                 const int fb = cb == 0 ? 2 : cb - 1;
-                constexpr int kEvery = kYT / kPW;  // a piece every tile (one wave per SIMD) or every other tile
-                if (kEvery == 1) stage_piece(yprep, c + 2, fb, yt);
-                else if (even) stage_piece(yprep, c + 2, fb, yt / 2);
-                if (yt == 0) stage_rs(yrs, c + 2, fb);
+                constexpr int kEvery = kYS / kPW;  // a piece every other step
+                static_assert(kEvery == 2, "a DMA piece per block, behind its first step");
+                if (sp == 0) stage_piece(yprep, c + 2, fb, ys / kEvery);
+                if (ys == 0) stage_rs(yrs, c + 2, fb);
             }
             if (cross) {
                 // chunk c + 1 must have landed: everything but this chunk's own kPW (+ 1) pieces of chunk c + 2
@@ -442,20 +412,18 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
                 asm volatile("s_barrier" ::: "memory");
             }
             if (active) {
-                // very last tile: re-read itself (result unused) to stay branch-free
+                // very last step: re-read itself (result unused) to stay branch-free
                 const int nbuf = cross ? nb : cb;
-                const int nyt = lastt ? (cross ? 0 : yt) : yt + 1;
-                const int tile = c * kYT + yt;
-                constexpr int RPP = 16 / XT;  // reads behind each phase of the step's first half
+                const int nys = lastt ? (cross ? 0 : ys) : ys + 1;
+                const int gb = c * kUPC + ys / 2;
 #pragma unroll
-                for (int xt = 0; xt < XT; ++xt) {
-                    if (xt + 1 < XT)
-                        phase(acc[(xt + 1) & 1], yc, xt + 1, acc[xt & 1], xt, tile);
+                for (int xt = 0; xt < kXT; ++xt) {
+                    if (xt + 1 < kXT)
+                        phase(acc[(xt + 1) & 1], yc, xt + 1, acc[xt & 1], xt, sp, gb);
                     else
-                        phase(acc[0], yn, 0, acc[xt & 1], xt, tile);
-                    if (xt < XT / 2) {
-#pragma unroll
-                        for (int r = 0; r < RPP; ++r) load_y_part(yn, nbuf, nyt, xt * RPP + r);
+                        phase(acc[0], yn, 0, acc[xt & 1], xt, sp, gb);
+                    if (xt < 6) {
+                        load_y_part(yn, nbuf, nys, xt);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
@@ -463,60 +431,65 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
         };
         for (int c = 0, cb = 0; c < nchunks; ++c) {
             const int nb = cb == 2 ? 0 : cb + 1;
-            const int yend = (c == nchunks - 1) ? last_tiles : kYT;
+            const int yend = (c == nchunks - 1) ? last_steps : kYS;
 #pragma unroll 1
-            for (int yt = 0; yt < yend; yt += 2) {
-                step(y0, y1, c, cb, nb, yt, true);
-                step(y1, y0, c, cb, nb, yt + 1, false);
+            for (int ys = 0; ys < yend; ys += 2) {
+                step(y0, y1, c, cb, nb, ys, 0);
+                step(y1, y0, c, cb, nb, ys + 1, 1);
             }
             cb = nb;
         }
         if (active) {
-            insert(XT - 1, pm, 126 - (ptile & 63));  // the last unit's maximum is still pending
-            flush(ptile >> 6);
+            const int lastb = (nchunks - 1) * kUPC + last_steps / 2 - 1;
+            insert(kXT - 1, 126 - (lastb & 63));  // the last unit's maximum is still pending
+            flush(lastb >> 6);
 #pragma unroll
-            for (int xt = 0; xt < XT; ++xt) {  // keys -> values
+            for (int xt = 0; xt < kXT; ++xt) {  // keys -> values
                 best[xt] >>= kKeyShift;
                 sec[xt] >>= kKeyShift;
             }
         }
-        __syncthreads();  // everyone is done with both LDS chunk buffers (and has read the queue slot)
+        __syncthreads();  // everyone is done with the LDS chunk buffers (and has read the queue slot)
 
         // ---- item done.  Start the next one's loads, then decode and store this one under them ----
-        int eb[XT], es[XT], et[XT], ex[XT];
+        int eb[kXT], es[kXT], et[kXT], ex[kXT];
 #pragma unroll
-        for (int xt = 0; xt < XT; ++xt) {
-            // (asm: hipcc otherwise sinks these copies into the scan loop, 3 x XT moves per Y tile)
+        for (int xt = 0; xt < kXT; ++xt) {
+            // (asm: hipcc otherwise sinks these copies into the scan loop, 3 x kXT moves per step)
             asm volatile("v_mov_b32 %0, %1" : "=v"(eb[xt]) : "v"(best[xt]));
             asm volatile("v_mov_b32 %0, %1" : "=v"(es[xt]) : "v"(sec[xt]));
             asm volatile("v_mov_b32 %0, %1" : "=v"(et[xt]) : "v"(btile[xt]));
             ex[xt] = xterm[xt];
         }
         if (qn < nitems) {
-            stage(dptr(dvn, 0, kDYprep), dptr(dvn, 0, kDYrs), 0, 0);
-            if (dword(dvn, 0, kDYrows) > kBN) stage(dptr(dvn, 0, kDYprep), dptr(dvn, 0, kDYrs), 1, 1);
-            if (any_rows(dvn)) load_x(dvn);
+            stage(dptr(dvn, kDYprep), dptr(dvn, kDYrs), 0, 0);
+            if (dword(dvn, kDYrows) > kBN) stage(dptr(dvn, kDYprep), dptr(dvn, kDYrs), 1, 1);
+            if (dword(dvn, kDCnt) > 0) load_x(dvn);
         }
         if (active) {
+            const int cnt = dword(dv, kDCnt);
+            uint32_t bits_lo = 0;
 #pragma unroll
-            for (int xt = 0; xt < XT; ++xt) {
-                const int h = xt / kSegTiles;
-                const int kl = (xt % kSegTiles) * 32 + l31;
-                const int cnt = dword(dv, h, kDCnt);
-                // merge the two lane halves (they saw different Y rows of every tile)
-                const int ob = __shfl_xor(eb[xt], 32);
-                const int os = __shfl_xor(es[xt], 32);
-                const int ot = __shfl_xor(et[xt], 32);
-                int b = eb[xt], s = es[xt], t = et[xt];
-                const bool ow = (ob > b) || (ob == b && (unsigned)ot < (unsigned)t);
-                s = max(max(s, os), ow ? b : ob);
-                t = ow ? ot : t;
-                b = ow ? ob : b;
+            for (int xt = 0; xt < kXT; ++xt) {
+                const int kl = xt * 16 + l15;
+                // merge the four lane quarters (they saw different Y rows of every block): equal values keep the
+                // lower tile.  A lane's tile: its block's first or second, by the quarter (-1 while nothing beat the floor)
+                int b = eb[xt], s = es[xt], t = et[xt] < 0 ? -1 : et[xt] * 2 + (lq >> 1);
+#pragma unroll
+                for (int m = 16; m <= 32; m <<= 1) {
+                    const int ob = __shfl_xor(b, m);
+                    const int os = __shfl_xor(s, m);
+                    const int ot = __shfl_xor(t, m);
+                    const bool ow = (ob > b) || (ob == b && (unsigned)ot < (unsigned)t);
+                    s = max(max(s, os), ow ? b : ob);
+                    t = ow ? ot : t;
+                    b = ow ? ob : b;
+                }
                 bool acc_bit = false;
-                if (lh == 0 && kl < cnt) {
-                    Top2* out = reinterpret_cast<Top2*>(const_cast<char*>(dptr(dv, h, kDOut)));
+                if (lq == 0 && kl < cnt) {
+                    Top2* out = reinterpret_cast<Top2*>(const_cast<char*>(dptr(dv, kDOut)));
                     int row = kl;  // MODE 0: `out` points at the segment's first row
-                    if (MODE == 1) row = (int)reinterpret_cast<const uint32_t*>(dptr(dv, h, kDList))[kl];
+                    if (MODE == 1) row = (int)reinterpret_cast<const uint32_t*>(dptr(dv, kDList))[kl];
                     Top2 o;
                     o.best_v = (uint32_t)(b + ex[xt]);
                     o.best_idx = o.best_v ? (uint32_t)t : 0xFFFFFFFFu;  // TILE of the best
@@ -527,9 +500,13 @@ __global__ __launch_bounds__(64 * W) void match_mfma_kernel(const SegDesc* __res
                     // (scan_accept.h: thresholds instead of acos; a superset of what the exact tests keep)
                     if (MODE == 0) acc_bit = scan_may_accept(sa, o.best_v, o.second_v);
                 }
-                if (MODE == 0 && cnt > 0) {  // accept bits of the 32 rows of this X tile (lanes 0..31)
+                if (MODE == 0) {  // accept bits of 32 rows = two X tiles (lanes 0..15 of each)
                     const uint32_t bits = (uint32_t)__ballot(acc_bit);
-                    if (lane == 0) accmask[(uint32_t)dword(dv, h, kDAccword) + (xt % kSegTiles)] = bits;
+                    if (xt & 1) {
+                        if (lane == 0) accmask[(uint32_t)dword(dv, kDAccword) + (xt >> 1)] = bits_lo | (bits << 16);
+                    } else {
+                        bits_lo = bits;
+                    }
                 }
             }
         }
@@ -727,12 +704,11 @@ hipError_t launch_match_mfma(int mode, const SegDesc* segs, const uint32_t* nite
     const uint32_t grid = max_items < (uint32_t)cus ? max_items : (uint32_t)cus;
     if (job.parts > grid) job.parts = grid;  // every part needs a workgroup
     if ((e = memset_async(queue_head, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
-    constexpr int kW = 8, kXT = 4;  // eight waves x four X tiles (see "Shape" at the top)
     if (mode == 0)
-        hipLaunchKernelGGL((match_mfma_kernel<0, kW, kXT>), dim3(grid), dim3(64 * kW), 0, s, segs, nitems_dev, queue_head,
+        hipLaunchKernelGGL((match_mfma_kernel<0>), dim3(grid), dim3(64 * kW), 0, s, segs, nitems_dev, queue_head,
                            accmask, accept_dev, job, copy_head);
     else
-        hipLaunchKernelGGL((match_mfma_kernel<1, kW, kXT>), dim3(grid), dim3(64 * kW), 0, s, segs, nitems_dev, queue_head,
+        hipLaunchKernelGGL((match_mfma_kernel<1>), dim3(grid), dim3(64 * kW), 0, s, segs, nitems_dev, queue_head,
                            accmask, accept_dev, job, copy_head);
     return hipGetLastError();
 }

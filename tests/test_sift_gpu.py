@@ -1,6 +1,7 @@
 """The SIFT extractor on the GPU (libamc.so's amc_sift_extract, pycolmap_amd.Sift) against its CPU reference
 (tests/sift_ref/sift_ref.cc): keypoint float bits and descriptor bytes identical, for seeded textured, noise, blob and
-rendered images, every option the extractor reads, odd and tiny sizes, batches and repeated runs."""
+rendered images, every option the extractor reads, odd and tiny sizes, the kernels' tile edges, batches and repeated
+runs."""
 import numpy as np
 import pytest
 
@@ -67,6 +68,62 @@ def test_tiny_and_odd_sizes(amc_ctx, shape):
     img = si.noise(11, *shape)
     got, _ = amc_ctx.sift_extract(img)
     assert_same(got, ref.extract(img), str(shape))
+
+
+# The kernels' tile edges, at first_octave = 0 so that the octave has exactly these sizes: the 64-pixel strip of k_vblur
+# (63 .. 65), the 256-pixel segment of k_hblur and the 256-pixel chunk of k_detect over pixels 1 .. w - 2 (255 .. 259),
+# two segments and one pixel (513); the 16-row tile (15 .. 18), three tiles (33), and the smallest octave that is
+# processed (8, 9: deviation S3).  Every width once, every height once.
+TILE_EDGE_SHAPES = [(15, 63), (16, 64), (17, 65), (18, 255), (33, 256), (8, 257), (9, 258), (15, 259), (16, 513)]
+
+
+@pytest.mark.parametrize("shape", TILE_EDGE_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_tile_edge_sizes_bit_exact(amc_ctx, shape):
+    img = si.textured(60, *shape)
+    got, _ = amc_ctx.sift_extract(img, first_octave=0)
+    want = ref.extract(img, first_octave=0)
+    assert_same(got, want, str(shape))
+    assert len(want[0]) > 0
+    # the same octave sizes reached through the doubling and through decimation
+    half = np.ascontiguousarray(img[:(shape[0] + 1) // 2, :(shape[1] + 1) // 2])
+    assert_same(amc_ctx.sift_extract(half, first_octave=-1, num_octaves=1)[0],
+                ref.extract(half, first_octave=-1, num_octaves=1), f"{half.shape} doubled")
+
+
+@pytest.mark.parametrize("opts", [
+    dict(octave_resolution=1),              # the widest blur aprons: 45 taps each side
+    dict(octave_resolution=5),
+    dict(num_octaves=1),
+    dict(num_octaves=8),                    # more than fit: the octaves below 8 pixels are not processed
+    dict(first_octave=2),
+    dict(first_octave=1, octave_resolution=1, num_octaves=2),
+], ids=str)
+def test_octave_options_bit_exact(amc_ctx, opts):
+    img = si.textured(61, 150, 200)
+    got, _ = amc_ctx.sift_extract(img, **opts)
+    want = ref.extract(img, **opts)
+    assert_same(got, want, str(opts))
+    assert len(want[0]) > 0
+
+
+@pytest.mark.parametrize("name,opts", [
+    ("noise", dict(peak_threshold=0.0)),
+    # white noise has few extrema across scale (its DoG shrinks with sigma); a texture with no contrast or edge test
+    # keeps nearly every one: many hits per 256-pixel detection chunk, rows with hits in both chunks, keypoints whose
+    # windows reach every border
+    ("textured", dict(peak_threshold=0.0, edge_threshold=1e6, max_num_features=0)),
+    ("textured", dict(peak_threshold=0.0, edge_threshold=1e6, max_num_features=0, octave_resolution=5)),
+], ids=["noise_tp0", "textured_keep_all", "textured_keep_all_S5"])
+def test_zero_peak_threshold_bit_exact(amc_ctx, name, opts):
+    img = si.noise(62, 64, 300) if name == "noise" else si.textured(63, 64, 300)
+    got, _ = amc_ctx.sift_extract(img, first_octave=0, **opts)
+    want = ref.extract(img, first_octave=0, **opts)
+    assert_same(got, want, f"{name} {opts}")
+    kp = want[0]
+    assert len(kp) > 0
+    if name == "textured":
+        assert len(kp) > 150 and (kp[:, 0] < 256).sum() > 50 and (kp[:, 0] > 258).sum() > 10
+        assert kp[:, 0].min() < 8 and kp[:, 0].max() > 292 and kp[:, 1].min() < 8 and kp[:, 1].max() > 56
 
 
 def test_constant_image_has_no_features(amc_ctx):

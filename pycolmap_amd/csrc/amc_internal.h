@@ -25,10 +25,10 @@ constexpr int kRowPad = 256;         // = MFMA kernel's column chunk; multiple o
 constexpr int kAcosLutSize = 262145; // d in [0, 512*512]
 
 // The prepared arena stores the eight 16-byte slots of a row XOR-swizzled: slot q of row r lies at q ^ arena_swizzle(r).
-// The scan's lanes read, per ds_read_b128 group of 16, rows that differ in bits 0, 1, 4 and 5 (match_mfma.hip: a lane
-// quarter's rows of a 64-row block are contiguous): bit 0 picks the half of the 64 banks, bits 1, 4, 5 the slot.
+// The scan's lanes read, per ds_read_b128 group of 16, rows that differ in bits 0, 1, 5 and 6 (match_mfma.hip: a lane
+// quarter's rows of a 128-row block are contiguous): bit 0 picks the half of the 64 banks, bits 1, 5, 6 the slot.
 __host__ __device__ __forceinline__ constexpr uint32_t arena_swizzle(uint32_t row) {
-    return ((row >> 1) & 1u) | (((row >> 4) & 3u) << 1);
+    return ((row >> 1) & 1u) | (((row >> 5) & 3u) << 1);
 }
 
 // Device-side view of one image slot.

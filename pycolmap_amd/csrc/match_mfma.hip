@@ -9,19 +9,20 @@
 //           columns some accepted row points at (select_candidates_kernel); the cross check
 //           never looks at any other column, so results equal COLMAP's full transposed scan.
 // The kernel reports the best VALUE, the 32-row TILE of Y that holds it, and the largest value
-// OUTSIDE the best's 16-output unit (a lower bound of the second); resolve_index_kernel
+// OUTSIDE the best's unit, which is that tile (a lower bound of the second); resolve_index_kernel
 // (match_common.hip) turns the tile into the exact lowest index and completes the second value
 // by recomputing those 32 dot products, only for rows that can still pass COLMAP's acceptance
 // tests (a larger second only ever rejects).
 //
-// Why this shape (measured on MI355X, tools/ubench_ladder.hip, profiles/scan16/):
+// Why this shape (measured on MI355X, tools/ubench_ladder.hip, profiles/scan16/, profiles/scan128/):
 //   * the scan is bound by the package power budget; v_mfma_i32_16x16x64_i8 costs a quarter less energy per
 //     MAC than v_mfma_i32_32x32x32_i8, the instruction this kernel used before;
 //   * every 32-bit min/max/med3/max3/shift-or is HALF rate on gfx950 (~4.5 clk / wave64) and a wave has room for
-//     about 14 of them per 8 MFMAs (16 outputs per lane).
+//     about 14 of them per 8 MFMAs (16 outputs per lane); at ~2.0 GHz the loop is limited by vector issue (an MFMA
+//     of this shape holds the SIMD's vector issue for 8 of its 16 clocks), so every VALU instruction saved counts.
 // A values-only top-2 insertion per output does not fit that.  The scan therefore does less: it reduces a
-// lane's 16 outputs of a UNIT to their maximum (8 x v_max3/v_max) and keeps the top two of those maxima plus the
-// unit of the best: 11 VALU per 16 outputs.  The row's exact second-largest value is completed by
+// lane's 32 outputs of a UNIT to their maximum (16 x v_max3/v_max) and keeps the top two of those maxima plus the
+// unit of the best: 19 VALU per 32 outputs = 9.5 per 16.  The row's exact second-largest value is completed by
 // resolve_index_kernel from the winning tile (see `phase` below).  Everything else is moved off the VALU:
 //   * zero point: the matrix core is signed, the arena holds a' = a - 128 (bytes ^ 0x80) and
 //         sum a*b = sum a'*b' + 128*SX_i + 128*SY_j - 2^21        (SX, SY = byte sums, int32 exact)
@@ -35,10 +36,11 @@
 //
 // Units.  v_mfma_i32_16x16x64_i8: lane l supplies row (l & 15) of A and of B, k bytes 16 (l >> 4) .. + 15 of the
 // 64, and owns D rows 4 q + r (q = l >> 4, r = 0..3) of column (l & 15).  Which Y row is fed as A row m is the
-// kernel's choice (each lane picks the LDS address it reads): within a 64-row BLOCK of Y, row m of MFMA tile
-// t = 0..3 is Y row 16 (m >> 2) + 4 t + (m & 3).  Lane quarter q's 16 outputs of a block are then the contiguous
-// rows 16 q .. 16 q + 15 - one unit, inside the 32-row tile 2 block + (q >> 1) - and the C operand of a tile is
-// four consecutive ints.  A block is scanned in two STEPS of two MFMA tiles each (32 rows' worth of fragments).
+// kernel's choice (each lane picks the LDS address it reads): within a 128-row BLOCK of Y, row m of MFMA tile
+// t = 0..7 is Y row 32 (m >> 2) + 4 t + (m & 3).  Lane quarter q's 32 outputs of a block are then the contiguous
+// rows 32 q .. 32 q + 31 - one unit, exactly the 32-row tile 4 block + q that resolve_index recomputes - and the C
+// operand of a tile is four consecutive ints.  A block is scanned in four STEPS of two MFMA tiles each (32 rows'
+// worth of fragments); the scan of an image's last chunk ends at the last block that holds rows.
 //
 // Work items.  Every pair's X side is cut into
 // SEGMENTS of 128 rows; the segments of all pairs that stream the same Y image are packed, eight to
@@ -72,9 +74,8 @@ typedef __attribute__((address_space(3))) void lvoid_t;
 
 constexpr int kBN = 256;                // Y rows per LDS chunk (= kRowPad); 512 measured 2 % slower
 constexpr int kYS = kBN / 32;           // 32-row steps per chunk
-constexpr int kUR = 64;                 // Y rows per block: two steps.  The width is built in, not a parameter: the
-                                        // row mapping, arena_swizzle, the six-read fragment schedule of a step, the
-                                        // two-step loop and the epilogue's tile of a lane quarter are those of 64 rows
+constexpr int kUR = 128;                // Y rows per block; arena_swizzle (amc_internal.h) is made for this width
+constexpr int kSPB = kUR / 32;          // steps per block
 constexpr int kUPC = kBN / kUR;         // blocks per chunk
 constexpr int kChunkBytes = kBN * kDim; // 32 KiB
 constexpr int kW = kSegsPerItem;        // waves per workgroup: a segment each
@@ -91,6 +92,7 @@ constexpr int kOffQ = kOffRs + kNB * kBN * 4;    // queue slot
 constexpr int kOffB = kOffQ + 16;                // kNB x descriptor chunks
 constexpr int kLdsBytes = kOffB + kNB * kChunkBytes;
 static_assert(kBN == kRowPad, "a chunk is the row padding unit");
+static_assert(kUR == 128 && kSPB == 4, "a lane quarter's rows of a block are one 32-row tile; the loop body is one block");
 static_assert(kRowPad % kSegRows == 0 && kSegRows % 32 == 0, "segments tile the padded rows");
 static_assert(kLdsBytes <= 160 * 1024, "LDS of one CU");
 static_assert(sizeof(SegDesc) == 64, "a descriptor is 16 dwords: one per lane of a quarter wave");
@@ -120,6 +122,20 @@ struct YFrag {
     i32x4 f[2][2];  // one step: two MFMA tiles x two 64-deep k halves (MFMA A operand)
     i32x4 ci[2];    // 128*SY_j for this lane's four Y rows of either tile (MFMA C operand)
 };
+
+#ifdef AMC_SCAN_STAMPS
+// Diagnostic build only (tools/scan_stamps.hip includes this file with the macro; libamc.so is compiled without it and
+// holds none of this): s_memtime stamps around the places where a wave's MFMA stream stops, summed per wave in scalar
+// registers and stored - running sums, lane 0 - behind every item.  Per (MODE, workgroup, wave) eight dwords, over the
+// items that had a successor in the same workgroup:
+//   [0] clocks from arriving at a chunk crossing's s_waitcnt to leaving its s_barrier   [1] clocks from the
+//   __syncthreads() that ends an item's scan to the first MFMA of the next item   [2] clocks from an item's first MFMA
+//   to the next item's   [3] such items   [4] those of them this wave had rows in
+// and for the workgroup's last item: [5] as [0]   [6] first MFMA to the end of the epilogue   [7] 1
+constexpr int kStampMaxWG = 1024;
+__device__ uint32_t g_scan_stamps[2 * kStampMaxWG * kSegsPerItem * 8];
+#define AMC_STAMP() ((uint32_t)__builtin_amdgcn_s_memtime())
+#endif
 
 // The previous batch's matches on their way to the host (CopyJob, amc_internal.h).  The runtime's own copy kernel
 // covers the buffer with its grid and takes every CU while PCIe moves 400 MB (10 ms, and the scan behind it waits:
@@ -207,8 +223,8 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
     // A-operand fragments + C blocks of step `ys` of the chunk in LDS buffer `buf`, as six 16-byte reads: parts 0, 1 =
     // the C blocks (needed first), 2..5 = the two tiles' two k halves.  The scan spreads them over the phases of the
     // previous step, one behind each phase's last MFMA, so they never pile up in one MFMA shadow.
-    // This lane's A row m = l15 of tile t of block b is row b*64 + 16 (m >> 2) + 4 t + (m & 3) of the chunk; its
-    // swizzle does not depend on b and t (arena_swizzle takes row bits 1, 4 and 5).
+    // This lane's A row m = l15 of tile t of block b is row b*128 + 32 (m >> 2) + 4 t + (m & 3) of the chunk; its
+    // swizzle does not depend on b and t (arena_swizzle takes row bits 1, 5 and 6).
     const int yrow_lane = (kUR / 4) * (l15 >> 2) + (l15 & 3);
     const int ysw_lane = arena_swizzle(yrow_lane);
     // per-lane byte offsets of the two k halves' slots and of the C block; what a step adds is wave-uniform
@@ -216,9 +232,9 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
     const int yoff1 = kOffB + yrow_lane * kDim + (((4 + lq) ^ ysw_lane) * 16);
     const int coff = kOffRs + (kUR / 4) * lq * 4;
     auto load_y_part = [&](YFrag& y, int buf, int ys, int part) __attribute__((always_inline)) {
-        const int ub = (ys / 2) * kUR, sp = ys % 2;
+        const int ub = (ys / kSPB) * kUR, sp = ys % kSPB;
         if (part < 2) {
-            // accumulator register r of tile t <-> Y row 16 lq + 4 t + r of the block
+            // accumulator register r of tile t <-> Y row 32 lq + 4 t + r of the block
             const int so = buf * kBN * 4 + (ub + 8 * sp) * 4;
             y.ci[part] = *reinterpret_cast<const i32x4*>(smem + (coff + so) + 16 * part);  // the -2^21 lives in xterm
         } else {
@@ -264,6 +280,11 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
         }
     };
 
+#ifdef AMC_SCAN_STAMPS
+    uint32_t st_a = 0, st_first = 0, st_end = 0, st_sum[5] = {0, 0, 0, 0, 0};
+    bool st_prev = false, st_prev_active = false;
+    uint32_t* const st_slot = g_scan_stamps + ((size_t)(MODE * kStampMaxWG + min((int)blockIdx.x, kStampMaxWG - 1)) * kW + wid) * 8;
+#endif
     if (tid == 0) *s_q = atomicAdd(queue_head, 1u);
     __syncthreads();
     uint32_t q = *s_q;
@@ -285,21 +306,22 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
         // Steps of the LAST chunk that hold rows, rounded up to a block: what follows them in the chunk is the
         // image's zero padding (rows_pad is a multiple of 256) - a zero row can never become a best nor raise a second,
         // so its blocks need not be scanned (an image of 4,000 rows paid for 4,096; n ~ U[2000, 6000]: 2.4 % of
-        // the scan).  An image whose rows fill its last chunk scans all kYS steps.
-        const int last_steps = (((yrows_item - (nchunks - 1) * kBN) + 31) / 32 + 1) & ~1;
+        // the scan; ending at a 128-row block leaves 64 padded rows per image on average where a chunk leaves 128).  An image whose rows fill its last chunk scans
+        // all kYS steps.
+        const int last_steps = (((yrows_item - (nchunks - 1) * kBN) + 31) / 32 + kSPB - 1) & ~(kSPB - 1);
         const bool active = dword(dv, kDCnt) > 0;  // wave-uniform
         if (tid == 0) *s_q = atomicAdd(queue_head, 1u);  // the next item, behind the loads already in flight
 
         i32x4 acc[2][2];
-        // 11 VALU for 16 outputs: the scan only keeps, per lane, the top two of the per-unit
-        // MAXIMA (8 v_max3/v_max for the maximum of the unit's 16 outputs, then one insertion)
+        // 19 VALU for 32 outputs: the scan only keeps, per lane, the top two of the per-unit
+        // MAXIMA (16 v_max3/v_max for the maximum of the unit's 32 outputs, then one insertion)
         // and the block of the best.  The second-largest VALUE of the whole row is either the
         // maximum of another unit - which the running `sec` then holds, ties included - or
         // sits inside the winning tile, where resolve_index_kernel recomputes the 32 dot
         // products anyway to find the index: it takes the second of those 32 as well and the
         // row's second is the larger of the two.
         // Insertion of a unit maximum (part[xt], consumed) into a lane's (best, second) state, in place.
-        // Three instructions: the state holds KEYS, value << 7 | code, code = 126 - (block mod 64).  The accumulators stay
+        // Three instructions: the state holds KEYS, value << 7 | code, code = 126 - (block mod 64) (64 blocks = 8,192 rows).  The accumulators stay
         // below 2^24 in magnitude (|sum a'b'| <= 2^21, 128 SY < 2^22), so a key fits 32 bits; a larger value is a
         // larger key, equal values are ordered first block first (strict '>' of the reference scan), and the second
         // largest key carries the second largest value, equal ones included.  Every 64 blocks (and at the end of the
@@ -333,7 +355,7 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
             mfma_first(an[0], y.f[0][0], xf[xtn][0], y.ci[0]);
             mfma_first(an[1], y.f[1][0], xf[xtn][0], y.ci[1]);
             __builtin_amdgcn_sched_barrier(0);
-            if (xtc == 0 ? sp == 0 : sp == 1) {
+            if (xtc == 0 ? sp == 0 : sp == kSPB - 1) {
                 insert((xtc + kXT - 1) % kXT, 126 - ((xtc == 0 ? gb - 1 : gb) & 63));
                 // the last unit of a 64-block group has just gone in: settle the blocks before the next group reuses the codes
                 if (xtc == 0 && gb != 0 && (gb & 63) == 0) flush((gb >> 6) - 1);
@@ -374,6 +396,24 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
         __syncthreads();
         const uint32_t qn = *s_q;
         const int dvn = load_desc(qn);  // in flight during the scan
+#ifdef AMC_SCAN_STAMPS
+        {
+            const uint32_t now = AMC_STAMP();
+            if (st_prev) {  // the item before this one is complete: its crossings, its boundary, its period
+                st_sum[0] += st_a;
+                st_sum[1] += now - st_end;
+                st_sum[2] += now - st_first;
+                st_sum[3] += 1;
+                st_sum[4] += st_prev_active ? 1 : 0;
+                if (lane == 0) {
+#pragma unroll
+                    for (int k = 0; k < 5; ++k) st_slot[k] = st_sum[k];
+                }
+            }
+            st_a = 0;
+            st_first = now;
+        }
+#endif
         if (active) {
             load_y(y0, 0, 0);
             mfma_first(acc[0][0], y0.f[0][0], xf[0][0], y0.ci[0]);
@@ -392,17 +432,20 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
         // one step = 32 rows' worth of Y held in `yc`; prefetches the next step into `yn`
         // cb / nb: LDS buffers of chunk c and c + 1 (c % 3, (c + 1) % 3)
         auto step = [&](YFrag& yc, YFrag& yn, int c, int cb, int nb, int ys, int sp) __attribute__((always_inline)) {
-            const bool lastt = (ys == kYS - 1);
+            const bool lastt = sp == kSPB - 1 && ys == kYS - 1;  // (a chunk ends with a block)
             const bool cross = lastt && (c + 1 < nchunks);
             const bool fetch = c + 2 < nchunks;  // chunk c + 2 goes to the buffer chunk c - 1 left: (c + 2) % 3
             if (fetch) {
                 const int fb = cb == 0 ? 2 : cb - 1;
                 constexpr int kEvery = kYS / kPW;  // a piece every other step
-                static_assert(kEvery == 2, "a DMA piece per block, behind its first step");
-                if (sp == 0) stage_piece(yprep, c + 2, fb, ys / kEvery);
+                static_assert(kEvery == 2, "a DMA piece behind every other step");
+                if (sp % kEvery == 0) stage_piece(yprep, c + 2, fb, ys / kEvery);
                 if (ys == 0) stage_rs(yrs, c + 2, fb);
             }
             if (cross) {
+#ifdef AMC_SCAN_STAMPS
+                const uint32_t st_t = AMC_STAMP();
+#endif
                 // chunk c + 1 must have landed: everything but this chunk's own kPW (+ 1) pieces of chunk c + 2
                 if (!fetch) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 else if (wid == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPW + 1) : "memory");
@@ -410,12 +453,15 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
                 // a bare barrier: __syncthreads() is a fence and would drain the pieces just issued (vmcnt(0)).
                 // Nothing is stored to LDS here by a wave itself; the DMA'd bytes are ordered by the waits above.
                 asm volatile("s_barrier" ::: "memory");
+#ifdef AMC_SCAN_STAMPS
+                st_a += AMC_STAMP() - st_t;
+#endif
             }
             if (active) {
                 // very last step: re-read itself (result unused) to stay branch-free
                 const int nbuf = cross ? nb : cb;
                 const int nys = lastt ? (cross ? 0 : ys) : ys + 1;
-                const int gb = c * kUPC + ys / 2;
+                const int gb = c * kUPC + ys / kSPB;
 #pragma unroll
                 for (int xt = 0; xt < kXT; ++xt) {
                     if (xt + 1 < kXT)
@@ -433,14 +479,16 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
             const int nb = cb == 2 ? 0 : cb + 1;
             const int yend = (c == nchunks - 1) ? last_steps : kYS;
 #pragma unroll 1
-            for (int ys = 0; ys < yend; ys += 2) {
+            for (int ys = 0; ys < yend; ys += kSPB) {  // one block
                 step(y0, y1, c, cb, nb, ys, 0);
                 step(y1, y0, c, cb, nb, ys + 1, 1);
+                step(y0, y1, c, cb, nb, ys + 2, 2);
+                step(y1, y0, c, cb, nb, ys + 3, 3);
             }
             cb = nb;
         }
         if (active) {
-            const int lastb = (nchunks - 1) * kUPC + last_steps / 2 - 1;
+            const int lastb = (nchunks - 1) * kUPC + last_steps / kSPB - 1;
             insert(kXT - 1, 126 - (lastb & 63));  // the last unit's maximum is still pending
             flush(lastb >> 6);
 #pragma unroll
@@ -450,6 +498,11 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
             }
         }
         __syncthreads();  // everyone is done with the LDS chunk buffers (and has read the queue slot)
+#ifdef AMC_SCAN_STAMPS
+        st_end = AMC_STAMP();
+        st_prev = true;
+        st_prev_active = active;
+#endif
 
         // ---- item done.  Start the next one's loads, then decode and store this one under them ----
         int eb[kXT], es[kXT], et[kXT], ex[kXT];
@@ -473,8 +526,8 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
             for (int xt = 0; xt < kXT; ++xt) {
                 const int kl = xt * 16 + l15;
                 // merge the four lane quarters (they saw different Y rows of every block): equal values keep the
-                // lower tile.  A lane's tile: its block's first or second, by the quarter (-1 while nothing beat the floor)
-                int b = eb[xt], s = es[xt], t = et[xt] < 0 ? -1 : et[xt] * 2 + (lq >> 1);
+                // lower tile.  A lane's tile: the quarter's own of its block's four (-1 while nothing beat the floor)
+                int b = eb[xt], s = es[xt], t = et[xt] < 0 ? -1 : et[xt] * kSPB + lq;
 #pragma unroll
                 for (int m = 16; m <= 32; m <<= 1) {
                     const int ob = __shfl_xor(b, m);
@@ -510,6 +563,13 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
                 }
             }
         }
+#ifdef AMC_SCAN_STAMPS
+        if (qn >= nitems && lane == 0) {  // the workgroup's last item
+            st_slot[5] = st_a;
+            st_slot[6] = AMC_STAMP() - st_first;
+            st_slot[7] = 1;
+        }
+#endif
         q = qn;
         dv = dvn;
     }

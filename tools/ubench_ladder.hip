@@ -25,8 +25,11 @@
 //   hipcc --offload-arch=gfx950 -O3 -o tools/bin/ubench_ladder tools/ubench_ladder.hip && tools/bin/ubench_ladder
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <random>
 #include <vector>
 
 typedef int i32x16 __attribute__((ext_vector_type(16)));
@@ -587,11 +590,47 @@ int main() {
     //   2 small positive bytes (what a zero point of 0 would feed) | 3 zeros | 4 all 0x80
     //   5 small - 36 (a per-image zero point z = max byte - 127 of extractor-like data: small magnitudes of either sign)
     //   6 small - 64
+    //   7 the benchmark's bytes (bench.py, make_arena_torch(stats="l2")) under the kernel's zero point: 128-D rows, 60 %
+    //     noisy copies of |N(0,1)|^3 prototypes and 40 % noise rows, L2-normalised, x 512, rounded, clamped to u8, ^ 0x80
     // LADDER_DATA_X: the same choice for the resident X side alone (default: what LADDER_DATA says) - the streamed Y side
     // (A operand, through LDS) and the X side (B operand, registers) may be encoded independently.
     const int mode = std::getenv("LADDER_DATA") ? std::atoi(std::getenv("LADDER_DATA")) : 0;
     const int mode_x = std::getenv("LADDER_DATA_X") ? std::atoi(std::getenv("LADDER_DATA_X")) : mode;
     std::vector<int> h(8192);
+    // mode 7: 256 rows of 128 bytes (the first 128 rows feed the Y side, the others the X side)
+    std::vector<unsigned char> bench_bytes(8192 * 4);
+    {
+        std::mt19937 gen(2024);
+        std::normal_distribution<float> nd(0.0f, 1.0f);
+        auto cube = [&] { const float v = std::fabs(nd(gen)); return v * v * v; };
+        const int nproto = 32;
+        std::vector<float> proto(nproto * 128), pmean(nproto);
+        for (int p = 0; p < nproto; ++p) {
+            float n2 = 0.0f, sum = 0.0f;
+            for (int k = 0; k < 128; ++k) { proto[p * 128 + k] = cube(); n2 += proto[p * 128 + k] * proto[p * 128 + k]; }
+            for (int k = 0; k < 128; ++k) { proto[p * 128 + k] /= std::sqrt(n2); sum += proto[p * 128 + k]; }
+            pmean[p] = sum / 128.0f;
+        }
+        size_t high = 0;
+        for (int r = 0; r < 256; ++r) {
+            float d[128], n2 = 0.0f;
+            const bool copy = (gen() % 10u) < 6u;
+            const int p = (int)(gen() % (unsigned)nproto);
+            for (int k = 0; k < 128; ++k) {
+                d[k] = copy ? std::max(0.0f, proto[p * 128 + k] + nd(gen) * 0.08f * pmean[p]) : cube() * 0.1f;
+                n2 += d[k] * d[k];
+            }
+            const float inv = 1.0f / std::max(std::sqrt(n2), 1e-12f);
+            for (int k = 0; k < 128; ++k) {
+                const float q = std::nearbyint(512.0f * d[k] * inv);
+                const unsigned char u = (unsigned char)std::min(255.0f, std::max(0.0f, q));
+                high += u >= 128;
+                bench_bytes[r * 128 + k] = u ^ 0x80u;
+            }
+        }
+        if (mode == 7 || mode_x == 7)
+            std::printf("data mode 7: %.4f of the u8 bytes are >= 128 (before the zero point)\n", (double)high / (256.0 * 128.0));
+    }
     unsigned s = 12345;
     auto rnd = [&] { s = s * 1664525u + 1013904223u; return s >> 8; };
     for (size_t i = 0; i < h.size(); ++i) {
@@ -608,6 +647,7 @@ int main() {
                 case 4: byte = 0x80u; break;
                 case 5: byte = (small - 36u) & 255u; break;
                 case 6: byte = (small - 64u) & 255u; break;
+                case 7: byte = bench_bytes[i * 4 + b]; break;
                 default: byte = r & 255u;
             }
             w |= byte << (8 * b);

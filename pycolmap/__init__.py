@@ -2,8 +2,9 @@
 (/root/reference/pycolmap/main.cc:91-118 registers them on the `pycolmap` module) and of SIFT feature extraction
 (`extract_features`, `Sift`, `SiftExtractionOptions`, `Normalization`, `ImageReaderOptions`, `CameraMode`) and of
 known-pose triangulation (`estimate_triangulation`, `PointData`, `EstimateTriangulationOptions`) and of absolute pose
-(`absolute_pose_estimation`, `pose_refinement`, `AbsolutePoseEstimationOptions`, `AbsolutePoseRefinementOptions`)
-resolves to pycolmap_amd's MI355X implementation.  Only what SURVEY.md section 8 and DESIGN.md sections 10 to 12 put in
+(`absolute_pose_estimation`, `pose_refinement`, `AbsolutePoseEstimationOptions`, `AbsolutePoseRefinementOptions`,
+`rig_absolute_pose_estimation`)
+resolves to pycolmap_amd's MI355X implementation.  Only what SURVEY.md section 8 and DESIGN.md sections 10 to 13 put in
 scope exists;
 anything else raises AttributeError naming this package, so that a script reaching for `import_images`, SfM or MVS
 fails at the attribute, not later."""

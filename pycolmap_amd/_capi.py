@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "amc_comm_unique_id", "amc_comm_create", "amc_comm_destroy", "amc_allgather_match_tables", "amc_gathered_tables_free",
     "amc_allgather_pair_records", "amc_gathered_records_free", "amc_allgather_inlier_tables", "amc_ctx_last_timeline",
     "amc_upload_matches",
+    "amc_estimate_rig_absolute_poses", "amc_rigpose_result_free",
 ]
 COMM_ID_BYTES = 128
 RANSAC_F, RANSAC_H, RANSAC_E = 0, 1, 2
@@ -198,6 +199,59 @@ def abspose_inputs(offsets, camera_models, camera_params, points2D, points3D):
     return off, models, prm, p2, p3
 
 
+class RigPoseResult(C.Structure):  # amc_rigpose_result (include/amc_rigpose.h)
+    _fields_ = [("nqueries", C.c_size_t), ("ncorr", C.c_size_t), ("success", C.POINTER(C.c_uint8)),
+                ("qvec", C.POINTER(C.c_double)), ("tvec", C.POINTER(C.c_double)),
+                ("num_inliers", C.POINTER(C.c_uint32)), ("num_all_inliers", C.POINTER(C.c_uint32)),
+                ("num_trials", C.POINTER(C.c_uint64)), ("covariance", C.POINTER(C.c_double)),
+                ("inlier_mask", C.POINTER(C.c_uint8)), ("device_ms", C.c_double), ("kernel_ms", C.c_double),
+                ("num_batches", C.c_uint32), ("_priv", C.c_void_p)]
+
+
+def rigpose_options(estimation=None, refinement=None):
+    """amc_ransac_opts at pycolmap's RANSACOptions() defaults and amc_abspose_refine_opts at its own, with the given
+    fields replaced; an unknown field raises ValueError."""
+    eo = RansacOpts()
+    for k, v in dict(max_error=4.0, min_inlier_ratio=0.01, confidence=0.9999, dyn_num_trials_multiplier=3.0,
+                     min_num_trials=1000, max_num_trials=100000).items():
+        setattr(eo, k, v)
+    for k, v in (estimation or {}).items():
+        if k not in dict(RansacOpts._fields_):
+            raise ValueError(f"unknown rig pose RANSAC option {k!r}")
+        setattr(eo, k, type(getattr(eo, k))(v))
+    return eo, abspose_options(None, refinement)[1]
+
+
+def rigpose_inputs(offsets, camera_offsets, camera_models, camera_params, cams_from_rig, camera_idxs, points2D,
+                   points3D):
+    """The CSR batch of amc_estimate_rig_absolute_poses as contiguous arrays: offsets (Q + 1,) and camera_offsets
+    (Q + 1,) uint64, models (C,) int32, params (C, 12), cams_from_rig (C, 7) x y z w tx ty tz, camera_idxs (N,) int32
+    (each into its query's own cameras), points2D (N, 2), points3D (N, 3)."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    coff = np.ascontiguousarray(camera_offsets, dtype=np.uint64).reshape(-1)
+    if off.size < 1 or coff.size != off.size:
+        raise ValueError("rig poses: offsets and camera_offsets need nqueries + 1 entries each")
+    n, nc = int(off[-1]), int(coff[-1])
+    models = np.ascontiguousarray(camera_models, dtype=np.int32).reshape(-1)
+    rigs = np.ascontiguousarray(cams_from_rig, dtype=np.float64).reshape(-1, 7)
+    if models.size != nc or len(camera_params) != nc or rigs.shape[0] != nc:
+        raise ValueError(f"rig poses: {nc} cameras by camera_offsets, {models.size} camera models, "
+                         f"{len(camera_params)} parameter sets, {rigs.shape[0]} cams_from_rig")
+    prm = np.zeros((nc, 12), np.float64)
+    for i, p in enumerate(camera_params):
+        p = np.asarray(p, dtype=np.float64).reshape(-1)
+        if p.size > 12:
+            raise ValueError(f"rig poses: camera {i} has {p.size} parameters (at most 12)")
+        prm[i, :p.size] = p
+    idx = np.ascontiguousarray(camera_idxs, dtype=np.int32).reshape(-1)
+    p2 = np.ascontiguousarray(points2D, dtype=np.float64).reshape(-1, 2)
+    p3 = np.ascontiguousarray(points3D, dtype=np.float64).reshape(-1, 3)
+    if p2.shape[0] != n or p3.shape[0] != n or idx.size != n:
+        raise ValueError(f"rig poses: {n} correspondences by offsets, {p2.shape[0]} points2D, {p3.shape[0]} points3D, "
+                         f"{idx.size} camera_idxs")
+    return off, coff, models, prm, rigs, idx, p2, p3
+
+
 class TriOpts(C.Structure):  # amc_tri_opts (include/amc_tri.h)
     _fields_ = [("min_tri_angle", C.c_double), ("max_error", C.c_double), ("min_inlier_ratio", C.c_double),
                 ("confidence", C.c_double), ("dyn_num_trials_multiplier", C.c_double),
@@ -332,6 +386,13 @@ def load() -> C.CDLL:
         lib.amc_refine_absolute_poses.restype = C.c_int
         lib.amc_abspose_result_free.argtypes = [C.POINTER(AbsPoseResult)]
         lib.amc_abspose_result_free.restype = None
+    if hasattr(lib, "amc_estimate_rig_absolute_poses"):
+        lib.amc_estimate_rig_absolute_poses.argtypes = ([C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7 +
+                                                        [C.POINTER(RansacOpts), C.POINTER(AbsPoseRefineOpts), C.c_int,
+                                                         C.POINTER(RigPoseResult)])
+        lib.amc_estimate_rig_absolute_poses.restype = C.c_int
+        lib.amc_rigpose_result_free.argtypes = [C.POINTER(RigPoseResult)]
+        lib.amc_rigpose_result_free.restype = None
     if hasattr(lib, "amc_triangulate_tracks"):  # (absent from a library built from an older revision)
         lib.amc_tri_opts_default.argtypes = [C.POINTER(TriOpts)]
         lib.amc_tri_opts_default.restype = None
@@ -736,6 +797,39 @@ class Context:
                 out["covariance"] = a(res.covariance, (nq, 36)).reshape(nq, 6, 6)
         finally:
             self._lib.amc_abspose_result_free(C.byref(res))
+        return out
+
+    def estimate_rig_absolute_poses(self, offsets, camera_offsets, camera_models, camera_params, cams_from_rig,
+                                    camera_idxs, points2D, points3D, estimation=None, refinement=None,
+                                    return_covariance=False):
+        """amc_estimate_rig_absolute_poses: one RANSAC of the generalised P3P and one refinement of rig_from_world per
+        query (DESIGN.md section 13).  offsets / camera_offsets: (Q + 1,) CSR over the correspondences / the cameras;
+        camera_models, camera_params, cams_from_rig (x y z w tx ty tz): one entry per camera; camera_idxs: (N,) indices
+        into the query's own cameras; points2D: (N, 2) pixels; points3D: (N, 3).  estimation / refinement: dicts of
+        amc_ransac_opts / amc_abspose_refine_opts fields.  Returns a dict: success (Q,) bool, qvec (Q, 4) x y z w,
+        tvec (Q, 3), num_inliers (distinct 3D points), num_all_inliers, num_trials, inlier_mask (N,) bool, covariance
+        (Q, 6, 6) when asked, device_ms, kernel_ms, num_batches."""
+        off, coff, models, prm, rigs, idx, p2, p3 = rigpose_inputs(offsets, camera_offsets, camera_models,
+                                                                   camera_params, cams_from_rig, camera_idxs,
+                                                                   points2D, points3D)
+        eo, ro = rigpose_options(estimation, refinement)
+        nq, n = off.size - 1, int(off[-1])
+        res = RigPoseResult()
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _check(self._lib.amc_estimate_rig_absolute_poses(self._h, ptr(off), nq, ptr(coff), ptr(models), ptr(prm),
+                                                          ptr(rigs), ptr(idx), ptr(p2), ptr(p3), C.byref(eo),
+                                                          C.byref(ro), int(bool(return_covariance)), C.byref(res)))
+        try:
+            a = lambda p, shape: np.ctypeslib.as_array(p, (max(shape[0], 1),) + shape[1:])[:shape[0]].copy()  # noqa: E731
+            out = {"success": a(res.success, (nq,)).astype(bool), "qvec": a(res.qvec, (nq, 4)),
+                   "tvec": a(res.tvec, (nq, 3)), "num_inliers": a(res.num_inliers, (nq,)),
+                   "num_all_inliers": a(res.num_all_inliers, (nq,)), "num_trials": a(res.num_trials, (nq,)),
+                   "inlier_mask": a(res.inlier_mask, (n,)).astype(bool), "device_ms": res.device_ms,
+                   "kernel_ms": res.kernel_ms, "num_batches": int(res.num_batches)}
+            if return_covariance:
+                out["covariance"] = a(res.covariance, (nq, 36)).reshape(nq, 6, 6)
+        finally:
+            self._lib.amc_rigpose_result_free(C.byref(res))
         return out
 
     def triangulate_tracks(self, poses, track_offsets, obs_pose, obs_xy, **opts):

@@ -1172,9 +1172,11 @@ struct Eval {
     double H[21];
     double g[6];
 };
-AMC_HD Eval evaluate(const RefineParams& rp, const double* q, const double* t, const double* xy, const double* X,
-                     const uint8_t* mask, uint32_t n, bool jac) {
-    const double b = rp.loss_scale * rp.loss_scale, c = 1.0 / b;
+// res(k, q, t, rx, ry): the residual of correspondence k with d/d(q, t) (the rig refinement of rigpose_core.h passes its own)
+template <class Res>
+AMC_HD Eval evaluate_t(const Res& res, double loss_scale, const double* q, const double* t, const uint8_t* mask,
+                       uint32_t n, bool jac) {
+    const double b = loss_scale * loss_scale, c = 1.0 / b;
     double Jm[12];
     quat_plus_jacobian(q, Jm);
     Eval ev;
@@ -1185,7 +1187,7 @@ AMC_HD Eval evaluate(const RefineParams& rp, const double* q, const double* t, c
             for (uint32_t k = (uint32_t)l; k < n; k += kLanes) {
                 if (!mask[k]) continue;
                 Jet rx, ry;
-                pixel_residual(rp, q, t, X + 3 * k, xy[2 * k], xy[2 * k + 1], rx, ry);
+                res(k, q, t, rx, ry);
                 const double sq = rx.a * rx.a + ry.a * ry.a;
                 const double sum = 1.0 + sq * c;
                 const double inv = 1.0 / sum;
@@ -1232,8 +1234,16 @@ AMC_HD double gradient_max_norm(const double* q, const double* t, const double* 
     return m;
 }
 
-AMC_HD RefineOut refine(const RefineParams& rp, const double* q0, const double* t0, const double* xy, const double* X,
-                        const uint8_t* mask, uint32_t n) {
+// the solver's settings without the camera (12.7)
+struct LmParams {
+    double gradient_tolerance;
+    int64_t max_num_iterations;
+    double loss_scale;
+    bool covariance;
+};
+template <class Res>
+AMC_HD RefineOut refine_t(const Res& res, const LmParams& rp, const double* q0, const double* t0, const uint8_t* mask,
+                          uint32_t n) {
     RefineOut out;
     out.success = false;
     out.iterations = 0;
@@ -1248,7 +1258,7 @@ AMC_HD RefineOut refine(const RefineParams& rp, const double* q0, const double* 
         cnt);
     bool usable = true;
     if (cnt[0] > 0.0) {
-        Eval ev = evaluate(rp, q, t, xy, X, mask, n, true);
+        Eval ev = evaluate_t(res, rp.loss_scale, q, t, mask, n, true);
         if (!finite(ev.cost)) usable = false;
         double scale[6];
         for (int i = 0; i < 6; ++i) scale[i] = 1.0 / (1.0 + dsqrt(sym6(ev.H, i, i)));
@@ -1308,7 +1318,7 @@ AMC_HD RefineOut refine(const RefineParams& rp, const double* q0, const double* 
                 xn = xn + t[i] * t[i];
             }
             if (dsqrt(sn) <= 1e-8 * (dsqrt(xn) + 1e-8)) break;
-            const Eval cand = evaluate(rp, qn, tn, xy, X, mask, n, false);
+            const Eval cand = evaluate_t(res, rp.loss_scale, qn, tn, mask, n, false);
             const double new_cost = finite(cand.cost) ? cand.cost : kDblMax;
             const double cost_change = ev.cost - new_cost;
             if (dabs(cost_change) <= 1e-6 * ev.cost) break;  // function tolerance
@@ -1316,7 +1326,7 @@ AMC_HD RefineOut refine(const RefineParams& rp, const double* q0, const double* 
             if (rel > 1e-3) {
                 for (int i = 0; i < 4; ++i) q[i] = qn[i];
                 for (int i = 0; i < 3; ++i) t[i] = tn[i];
-                ev = evaluate(rp, q, t, xy, X, mask, n, true);
+                ev = evaluate_t(res, rp.loss_scale, q, t, mask, n, true);
                 const double z = 2.0 * rel - 1.0;
                 const double f = 1.0 - z * z * z;
                 radius = radius / (f > 1.0 / 3.0 ? f : 1.0 / 3.0);
@@ -1356,6 +1366,15 @@ AMC_HD RefineOut refine(const RefineParams& rp, const double* q0, const double* 
     for (int i = 0; i < 4; ++i) out.q[i] = q[i];
     for (int i = 0; i < 3; ++i) out.t[i] = t[i];
     return out;
+}
+AMC_HD RefineOut refine(const RefineParams& rp, const double* q0, const double* t0, const double* xy, const double* X,
+                        const uint8_t* mask, uint32_t n) {
+    const LmParams lm{rp.gradient_tolerance, rp.max_num_iterations, rp.loss_scale, rp.covariance};
+    return refine_t(
+        [&](uint32_t k, const double* qq, const double* tt, Jet& rx, Jet& ry) {
+            pixel_residual(rp, qq, tt, X + 3 * k, xy[2 * k], xy[2 * k + 1], rx, ry);
+        },
+        lm, q0, t0, mask, n);
 }
 
 // ---- 12.1: the model -> quaternion step and the NaN test --------------------------------------------------------------

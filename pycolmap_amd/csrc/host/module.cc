@@ -37,6 +37,7 @@
 #include "sift_host.h"
 #include "tri_host.h"
 #include "abspose_host.h"
+#include "rigpose_host.h"
 
 namespace py = pybind11;
 using namespace pybind11::literals;
@@ -963,6 +964,19 @@ PYBIND11_MODULE(_pycolmap, m) {
           "return_covariance"_a = false, "Absolute pose estimation with non-linear refinement.");
     m.def("pose_refinement", &RefineAbsolutePose, "cam_from_world"_a, "points2D"_a, "points3D"_a, "inlier_mask"_a,
           "camera"_a, "refinement_options"_a = abs_ref_defaults, "Non-linear refinement of absolute pose.");
+
+    // ---- rig_absolute_pose_estimation (reference: pycolmap/estimators/generalized_absolute_pose.h; rigpose_host.h) -----
+    // The reference's m.def attaches the keyword names "cameras", "camera_idxs", "cams_from_rig" to the positions of
+    // camera_idxs, cams_from_rig, cameras: cameras= names the index slot.  Reproduced as it is.
+    m.def("rig_absolute_pose_estimation", &EstimateAndRefineGeneralizedAbsolutePose, "points2D"_a, "points3D"_a,
+          "cameras"_a, "camera_idxs"_a, "cams_from_rig"_a,
+          "estimation_options"_a = py_ransac_cls().cast<RANSACOptions>(), "refinement_options"_a = abs_ref_defaults,
+          "return_covariance"_a = false,
+          "Absolute pose estimation with non-linear refinement for a multi-camera rig.\n\n"
+          "Positional order: points2D, points3D, camera_idxs, cams_from_rig, cameras, estimation_options, "
+          "refinement_options, return_covariance.  As in the reference binding, the keyword names of the third to "
+          "fifth argument are shifted: cameras= takes the camera indices, camera_idxs= the cams_from_rig list and "
+          "cams_from_rig= the cameras.");
 
     // ---- Database ---------------------------------------------------------------------------
     py::class_<Database>(m, "Database")

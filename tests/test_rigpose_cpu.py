@@ -1,0 +1,333 @@
+"""Rig absolute pose without a GPU: the pycolmap surface (names, defaults, the reference's shifted keyword names, every
+THROW_CHECK error, N = 0, the out-of-scope options), the C header, and the CPU reference (tests/rigpose_ref) against its
+frozen fixture, an independent numpy restatement of the generalised P3P, hand-built unique-inlier supports, central
+differences and numpy's covariance."""
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import rigpose_cases
+import rigpose_ref_lib as ref
+from pycolmap_amd import _capi, synth
+
+ROOT = Path(__file__).resolve().parent.parent
+GOLDEN = ROOT / "tests" / "golden" / "rigpose_ref_v1.npz"
+FIELDS = ("success", "qvec", "tvec", "num_inliers", "num_all_inliers", "num_trials", "inlier_mask", "covariance")
+
+
+# ---- the pycolmap surface -------------------------------------------------------------------------------------------
+def rig_of_two():
+    import pycolmap_amd as pc
+    cams = [pc.Camera(model="SIMPLE_PINHOLE", width=100, height=100, params=[100.0, 50.0, 50.0]),
+            pc.Camera(model="PINHOLE", width=100, height=100, params=[100.0, 100.0, 50.0, 50.0])]
+    return cams, [pc.Rigid3d(), pc.Rigid3d()]
+
+
+def test_names_defaults_and_shifted_keywords():
+    import pycolmap
+    import pycolmap_amd as pc
+    assert pycolmap.rig_absolute_pose_estimation is pc.rig_absolute_pose_estimation
+    doc = pc.rig_absolute_pose_estimation.__doc__
+    sig = doc.splitlines()[0]
+    # the reference's keyword names, in its order; the defaults
+    order = ["points2D", "points3D", "cameras", "camera_idxs", "cams_from_rig", "estimation_options",
+             "refinement_options", "return_covariance"]
+    assert [sig.index(f"{n}:") for n in order] == sorted(sig.index(f"{n}:") for n in order)
+    assert "return_covariance: bool = False" in sig and "RANSACOptions" in sig and "AbsolutePoseRefinementOptions" in sig
+    assert "cameras= takes the camera indices" in doc
+    cams, rigs = rig_of_two()
+    # cameras= names the index slot: the value 5 reaches the index check against the two cameras of cams_from_rig=
+    with pytest.raises(ValueError, match=r"< cameras.size\(\) \(5 vs. 2\)"):
+        pc.rig_absolute_pose_estimation(np.zeros((3, 2)), np.zeros((3, 3)), cameras=[0, 1, 5], camera_idxs=rigs,
+                                        cams_from_rig=cams)
+    with pytest.raises(TypeError):
+        pc.rig_absolute_pose_estimation(np.zeros((3, 2)), np.zeros((3, 3)), [0, 1, 1], rigs, cams, ransac_options=None)
+
+
+def test_throw_checks_empty_input_and_out_of_scope_options():
+    import pycolmap_amd as pc
+    cams, rigs = rig_of_two()
+    f = pc.rig_absolute_pose_estimation
+    with pytest.raises(ValueError, match=r"Check Failed: points2D.size\(\) == points3D.size\(\) \(3 vs. 4\)"):
+        f(np.zeros((3, 2)), np.zeros((4, 3)), [0, 0, 0], rigs, cams)
+    with pytest.raises(ValueError, match=r"Check Failed: points2D.size\(\) == camera_idxs.size\(\) \(3 vs. 2\)"):
+        f(np.zeros((3, 2)), np.zeros((3, 3)), [0, 0], rigs, cams)
+    with pytest.raises(ValueError, match=r"Check Failed: cams_from_rig.size\(\) == cameras.size\(\) \(1 vs. 2\)"):
+        f(np.zeros((3, 2)), np.zeros((3, 3)), [0, 0, 0], rigs[:1], cams)
+    with pytest.raises(ValueError, match=r"min_element\(camera_idxs.begin\(\), camera_idxs.end\(\)\) >= 0 \(-1 vs. 0\)"):
+        f(np.zeros((3, 2)), np.zeros((3, 3)), [0, -1, 1], rigs, cams)
+    with pytest.raises(ValueError, match=r"max_element\(camera_idxs.begin\(\), camera_idxs.end\(\)\) < cameras.size\(\) \(2 vs. 2\)"):
+        f(np.zeros((3, 2)), np.zeros((3, 3)), [0, 2, 1], rigs, cams)
+    with pytest.raises(ValueError, match="N x 2"):
+        f(np.zeros((3, 3)), np.zeros((3, 3)), [0, 0, 0], rigs, cams)
+    # N = 0: no index checks, None (also with no cameras at all)
+    assert f(np.zeros((0, 2)), np.zeros((0, 3)), [], rigs, cams) is None
+    assert f([], [], [], [], []) is None
+    for k in ("refine_focal_length", "refine_extra_params"):
+        with pytest.raises(ValueError, match=f"{k}=True is not supported"):
+            f(np.zeros((3, 2)), np.zeros((3, 3)), [0, 0, 0], rigs, cams,
+              refinement_options=pc.AbsolutePoseRefinementOptions({k: True}))
+
+
+def test_header_and_ctypes_layer_name_the_entry_points():
+    h = (ROOT / "include" / "amc_rigpose.h").read_text()
+    for name in ("amc_estimate_rig_absolute_poses", "amc_rigpose_result_free", "amc_rigpose_result"):
+        assert name in h
+    assert "AMC_ABI_VERSION" not in h.replace("AMC_ABI_VERSION is unchanged", "")
+    assert {"amc_estimate_rig_absolute_poses", "amc_rigpose_result_free"} <= set(_capi.EXPORTED_SYMBOLS)
+    lib = _capi.load()
+    assert hasattr(lib, "amc_estimate_rig_absolute_poses") and lib.amc_abi_version() == 5
+    assert hasattr(_capi.Context, "estimate_rig_absolute_poses")
+    eo, ro = _capi.rigpose_options(dict(max_error=2.0), dict(max_num_iterations=7))
+    assert (eo.max_error, eo.min_num_trials, eo.max_num_trials, ro.max_num_iterations) == (2.0, 1000, 100000, 7)
+    with pytest.raises(ValueError):
+        _capi.rigpose_options(dict(estimate_focal_length=1))
+
+
+# ---- the reference against its fixture ------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def reference_results():
+    return {n: (sc, ref.estimate(*rigpose_cases.args(sc), est, rf, cov))
+            for n, (sc, est, rf, cov) in rigpose_cases.cases().items()}
+
+
+def test_reference_equals_its_fixture_bit_for_bit(reference_results):
+    with np.load(GOLDEN) as g:
+        seen = set()
+        for name, (_, r) in reference_results.items():
+            for k in FIELDS:
+                if k in r:
+                    a, b = np.asarray(r[k]), g[f"{name}/{k}"]
+                    if a.dtype == np.float64:
+                        a, b = a.view(np.uint64), b.view(np.uint64)
+                    assert np.array_equal(a, b), f"{name}: {k}"
+                    seen.add(f"{name}/{k}")
+        assert seen == set(g.files)
+
+
+def test_reference_recovers_the_true_rig_pose(reference_results):
+    for name, (sc, r) in reference_results.items():
+        if name in ("n2", "n3"):  # too few points to succeed (n2) or to pin the pose down under noise (n3)
+            assert r["success"][0] == (name == "n3")
+            continue
+        assert r["success"][0], name
+        dq = abs(abs(float((r["qvec"] * sc["qvec"]).sum())) - 1.0)
+        dt = np.linalg.norm(r["tvec"] - sc["tvec"])
+        assert dq < 1e-5 and dt < 2e-2, (name, dq, dt)
+        inl = r["inlier_mask"]
+        assert r["num_all_inliers"][0] == inl.sum() and r["num_inliers"][0] <= inl.sum()
+        # 2 px noise per axis leaves 1 - exp(-4^2 / (2 * 2^2)) = 86 % of the true matches within max_error = 4 px of
+        # the true pose (refine_opts); 0.5 px noise or less leaves all of them
+        frac = 0.7 if name == "refine_opts" else 0.9
+        assert (inl & ~sc["outlier"]).sum() >= frac * (~sc["outlier"]).sum(), name
+    sc, r = reference_results["duplicates"]
+    ids = {tuple(x) for x in sc["points3D"][r["inlier_mask"]]}
+    assert r["num_inliers"][0] == len(ids) < r["num_all_inliers"][0]
+
+
+# ---- GP3P against an independent numpy restatement ----------------------------------------------------------------------
+def gp3p_sample(seed):
+    """three rays of a rig (a quarter of the samples with one common centre), their world points and the true pose"""
+    r = np.random.default_rng(seed)
+    R, _ = synth.random_rotation(r)
+    t = r.normal(size=3)
+    X = r.normal(size=(3, 3)) * 3
+    Y = X @ R.T + t
+    c = r.normal(size=(3, 3)) * 0.3
+    if seed % 4 == 0:
+        c[:] = c[0]
+    d = Y - c
+    lam = np.linalg.norm(d, axis=1)
+    return c, d / lam[:, None], X, R, t, lam
+
+
+def sylvester(p, q):
+    """the Sylvester matrix of two polynomials (coefficients high -> low)"""
+    m, n = len(p) - 1, len(q) - 1
+    S = np.zeros((m + n, m + n))
+    for i in range(n):
+        S[i, i:i + m + 1] = p
+    for i in range(m):
+        S[n + i, i:i + n + 1] = q
+    return S
+
+
+def numpy_gp3p(c, d, X):
+    """The real solutions (l1, l2, l3) of the three distance quadrics by another route than 13.3: both resultants as
+    numpy determinants of Sylvester matrices at Chebyshev nodes, the octic by interpolation, numpy.roots, the other two
+    depths from the quadrics' own roots, numpy Newton steps."""
+    def quad(i, j):
+        e = c[i] - c[j]
+        return -2 * d[i] @ d[j], 2 * e @ d[i], -2 * e @ d[j], e @ e - np.sum((X[i] - X[j]) ** 2)
+    (m12, u12, v12, k12), (m13, u13, v13, k13), (m23, u23, v23, k23) = quad(0, 1), quad(0, 2), quad(1, 2)
+
+    def f1(l2):
+        return [1, u12 + m12 * l2, k12 + v12 * l2 + l2 * l2]
+
+    def f2(l3):
+        return [1, u13 + m13 * l3, k13 + v13 * l3 + l3 * l3]
+
+    def f3(l3):
+        return [1, u23 + m23 * l3, k23 + v23 * l3 + l3 * l3]
+    s = np.sqrt(max(abs(k12), abs(k13), abs(k23), 1.0))  # the scale of the depths
+    xs = 2 * s * np.cos(np.pi * (np.arange(5) + 0.5) / 5)
+    ys = 2 * s * np.cos(np.pi * (np.arange(13) + 0.5) / 13)
+    h = []
+    for y in ys:
+        g = np.polyfit(xs, [np.linalg.det(sylvester(f1(x), f2(y))) for x in xs], 4)
+        h.append(np.linalg.det(sylvester(g, f3(y))))
+    octic = np.polyfit(ys / s, np.array(h) / s ** 8, 8)
+    sols = []
+    for r in np.roots(octic):
+        if abs(r.imag) > 1e-6 * max(1, abs(r)):
+            continue
+        l3 = r.real * s
+        best = None
+        for l2 in np.roots(f3(l3)):
+            for l1 in np.roots(f1(l2)):
+                f = abs(np.polyval(f2(l3), l1))
+                if best is None or f < best[0]:
+                    best = (f, l1, l2)
+        l = np.array([best[1], best[2], l3])
+        if np.abs(l.imag).max() > 1e-5 * max(1, np.abs(l).max()):
+            continue
+        l = l.real.astype(float)
+        for _ in range(4):
+            F = np.array([np.polyval(f1(l[1]), l[0]), np.polyval(f2(l[2]), l[0]), np.polyval(f3(l[2]), l[1])])
+            J = np.array([[2 * l[0] + m12 * l[1] + u12, 2 * l[1] + m12 * l[0] + v12, 0],
+                          [2 * l[0] + m13 * l[2] + u13, 0, 2 * l[2] + m13 * l[0] + v13],
+                          [0, 2 * l[1] + m23 * l[2] + u23, 2 * l[2] + m23 * l[1] + v23]])
+            l = l - np.linalg.solve(J, F)
+        if not any(np.abs(l - x).max() < 1e-7 * max(1, np.abs(l).max()) for x in sols):
+            sols.append(l)
+    return sols
+
+
+# Measured over the 1,000 samples below: the reference's depths are within 9.6e-13 of the numpy
+# solution's and within 4.5e-13 of the true depths (relative to the largest true depth), its best model within 4.8e-10 of
+# the true [R | t] (largest entry difference).  The bounds are a hundred times that; no sample is left out.
+GP3P_DEPTH_BOUND = 1e-10
+GP3P_POSE_BOUND = 5e-8
+
+
+def test_gp3p_agrees_with_numpy_restatement_and_finds_the_true_pose():
+    worst_set = worst_true = worst_pose = 0.0
+    counts = set()
+    for seed in range(1000):
+        c, d, X, R, t, lam = gp3p_sample(seed)
+        models, depths = ref.gp3p(c, d, X)
+        want = numpy_gp3p(c, d, X)
+        sc = max(1.0, np.abs(lam).max())
+        assert len(depths) == len(want), f"sample {seed}: {len(depths)} solutions, numpy has {len(want)}"
+        e = max(max(min(np.abs(l - x).max() for x in want) for l in depths),
+                max(min(np.abs(l - x).max() for l in depths) for x in want)) / sc
+        et = min(np.abs(l - lam).max() for l in depths) / sc
+        ep = min(max(np.abs(m[:, :3] - R).max(), np.abs(m[:, 3] - t).max()) for m in models)
+        worst_set, worst_true, worst_pose = max(worst_set, e), max(worst_true, et), max(worst_pose, ep)
+        counts.add(len(depths))
+        for m in models:
+            assert abs(np.linalg.det(m[:, :3]) - 1.0) < 1e-9 and np.abs(m[:, :3] @ m[:, :3].T - np.eye(3)).max() < 1e-9
+    print(f"gp3p: depths vs numpy {worst_set:.3e}, vs truth {worst_true:.3e}, pose vs truth {worst_pose:.3e}, "
+          f"solution counts {sorted(counts)}")
+    assert worst_set <= GP3P_DEPTH_BOUND and worst_true <= GP3P_DEPTH_BOUND and worst_pose <= GP3P_POSE_BOUND
+    assert counts <= {2, 4, 6, 8} and 8 in counts
+
+
+# ---- the unique-inlier support ----------------------------------------------------------------------------------------
+IDENT = np.hstack([np.eye(3), np.zeros((3, 1))])
+TWO_CAMS = dict(camera_models=[0, 0], camera_params=[[100.0, 50.0, 50.0]] * 2,
+                cams_from_rig=[[0, 0, 0, 1, 0, 0, 0], [0, 0, 0, 1, 0.5, 0, 0]])
+
+
+def two_cam_support(X, cidx, shift=None, thr=1e-6):
+    """the support of the identity rig pose over points X seen exactly (or off by `shift`) by the cameras cidx"""
+    X = np.asarray(X, dtype=np.float64)
+    tc = np.array([[0, 0, 0], [0.5, 0, 0]], dtype=np.float64)[np.asarray(cidx)]
+    Z = X + tc
+    uv = Z[:, :2] / Z[:, 2:]
+    if shift is not None:
+        uv = uv + np.asarray(shift, dtype=np.float64)
+    return ref.support(TWO_CAMS["camera_models"], TWO_CAMS["camera_params"], TWO_CAMS["cams_from_rig"], cidx, uv, X, IDENT,
+                       thr)
+
+
+def test_a_point_seen_by_two_cameras_counts_once():
+    P = [[0.1, 0.2, 5.0], [1.0, -0.5, 6.0], [-1.0, 0.3, 4.0], [0.4, 0.4, 7.0]]
+    cnt, uniq, s, mask = two_cam_support(P + P[:2], [0, 0, 1, 1, 1, 0])
+    assert (cnt, uniq) == (6, 4) and mask.all() and s < 1e-20
+    # +0 and -0 compare equal; a NaN never does; a duplicate that is an outlier takes nothing away
+    cnt, uniq, _, _ = two_cam_support([[0.0, 0.2, 5.0], [-0.0, 0.2, 5.0]], [0, 1])
+    assert (cnt, uniq) == (2, 1)
+    cnt, uniq, _, mask = two_cam_support(P + P[:1], [0, 0, 1, 1, 1], shift=[[0, 0]] * 4 + [[1.0, 0]])
+    assert (cnt, uniq) == (4, 4) and not mask[4]
+    # only the inliers' points count: the first of a point's two observations is the outlier
+    cnt, uniq, _, mask = two_cam_support(P[:1] + P, [1, 0, 0, 1, 1], shift=[[1.0, 0]] + [[0, 0]] * 4)
+    assert (cnt, uniq) == (4, 4) and not mask[0]
+    # behind the camera: DBL_MAX, never an inlier
+    cnt, uniq, _, _ = two_cam_support([[0.1, 0.2, -5.0]], [0], thr=1e300)
+    assert (cnt, uniq) == (0, 0)
+
+
+def test_unique_count_then_inlier_count_then_residual_sum_decide():
+    P = [[0.1, 0.2, 5.0], [1.0, -0.5, 6.0], [-1.0, 0.3, 4.0], [0.4, 0.4, 7.0]]
+    a = two_cam_support(P, [0, 1, 0, 1])[:3]                                       # 4 inliers, 4 points
+    b = two_cam_support(P[:3] + P[:2], [0, 1, 0, 1, 0])[:3]                        # 5 inliers, 3 points
+    c = two_cam_support(P + P[:1], [0, 1, 0, 1, 1])[:3]                            # 5 inliers, 4 points
+    d = two_cam_support(P, [0, 1, 0, 1], shift=[[1e-4, 0]] * 4)[:3]                # 4 inliers, 4 points, larger sum
+    assert (a[:2], b[:2], c[:2], d[:2]) == ((4, 4), (5, 3), (5, 4), (4, 4)) and d[2] > a[2]
+    assert ref.better(a, b) and not ref.better(b, a)        # more points beat more inliers
+    assert ref.better(c, a) and not ref.better(a, c)        # the same points: more inliers
+    assert ref.better(a, d) and not ref.better(d, a)        # the same counts: the smaller residual sum
+    assert not ref.better(a, a)
+    assert ref.better(a, (0, 0, np.finfo(np.float64).max))  # anything beats the initial support
+
+
+# ---- the refinement ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("model", range(11))
+def test_residual_jacobian_matches_central_differences(model):
+    rng = np.random.default_rng(200 + model)
+    sc = rigpose_cases.rig_scene(300 + model, 6, models=(model, 0), noise_px=0.5)
+    q = sc["qvec"][0] + rng.normal(scale=1e-3, size=4)  # off the unit sphere too: the derivative is the ambient one
+    t = sc["tvec"][0] + rng.normal(scale=1e-2, size=3)
+    worst = 0.0
+    for k in range(6):
+        c = int(sc["camera_idxs"][k])
+        a = (int(sc["camera_models"][c]), sc["camera_params"][c], sc["cams_from_rig"][c])
+        res, J = ref.residual(*a, q, t, sc["points3D"][k], sc["points2D"][k])
+        x = np.concatenate([q, t])
+        num = np.zeros((2, 7))
+        for i in range(7):
+            h = 1e-6 * max(1.0, abs(x[i]))
+            xp, xm = x.copy(), x.copy()
+            xp[i] += h
+            xm[i] -= h
+            num[:, i] = (ref.residual(*a, xp[:4], xp[4:], sc["points3D"][k], sc["points2D"][k])[0] -
+                         ref.residual(*a, xm[:4], xm[4:], sc["points3D"][k], sc["points2D"][k])[0]) / (xp[i] - xm[i])
+        worst = max(worst, np.abs(J - num).max() / max(1.0, np.abs(J).max()))
+    # central differences with h = 1e-6: truncation h^2 |f'''| / 6 and rounding eps |f| / h, both about 1e-9 of the
+    # Jacobian's scale for residuals of pixel size; 1e-6 leaves room for the distortion models' higher derivatives
+    assert worst < 1e-6, worst
+
+
+def test_covariance_matches_numpy_on_a_small_problem():
+    sc = rigpose_cases.rig_scene(400, 40, models=(1, 4), noise_px=1.0)
+    r = ref.estimate(*rigpose_cases.args(sc), rigpose_cases.FAST, None, True)
+    assert r["success"][0]
+    q, t = r["qvec"][0], r["tvec"][0]
+    Jm = np.array([[q[3], q[2], -q[1]], [-q[2], q[3], q[0]], [q[1], -q[0], q[3]], [-q[0], -q[1], -q[2]]])
+    rows = []
+    for k in np.flatnonzero(r["inlier_mask"]):
+        c = int(sc["camera_idxs"][k])
+        res, J = ref.residual(int(sc["camera_models"][c]), sc["camera_params"][c], sc["cams_from_rig"][c], q, t,
+                              sc["points3D"][k], sc["points2D"][k])
+        w = np.sqrt(1.0 / (1.0 + res @ res))  # CauchyLoss(1): rho' = 1 / (1 + s)
+        rows.append(w * np.hstack([J[:, :4] @ Jm, J[:, 4:]]))
+    J = np.vstack(rows)
+    want = np.linalg.inv(J.T @ J)
+    got = r["covariance"][0]
+    assert np.allclose(got, got.T, rtol=0, atol=1e-12 * np.abs(got).max())
+    # two inverses of one 6 x 6 matrix in doubles: relative error about cond * eps
+    cond = np.linalg.cond(J.T @ J)
+    assert np.abs(got - want).max() <= 100 * cond * np.finfo(np.float64).eps * np.abs(want).max()
+    assert np.all(np.linalg.eigvalsh(got) > 0)

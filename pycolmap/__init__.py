@@ -3,8 +3,9 @@
 (`extract_features`, `Sift`, `SiftExtractionOptions`, `Normalization`, `ImageReaderOptions`, `CameraMode`) and of
 known-pose triangulation (`estimate_triangulation`, `PointData`, `EstimateTriangulationOptions`) and of absolute pose
 (`absolute_pose_estimation`, `pose_refinement`, `AbsolutePoseEstimationOptions`, `AbsolutePoseRefinementOptions`,
-`rig_absolute_pose_estimation`)
-resolves to pycolmap_amd's MI355X implementation.  Only what SURVEY.md section 8 and DESIGN.md sections 10 to 13 put in
+`rig_absolute_pose_estimation`) and of image undistortion (`undistort_images`, `UndistortCameraOptions`, `CopyType`, with
+the building blocks `undistort_camera` and `undistort_image`)
+resolves to pycolmap_amd's MI355X implementation.  Only what SURVEY.md section 8 and DESIGN.md sections 10 to 14 put in
 scope exists;
 anything else raises AttributeError naming this package, so that a script reaching for `import_images`, SfM or MVS
 fails at the attribute, not later."""
@@ -18,4 +19,4 @@ globals().update({n: getattr(_impl, n) for n in _PUBLIC})
 
 def __getattr__(name):
     raise AttributeError(f"pycolmap.{name} is outside pycolmap_amd's scope (SIFT feature extraction, exhaustive / sequential "
-                         f"matching + two-view verification, known-pose triangulation, absolute pose behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}")
+                         f"matching + two-view verification, known-pose triangulation, absolute pose, image undistortion behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}")

@@ -15,7 +15,7 @@ __version__ = "0.1.0"
 
 try:  # the compiled host layer; absent only before `python -m pycolmap_amd.build`
     from ._pycolmap import (  # noqa: F401
-        AbsolutePoseEstimationOptions, AbsolutePoseRefinementOptions, COLMAP_build, COLMAP_version, Camera, CameraMode, CameraModelId, Database, DatabaseTransaction, Device, EstimateTriangulationOptions, ExhaustiveMatchingOptions, Image, ImageReaderOptions, Normalization, PointData, RANSACOptions, Rigid3d,
+        AbsolutePoseEstimationOptions, AbsolutePoseRefinementOptions, COLMAP_build, COLMAP_version, Camera, CopyType, UndistortCameraOptions, undistort_camera, undistort_image, CameraMode, CameraModelId, Database, DatabaseTransaction, Device, EstimateTriangulationOptions, ExhaustiveMatchingOptions, Image, ImageReaderOptions, Normalization, PointData, RANSACOptions, Rigid3d,
         Rotation3d, Sift, SiftExtractionOptions,
         SequentialMatchingOptions, SiftMatchingOptions, SpatialMatchingOptions, TwoViewGeometry, TwoViewGeometryConfiguration,
         VocabTreeMatchingOptions,
@@ -25,6 +25,7 @@ try:  # the compiled host layer; absent only before `python -m pycolmap_amd.buil
         match_spatial, match_vocabtree, pose_refinement, rig_absolute_pose_estimation, squared_sampson_error, verify_matches,
     )
     from ._extraction import extract_features  # noqa: F401
+    from ._undistortion import _undistort_plan, undistort_images  # noqa: F401
     _HOST_LAYER_ERROR = None
 except ImportError as _e:  # pragma: no cover - exercised only on an unbuilt tree
     _HOST_LAYER_ERROR = _e

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "amc_allgather_pair_records", "amc_gathered_records_free", "amc_allgather_inlier_tables", "amc_ctx_last_timeline",
     "amc_upload_matches",
     "amc_estimate_rig_absolute_poses", "amc_rigpose_result_free",
+    "amc_undistort_opts_default", "amc_undistort_camera", "amc_undistort_points", "amc_undistort_images",
 ]
 COMM_ID_BYTES = 128
 RANSAC_F, RANSAC_H, RANSAC_E = 0, 1, 2
@@ -270,6 +271,80 @@ SIFT_NORMALIZATIONS = {"L1_ROOT": 0, "L2": 1}
 SIFT_STAGES = ("scale_space", "detection", "orientation", "descriptors")
 
 
+class UndistortOpts(C.Structure):  # amc_undistort_opts (include/amc_undistort.h)
+    _fields_ = [("blank_pixels", C.c_double), ("min_scale", C.c_double), ("max_scale", C.c_double),
+                ("max_image_size", C.c_int32), ("_pad", C.c_int32), ("roi_min_x", C.c_double), ("roi_min_y", C.c_double),
+                ("roi_max_x", C.c_double), ("roi_max_y", C.c_double)]
+
+
+class UndistortCam(C.Structure):  # amc_undistort_cam
+    _fields_ = [("model", C.c_int32), ("_pad", C.c_int32), ("width", C.c_uint64), ("height", C.c_uint64),
+                ("params", C.c_double * 12)]
+
+
+class UndistortImage(C.Structure):  # amc_undistort_image
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_uint64), ("channels", C.c_int32), ("_pad", C.c_int32),
+                ("src_camera", UndistortCam), ("dst_camera", UndistortCam), ("dst", C.c_void_p)]
+
+
+class UndistortResult(C.Structure):  # amc_undistort_result
+    _fields_ = [("device_ms", C.c_double), ("kernel_ms", C.c_double), ("num_batches", C.c_uint32),
+                ("num_resized", C.c_uint32)]
+
+
+CAMERA_MODEL_IDS = {"SIMPLE_PINHOLE": 0, "PINHOLE": 1, "SIMPLE_RADIAL": 2, "RADIAL": 3, "OPENCV": 4, "OPENCV_FISHEYE": 5,
+                    "FULL_OPENCV": 6, "FOV": 7, "SIMPLE_RADIAL_FISHEYE": 8, "RADIAL_FISHEYE": 9, "THIN_PRISM_FISHEYE": 10}
+CAMERA_NUM_PARAMS = [3, 4, 4, 5, 8, 8, 12, 5, 4, 5, 12]
+
+
+def _undistort_cam(camera) -> UndistortCam:
+    """(model name or id, width, height, params) -> amc_undistort_cam; the parameter count is checked here (the C
+    struct has room for 12 and cannot tell)."""
+    model, width, height, params = camera
+    mid = CAMERA_MODEL_IDS[model] if isinstance(model, str) else int(model)
+    p = [float(v) for v in params]
+    if 0 <= mid < len(CAMERA_NUM_PARAMS) and len(p) != CAMERA_NUM_PARAMS[mid]:
+        raise ValueError(f"camera model {model} takes {CAMERA_NUM_PARAMS[mid]} parameters, got {len(p)}")
+    c = UndistortCam()
+    c.model, c.width, c.height = mid, int(width), int(height)
+    for i, v in enumerate(p[:12]):
+        c.params[i] = v
+    return c
+
+
+def _undistort_cam_tuple(c: UndistortCam):
+    n = CAMERA_NUM_PARAMS[c.model]
+    return (c.model, int(c.width), int(c.height), np.array(c.params[:n], dtype=np.float64))
+
+
+def undistort_options(**kw) -> UndistortOpts:
+    """UndistortCameraOptions() with keyword overrides."""
+    o = UndistortOpts()
+    load().amc_undistort_opts_default(C.byref(o))
+    for k, v in kw.items():
+        if k.startswith("_") or k not in dict(UndistortOpts._fields_):
+            raise ValueError(f"undistort options: unknown option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def undistort_camera(camera, **opts):
+    """amc_undistort_camera (a host computation, no device): camera = (model, width, height, params) ->
+    (1 = PINHOLE, width, height, params (4,) float64)."""
+    out = UndistortCam()
+    _check(load().amc_undistort_camera(C.byref(undistort_options(**opts)), C.byref(_undistort_cam(camera)), C.byref(out)))
+    return _undistort_cam_tuple(out)
+
+
+def undistort_points(camera, undistorted, points) -> np.ndarray:
+    """amc_undistort_points (host): undistorted.ImgFromCam(camera.CamFromImg(xy)) of N x 2 points."""
+    xy = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+    out = np.empty_like(xy)
+    _check(load().amc_undistort_points(C.byref(_undistort_cam(camera)), C.byref(_undistort_cam(undistorted)), xy.shape[0],
+                                       xy.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 class RansacOpts(C.Structure):
     _fields_ = [("max_error", C.c_double), ("min_inlier_ratio", C.c_double),
                 ("confidence", C.c_double), ("dyn_num_trials_multiplier", C.c_double),
@@ -401,6 +476,16 @@ def load() -> C.CDLL:
         lib.amc_triangulate_tracks.restype = C.c_int
         lib.amc_tri_result_free.argtypes = [C.POINTER(TriResult)]
         lib.amc_tri_result_free.restype = None
+    if hasattr(lib, "amc_undistort_images"):  # (absent from a library built from an older revision)
+        lib.amc_undistort_opts_default.argtypes = [C.POINTER(UndistortOpts)]
+        lib.amc_undistort_opts_default.restype = None
+        lib.amc_undistort_camera.argtypes = [C.POINTER(UndistortOpts), C.POINTER(UndistortCam), C.POINTER(UndistortCam)]
+        lib.amc_undistort_camera.restype = C.c_int
+        lib.amc_undistort_points.argtypes = [C.POINTER(UndistortCam), C.POINTER(UndistortCam), C.c_size_t, C.c_void_p,
+                                             C.c_void_p]
+        lib.amc_undistort_points.restype = C.c_int
+        lib.amc_undistort_images.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(UndistortResult)]
+        lib.amc_undistort_images.restype = C.c_int
     lib.amc_get_acos_lut.argtypes = [C.c_void_p, C.c_void_p]
     lib.amc_tvg_opts_default.argtypes = [C.POINTER(TvgOpts)]
     lib.amc_tvg_opts_default.restype = None
@@ -871,6 +956,36 @@ class Context:
         finally:
             self._lib.amc_tri_result_free(C.byref(res))
         return xyz, ok, mask, stats
+
+    def undistort_images(self, images, src_cameras, dst_cameras):
+        """amc_undistort_images: warp every image from its source camera onto its PINHOLE target.
+
+        images: H x W or H x W x 3 uint8 arrays (the last axis contiguous, rows at any stride); cameras: (model name or
+        id, width, height, params) each.  Returns (list of target arrays, stats dict with device_ms, kernel_ms,
+        num_batches, num_resized)."""
+        n = len(images)
+        if len(src_cameras) != n or len(dst_cameras) != n:
+            raise ValueError(f"undistort_images: {n} images, {len(src_cameras)} source and {len(dst_cameras)} target cameras")
+        arr = (UndistortImage * max(n, 1))()
+        keep, outs = [], []
+        for i, im in enumerate(images):
+            ok = (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim in (2, 3) and im.size > 0
+                  and (im.ndim == 2 or im.shape[2] in (1, 3)))
+            if not ok:
+                raise ValueError(f"undistort_images: image {i} must be a non-empty H x W or H x W x 3 uint8 array")
+            ch = 1 if im.ndim == 2 else im.shape[2]
+            packed = im.strides[-1] == 1 and (im.ndim == 2 or im.strides[1] == ch) and im.strides[0] >= im.shape[1] * ch
+            a = im if packed else np.ascontiguousarray(im)
+            keep.append(a)
+            dc = _undistort_cam(dst_cameras[i])
+            out = np.empty((int(dc.height), int(dc.width)) + ((ch,) if im.ndim == 3 else ()), dtype=np.uint8)
+            outs.append(out)
+            arr[i] = UndistortImage(a.ctypes.data, a.strides[0], ch, 0, _undistort_cam(src_cameras[i]), dc,
+                                    out.ctypes.data if out.size else None)
+        res = UndistortResult()
+        _check(self._lib.amc_undistort_images(self._h, n, C.cast(arr, C.c_void_p), C.byref(res)))
+        return outs, {"device_ms": res.device_ms, "kernel_ms": res.kernel_ms, "num_batches": int(res.num_batches),
+                      "num_resized": int(res.num_resized)}
 
     def match_pairs(self, slot1, slot2, max_ratio: float = 0.8, max_distance: float = 0.7,
                     cross_check: bool = True, kernel: str = "auto", copy: bool = True):

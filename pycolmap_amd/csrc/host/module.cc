@@ -38,6 +38,7 @@
 #include "tri_host.h"
 #include "abspose_host.h"
 #include "rigpose_host.h"
+#include "undistort_host.h"
 
 namespace py = pybind11;
 using namespace pybind11::literals;
@@ -978,6 +979,73 @@ PYBIND11_MODULE(_pycolmap, m) {
           "fifth argument are shifted: cameras= takes the camera indices, camera_idxs= the cams_from_rig list and "
           "cams_from_rig= the cameras.");
 
+    // ---- undistort_images (reference: pycolmap/pipeline/images.h:96-148, 203-261; undistort_host.h) ------------------------
+    py::class_<UndistortCameraOptions> PyUndistOpts(m, "UndistortCameraOptions");
+    PyUndistOpts.def(py::init<>())
+        .def_readwrite("blank_pixels", &UndistortCameraOptions::blank_pixels,
+                       "The amount of blank pixels in the undistorted image in the range [0, 1].")
+        .def_readwrite("min_scale", &UndistortCameraOptions::min_scale,
+                       "Minimum scale change of camera used to satisfy the blank pixel constraint.")
+        .def_readwrite("max_scale", &UndistortCameraOptions::max_scale,
+                       "Maximum scale change of camera used to satisfy the blank pixel constraint.")
+        .def_readwrite("max_image_size", &UndistortCameraOptions::max_image_size,
+                       "Maximum image size in terms of width or height of the undistorted camera.")
+        .def_readwrite("roi_min_x", &UndistortCameraOptions::roi_min_x)
+        .def_readwrite("roi_min_y", &UndistortCameraOptions::roi_min_y)
+        .def_readwrite("roi_max_x", &UndistortCameraOptions::roi_max_x)
+        .def_readwrite("roi_max_y", &UndistortCameraOptions::roi_max_y);
+    MakeDataclass(PyUndistOpts, {"blank_pixels", "min_scale", "max_scale", "max_image_size", "roi_min_x", "roi_min_y",
+                                 "roi_max_x", "roi_max_y"});
+    py::enum_<CopyType> PyCopyType(m, "CopyType");
+    PyCopyType.value("copy", CopyType::COPY).value("soft-link", CopyType::SOFT_LINK).value("hard-link", CopyType::HARD_LINK);
+    PyCopyType.def(py::init([](const std::string& s) {
+        if (s == "copy") return CopyType::COPY;
+        if (s == "soft-link") return CopyType::SOFT_LINK;
+        if (s == "hard-link") return CopyType::HARD_LINK;
+        throw py::value_error("Invalid string value " + s + " for enum CopyType");
+    }));
+    py::implicitly_convertible<std::string, CopyType>();
+    m.def("undistort_camera", &UndistortCameraPy, "options"_a, "camera"_a,
+          "Undistort camera: the PINHOLE camera of the undistorted image (pycolmap_amd extension under a later release's name).");
+    m.def("undistort_image", &UndistortImagePy, "options"_a, "image"_a, "camera"_a,
+          "Undistort an H x W or H x W x 3 uint8 image: (undistorted image, undistorted camera).");
+    auto plan_camera = [](const ModelCamera& c) {
+        PyCamera out;
+        out.camera_id = c.camera_id;
+        out.model = c.model;
+        out.width = c.width;
+        out.height = c.height;
+        out.params = c.params;
+        return out;
+    };
+    m.def(
+        "_undistort_plan",
+        [plan_camera](const py::object& input_path, const std::vector<std::string>& image_list,
+                      const UndistortCameraOptions& options) {
+            const SparseModel model = ReadSparseModel(PathToString(input_path));
+            const std::vector<UndistortPlanItem> plan =
+                UndistortPlan(model, image_list, options, [](const std::string& msg) {
+                    Logging::Write(Logging::WARNING, "undistort_images", 0, msg);
+                });
+            py::list out;
+            for (const UndistortPlanItem& it : plan)
+                out.append(py::dict("name"_a = it.name, "image_id"_a = it.image_id, "camera"_a = plan_camera(it.camera),
+                                    "undistorted_camera"_a = FromAmcCam(it.undistorted, it.camera.camera_id, false),
+                                    "copy"_a = it.copy));
+            return out;
+        },
+        "input_path"_a, "image_list"_a = std::vector<std::string>(), "undistort_options"_a = UndistortCameraOptions(),
+        "Per image of an undistort_images call: name, image_id, camera, undistorted_camera, copy (test hook)");
+    m.def(
+        "_write_undistorted_model",
+        [](const py::object& input_path, const py::object& output_path, const UndistortCameraOptions& options) {
+            const SparseModel model = ReadSparseModel(PathToString(input_path));
+            WriteSparseModelBin(PathToString(output_path), UndistortModel(model, options));
+            return py::make_tuple(model.cameras.size(), model.images.size(), model.points3D.size());
+        },
+        "input_path"_a, "output_path"_a, "undistort_options"_a = UndistortCameraOptions(),
+        "Read the sparse model at input_path, undistort it, write cameras / images / points3D .bin into output_path");
+
     // ---- Database ---------------------------------------------------------------------------
     py::class_<Database>(m, "Database")
         .def(py::init([](const py::object& path) {
@@ -1232,5 +1300,6 @@ PYBIND11_MODULE(_pycolmap, m) {
     m.def("match_vocabtree", unsupported("match_vocabtree"));
     m.attr("_last_stats") = py::dict();
     m.def("last_run_stats", []() { return py::module_::import("pycolmap_amd._pycolmap").attr("_last_stats"); },
-          "Timing / counters of the most recent match_* / verify_matches call (pycolmap_amd extension).");
+          "Timing / counters of the most recent match_* / verify_matches / extract_features / undistort_images call\n"
+          "(pycolmap_amd extension).");
 }

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "amc_upload_matches",
     "amc_estimate_rig_absolute_poses", "amc_rigpose_result_free",
     "amc_undistort_opts_default", "amc_undistort_camera", "amc_undistort_points", "amc_undistort_images",
+    "amc_ba_opts_default", "amc_bundle_adjust",
 ]
 COMM_ID_BYTES = 128
 RANSAC_F, RANSAC_H, RANSAC_E = 0, 1, 2
@@ -198,6 +199,93 @@ def abspose_inputs(offsets, camera_models, camera_params, points2D, points3D):
         raise ValueError(f"absolute poses: {n} correspondences by offsets, {p2.shape[0]} points2D, "
                          f"{p3.shape[0]} points3D")
     return off, models, prm, p2, p3
+
+
+class BaOpts(C.Structure):  # amc_ba_opts (include/amc_ba.h)
+    _fields_ = [("loss_function_type", C.c_int32), ("max_num_iterations", C.c_int32),
+                ("max_linear_solver_iterations", C.c_int32), ("max_num_consecutive_invalid_steps", C.c_int32),
+                ("loss_function_scale", C.c_double), ("function_tolerance", C.c_double),
+                ("gradient_tolerance", C.c_double), ("parameter_tolerance", C.c_double)]
+
+
+class BaProblem(C.Structure):  # amc_ba_problem
+    _fields_ = [("num_cameras", C.c_size_t), ("camera_models", C.c_void_p), ("camera_params", C.c_void_p),
+                ("camera_const", C.c_void_p), ("num_images", C.c_size_t), ("image_cameras", C.c_void_p),
+                ("qvec", C.c_void_p), ("tvec", C.c_void_p), ("pose_const", C.c_void_p), ("num_points", C.c_size_t),
+                ("xyz", C.c_void_p), ("num_observations", C.c_size_t), ("obs_image", C.c_void_p),
+                ("obs_point", C.c_void_p), ("obs_xy", C.c_void_p)]
+
+
+class BaResult(C.Structure):  # amc_ba_result
+    _fields_ = [("num_images", C.c_uint64), ("num_points", C.c_uint64), ("num_observations", C.c_uint64),
+                ("num_variable_parameters", C.c_uint64), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("num_successful_steps", C.c_uint32), ("num_unsuccessful_steps", C.c_uint32),
+                ("num_pcg_iterations", C.c_uint32), ("num_pcg_stops_residual", C.c_uint32),
+                ("num_pcg_stops_cap", C.c_uint32), ("termination", C.c_int32), ("host_ms", C.c_double),
+                ("device_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
+BA_LOSSES = {"TRIVIAL": 0, "SOFT_L1": 1, "CAUCHY": 2}
+BA_TERMINATIONS = ("FUNCTION_TOLERANCE", "PARAMETER_TOLERANCE", "GRADIENT_TOLERANCE", "MAX_ITERATIONS", "MIN_RADIUS",
+                   "INVALID_STEPS", "NOTHING_TO_REFINE")
+BA_PCG_TOLERANCE = 1e-8
+
+
+def ba_options(options=None) -> "BaOpts":
+    """amc_ba_opts at its defaults (COLMAP 3.9.1's BundleAdjustmentOptions, no library needed) with the given fields
+    replaced; loss_function_type may be a name; an unknown field raises ValueError."""
+    o = BaOpts()
+    for k, v in dict(loss_function_type=0, max_num_iterations=100, max_linear_solver_iterations=200,
+                     max_num_consecutive_invalid_steps=10, loss_function_scale=1.0, function_tolerance=0.0,
+                     gradient_tolerance=0.0, parameter_tolerance=0.0).items():
+        setattr(o, k, v)
+    for k, v in (options or {}).items():
+        if k not in dict(BaOpts._fields_):
+            raise ValueError(f"unknown bundle adjustment option {k!r}")
+        if k == "loss_function_type" and isinstance(v, str):
+            if v.upper() not in BA_LOSSES:
+                raise ValueError(f"unknown loss function type {v!r}")
+            v = BA_LOSSES[v.upper()]
+        setattr(o, k, type(getattr(o, k))(v))
+    return o
+
+
+def ba_inputs(camera_models, camera_params, camera_const, image_cameras, qvec, tvec, pose_const, xyz, obs_image,
+              obs_point, obs_xy):
+    """The flat problem of amc_bundle_adjust as contiguous arrays (copies: the caller's arrays are not touched):
+    models (C,) int32, params (C, 12), camera_const (C, 12) uint8, image_cameras (I,) uint32, qvec (I, 4) x y z w,
+    tvec (I, 3), pose_const (I, 6) uint8, xyz (P, 3), obs_image / obs_point (N,) uint32, obs_xy (N, 2)."""
+    models = np.array(camera_models, dtype=np.int32).reshape(-1)
+    nc = models.size
+    if len(camera_params) != nc:
+        raise ValueError(f"bundle adjustment: {nc} camera models, {len(camera_params)} parameter sets")
+    prm = np.zeros((nc, 12), np.float64)
+    for i, p in enumerate(camera_params):
+        p = np.asarray(p, dtype=np.float64).reshape(-1)
+        if p.size > 12:
+            raise ValueError(f"bundle adjustment: camera {i} has {p.size} parameters (at most 12)")
+        prm[i, :p.size] = p
+    cc = np.ones((nc, 12), np.uint8)
+    for i, m in enumerate(camera_const):
+        m = np.asarray(m).reshape(-1)
+        cc[i, :min(m.size, 12)] = m[:12] != 0
+    icam = np.array(image_cameras, dtype=np.int64).reshape(-1)
+    ni = icam.size
+    q = np.array(qvec, dtype=np.float64).reshape(-1, 4)
+    t = np.array(tvec, dtype=np.float64).reshape(-1, 3)
+    pc = (np.array(pose_const).reshape(-1, 6) != 0).astype(np.uint8)
+    X = np.array(xyz, dtype=np.float64).reshape(-1, 3)
+    oi = np.array(obs_image, dtype=np.int64).reshape(-1)
+    op = np.array(obs_point, dtype=np.int64).reshape(-1)
+    xy = np.array(obs_xy, dtype=np.float64).reshape(-1, 2)
+    if q.shape[0] != ni or t.shape[0] != ni or pc.shape[0] != ni or op.size != oi.size or xy.shape[0] != oi.size:
+        raise ValueError(f"bundle adjustment: {ni} images by image_cameras, {q.shape[0]} rotations, {t.shape[0]} "
+                         f"translations, {pc.shape[0]} pose masks; {oi.size} observations by obs_image, {op.size} "
+                         f"point indices, {xy.shape[0]} pixels")
+    for name, a in (("image_cameras", icam), ("obs_image", oi), ("obs_point", op)):
+        if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+            raise ValueError(f"bundle adjustment: {name} has an index outside 0 .. 2^32 - 1")
+    return (models, prm, cc, icam.astype(np.uint32), q, t, pc, X, oi.astype(np.uint32), op.astype(np.uint32), xy)
 
 
 class RigPoseResult(C.Structure):  # amc_rigpose_result (include/amc_rigpose.h)
@@ -468,6 +556,11 @@ def load() -> C.CDLL:
         lib.amc_estimate_rig_absolute_poses.restype = C.c_int
         lib.amc_rigpose_result_free.argtypes = [C.POINTER(RigPoseResult)]
         lib.amc_rigpose_result_free.restype = None
+    if hasattr(lib, "amc_bundle_adjust"):  # (absent from a library built from an older revision)
+        lib.amc_ba_opts_default.argtypes = [C.POINTER(BaOpts)]
+        lib.amc_ba_opts_default.restype = None
+        lib.amc_bundle_adjust.argtypes = [C.c_void_p, C.POINTER(BaProblem), C.POINTER(BaOpts), C.POINTER(BaResult)]
+        lib.amc_bundle_adjust.restype = C.c_int
     if hasattr(lib, "amc_triangulate_tracks"):  # (absent from a library built from an older revision)
         lib.amc_tri_opts_default.argtypes = [C.POINTER(TriOpts)]
         lib.amc_tri_opts_default.restype = None
@@ -882,6 +975,28 @@ class Context:
                 out["covariance"] = a(res.covariance, (nq, 36)).reshape(nq, 6, 6)
         finally:
             self._lib.amc_abspose_result_free(C.byref(res))
+        return out
+
+    def bundle_adjust(self, camera_models, camera_params, camera_const, image_cameras, qvec, tvec, pose_const, xyz,
+                      obs_image, obs_point, obs_xy, options=None):
+        """amc_bundle_adjust: Levenberg-Marquardt over every pose, point and camera at once.
+        camera_models (C,), camera_params: C parameter vectors, camera_const (C, <= 12) non-zero = constant;
+        image_cameras (I,) camera indices, qvec (I, 4) x y z w, tvec (I, 3), pose_const (I, 6) over the tangent
+        (rotation 3, translation 3); xyz (P, 3); obs_image / obs_point (N,), obs_xy (N, 2) pixels.  options: a dict of
+        amc_ba_opts fields.  The inputs are not modified.  Returns a dict: camera_params (C, 12), qvec, tvec, xyz and
+        the statistics of amc_ba_result (termination as a name)."""
+        models, prm, cc, icam, q, t, pc, X, oi, op, xy = ba_inputs(camera_models, camera_params, camera_const,
+                                                                   image_cameras, qvec, tvec, pose_const, xyz,
+                                                                   obs_image, obs_point, obs_xy)
+        o = ba_options(options)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        pb = BaProblem(models.size, ptr(models), ptr(prm), ptr(cc), icam.size, ptr(icam), ptr(q), ptr(t), ptr(pc),
+                       X.shape[0], ptr(X), oi.size, ptr(oi), ptr(op), ptr(xy))
+        res = BaResult()
+        _check(self._lib.amc_bundle_adjust(self._h, C.byref(pb), C.byref(o), C.byref(res)))
+        out = {k: getattr(res, k) for k, _ in BaResult._fields_}
+        out["termination"] = BA_TERMINATIONS[res.termination]
+        out.update(camera_params=prm, qvec=q, tvec=t, xyz=X)
         return out
 
     def estimate_rig_absolute_poses(self, offsets, camera_offsets, camera_models, camera_params, cams_from_rig,

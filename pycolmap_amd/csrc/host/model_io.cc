@@ -253,6 +253,9 @@ const ModelCamera* SparseModel::FindCamera(uint32_t camera_id) const {
     return nullptr;
 }
 
+SparseModel ReadSparseModelBin(const std::string& dir) { return ReadBin(dir); }
+SparseModel ReadSparseModelTxt(const std::string& dir) { return ReadTxt(dir); }
+
 SparseModel ReadSparseModel(const std::string& dir) {
     const bool bin = Exists(dir + "/cameras.bin") && Exists(dir + "/images.bin") && Exists(dir + "/points3D.bin");
     const bool txt = Exists(dir + "/cameras.txt") && Exists(dir + "/images.txt") && Exists(dir + "/points3D.txt");

@@ -52,6 +52,9 @@ int ModelIdFromName(const std::string& name);
 // Reconstruction::Read: the three .bin files when all of them exist, else the three .txt files.  Throws
 // std::invalid_argument naming the file and what is wrong with it.
 SparseModel ReadSparseModel(const std::string& dir);
+// Reconstruction::ReadBinary / ReadText: one format, whatever else the directory holds
+SparseModel ReadSparseModelBin(const std::string& dir);
+SparseModel ReadSparseModelTxt(const std::string& dir);
 // Reconstruction::WriteBinary into an existing directory
 void WriteSparseModelBin(const std::string& dir, const SparseModel& model);
 

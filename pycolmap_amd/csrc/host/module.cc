@@ -39,6 +39,8 @@
 #include "abspose_host.h"
 #include "rigpose_host.h"
 #include "undistort_host.h"
+#include "ba_host.h"
+#include "reconstruction.h"
 
 namespace py = pybind11;
 using namespace pybind11::literals;
@@ -793,11 +795,36 @@ PYBIND11_MODULE(_pycolmap, m) {
     // Image: the database-facing part of /root/reference/pycolmap/scene/image.h:74-130 (identifiers, name, pose and pose
     // prior, the keypoints it was constructed with); the reconstruction bookkeeping (points3D, observations) belongs
     // to COLMAP's mapper and is not part of this library
+    struct PyPoint2D {
+        std::array<double, 2> xy{{0.0, 0.0}};
+        uint64_t point3D_id = kInvalidPoint3DId;
+    };
+    py::class_<PyPoint2D>(m, "Point2D")
+        .def(py::init<>())
+        .def(py::init([](const std::array<double, 2>& xy, uint64_t point3D_id) {
+                 PyPoint2D p;
+                 p.xy = xy;
+                 p.point3D_id = point3D_id;
+                 return p;
+             }),
+             "xy"_a, "point3D_id"_a = kInvalidPoint3DId)
+        .def_readwrite("xy", &PyPoint2D::xy)
+        .def_readwrite("point3D_id", &PyPoint2D::point3D_id)
+        .def("has_point3D", [](const PyPoint2D& p) { return p.point3D_id != kInvalidPoint3DId; })
+        .def("__copy__", [](const PyPoint2D& p) { return PyPoint2D(p); })
+        .def("__deepcopy__", [](const PyPoint2D& p, const py::dict&) { return PyPoint2D(p); })
+        .def("__repr__", [](const PyPoint2D& p) {
+            std::ostringstream ss;
+            ss << "Point2D(xy=[" << p.xy[0] << ", " << p.xy[1] << "], point3D_id="
+               << (p.point3D_id != kInvalidPoint3DId ? std::to_string(p.point3D_id) : "Invalid") << ")";
+            return ss.str();
+        });
     struct PyImage {
         uint32_t image_id = 0xFFFFFFFFu, camera_id = 0xFFFFFFFFu;  // kInvalidImageId / kInvalidCameraId
         std::string name;
         PyRigid3d cam_from_world, cam_from_world_prior;
         std::vector<std::array<double, 2>> keypoints;
+        std::vector<PyPoint2D> points2D;  // the reconstruction's view of the image (Reconstruction, bundle_adjustment)
         PyImage() {
             const double nan = std::nan("");  // Image(): the prior is "unknown"
             cam_from_world_prior.rotation.xyzw = {{nan, nan, nan, nan}};
@@ -875,15 +902,430 @@ PYBIND11_MODULE(_pycolmap, m) {
              "Check whether identifier of camera has been set.")
         .def("num_points2D", [](const PyImage& im) { return im.keypoints.size(); },
              "Get the number of image points (keypoints).")
+        .def_readwrite("points2D", &PyImage::points2D,
+                       "The image's points with their 3D point ids (a copy of the list; assign to change it).")
+        .def("num_points3D", [](const PyImage& im) {
+            size_t n = 0;
+            for (const PyPoint2D& p : im.points2D) n += p.point3D_id != kInvalidPoint3DId;
+            return n;
+        }, "Get the number of triangulated points2D.")
         .def("__copy__", [](const PyImage& im) { return PyImage(im); })
         .def("__deepcopy__", [](const PyImage& im, const py::dict&) { return PyImage(im); })
         .def("__repr__", [](const PyImage& im) {
             std::ostringstream ss;
             ss << "Image(image_id=" << (im.image_id != 0xFFFFFFFFu ? std::to_string(im.image_id) : "Invalid")
                << ", camera_id=" << (im.camera_id != 0xFFFFFFFFu ? std::to_string(im.camera_id) : "Invalid") << ", name=\""
-               << im.name << "\", triangulated=0/" << im.keypoints.size() << ")";
+               << im.name << "\", triangulated=";
+            size_t tri = 0;
+            for (const PyPoint2D& p : im.points2D) tri += p.point3D_id != kInvalidPoint3DId;
+            ss << tri << "/" << (tri ? im.points2D.size() : im.keypoints.size()) << ")";
             return ss.str();
         });
+
+    // ---- Reconstruction, bundle_adjustment (/root/reference/pycolmap/scene/reconstruction.h, pipeline/sfm.h:95-103,
+    // 259-362): the minimal subset.  The three maps are Python dicts of Camera / Image / Point3D objects
+    // in file order, so they have reference semantics; every operation converts them to model_io's structs
+    // (reconstruction.h, ba_host.h do the work) and writes the outcome back into the same objects. ----------------------
+    struct PyTrackElement {
+        uint32_t image_id = 0xFFFFFFFFu, point2D_idx = 0xFFFFFFFFu;
+    };
+    struct PyTrack {
+        std::vector<PyTrackElement> elements;
+    };
+    struct PyPoint3D {
+        std::array<double, 3> xyz{{0.0, 0.0, 0.0}};
+        std::array<uint8_t, 3> color{{0, 0, 0}};
+        double error = -1.0;
+        PyTrack track;
+    };
+    py::class_<PyTrackElement>(m, "TrackElement")
+        .def(py::init<>())
+        .def(py::init([](uint32_t image_id, uint32_t point2D_idx) { return PyTrackElement{image_id, point2D_idx}; }),
+             "image_id"_a, "point2D_idx"_a)
+        .def_readwrite("image_id", &PyTrackElement::image_id)
+        .def_readwrite("point2D_idx", &PyTrackElement::point2D_idx)
+        .def("__copy__", [](const PyTrackElement& e) { return PyTrackElement(e); })
+        .def("__deepcopy__", [](const PyTrackElement& e, const py::dict&) { return PyTrackElement(e); })
+        .def("__repr__", [](const PyTrackElement& e) {
+            return "TrackElement(image_id=" + std::to_string(e.image_id) + ", point2D_idx=" + std::to_string(e.point2D_idx) + ")";
+        });
+    py::class_<PyTrack>(m, "Track")
+        .def(py::init<>())
+        .def(py::init([](const std::vector<PyTrackElement>& elements) { return PyTrack{elements}; }), "elements"_a)
+        .def_readwrite("elements", &PyTrack::elements)
+        .def("length", [](const PyTrack& t) { return t.elements.size(); })
+        .def("add_element", [](PyTrack& t, uint32_t image_id, uint32_t point2D_idx) { t.elements.push_back({image_id, point2D_idx}); },
+             "image_id"_a, "point2D_idx"_a)
+        .def("__copy__", [](const PyTrack& t) { return PyTrack(t); })
+        .def("__deepcopy__", [](const PyTrack& t, const py::dict&) { return PyTrack(t); })
+        .def("__repr__", [](const PyTrack& t) { return "Track(length=" + std::to_string(t.elements.size()) + ")"; });
+    py::class_<PyPoint3D>(m, "Point3D")
+        .def(py::init<>())
+        .def_readwrite("xyz", &PyPoint3D::xyz)
+        .def_readwrite("color", &PyPoint3D::color)
+        .def_readwrite("error", &PyPoint3D::error)
+        .def_readwrite("track", &PyPoint3D::track)
+        .def("__copy__", [](const PyPoint3D& p) { return PyPoint3D(p); })
+        .def("__deepcopy__", [](const PyPoint3D& p, const py::dict&) { return PyPoint3D(p); })
+        .def("__repr__", [](const PyPoint3D& p) {
+            std::ostringstream ss;
+            ss << "Point3D(xyz=[" << p.xyz[0] << ", " << p.xyz[1] << ", " << p.xyz[2] << "], track=Track(length="
+               << p.track.elements.size() << "))";
+            return ss.str();
+        });
+
+    struct PyReconstruction {
+        py::dict cameras, images, points3D;
+    };
+    // the dicts as a plain model; a key that is not its object's id is a ValueError
+    auto to_model = [](const PyReconstruction& r) {
+        SparseModel m;
+        for (auto item : r.cameras) {
+            const PyCamera& c = item.second.cast<const PyCamera&>();
+            if (item.first.cast<uint32_t>() != c.camera_id) throw py::value_error("Reconstruction.cameras: a key differs from its camera's camera_id");
+            ModelCamera mc;
+            mc.camera_id = c.camera_id;
+            mc.model = c.model;
+            mc.width = c.width;
+            mc.height = c.height;
+            mc.params = c.params;
+            m.cameras.push_back(std::move(mc));
+        }
+        for (auto item : r.images) {
+            const PyImage& im = item.second.cast<const PyImage&>();
+            if (item.first.cast<uint32_t>() != im.image_id) throw py::value_error("Reconstruction.images: a key differs from its image's image_id");
+            ModelImage mi;
+            mi.image_id = im.image_id;
+            mi.camera_id = im.camera_id;
+            mi.name = im.name;
+            const auto& q = im.cam_from_world.rotation.xyzw;
+            mi.qvec[0] = q[3];
+            for (int k = 0; k < 3; ++k) mi.qvec[1 + k] = q[k];
+            for (int k = 0; k < 3; ++k) mi.tvec[k] = im.cam_from_world.translation[k];
+            for (const PyPoint2D& p : im.points2D) {
+                ModelPoint2D mp;
+                mp.x = p.xy[0];
+                mp.y = p.xy[1];
+                mp.point3D_id = p.point3D_id;
+                mi.points2D.push_back(mp);
+            }
+            m.images.push_back(std::move(mi));
+        }
+        for (auto item : r.points3D) {
+            const PyPoint3D& p = item.second.cast<const PyPoint3D&>();
+            ModelPoint3D mp;
+            mp.point3D_id = item.first.cast<uint64_t>();
+            for (int k = 0; k < 3; ++k) mp.xyz[k] = p.xyz[k];
+            for (int k = 0; k < 3; ++k) mp.rgb[k] = p.color[k];
+            mp.error = p.error;
+            for (const PyTrackElement& e : p.track.elements) mp.track.emplace_back(e.image_id, e.point2D_idx);
+            m.points3D.push_back(std::move(mp));
+        }
+        return m;
+    };
+    // a model read from files as fresh objects
+    auto from_model = [](PyReconstruction& r, const SparseModel& m) {
+        r.cameras = py::dict();
+        r.images = py::dict();
+        r.points3D = py::dict();
+        for (const ModelCamera& mc : m.cameras) {
+            PyCamera c;
+            c.camera_id = mc.camera_id;
+            c.model = mc.model;
+            c.width = mc.width;
+            c.height = mc.height;
+            c.params = mc.params;
+            r.cameras[py::int_(mc.camera_id)] = py::cast(c);
+        }
+        for (const ModelImage& mi : m.images) {
+            PyImage im;
+            im.image_id = mi.image_id;
+            im.camera_id = mi.camera_id;
+            im.name = mi.name;
+            im.cam_from_world.rotation.xyzw = {{mi.qvec[1], mi.qvec[2], mi.qvec[3], mi.qvec[0]}};
+            im.cam_from_world.translation = {{mi.tvec[0], mi.tvec[1], mi.tvec[2]}};
+            for (const ModelPoint2D& mp : mi.points2D) {
+                PyPoint2D p;
+                p.xy = {{mp.x, mp.y}};
+                p.point3D_id = mp.point3D_id;
+                im.points2D.push_back(p);
+            }
+            r.images[py::int_(mi.image_id)] = py::cast(im);
+        }
+        for (const ModelPoint3D& mp : m.points3D) {
+            PyPoint3D p;
+            p.xyz = {{mp.xyz[0], mp.xyz[1], mp.xyz[2]}};
+            p.color = {{mp.rgb[0], mp.rgb[1], mp.rgb[2]}};
+            p.error = mp.error;
+            for (const auto& e : mp.track) p.track.elements.push_back({e.first, e.second});
+            r.points3D[py::int_(mp.point3D_id)] = py::cast(p);
+        }
+    };
+    // the outcome of an operation on to_model(r) back into r's own objects: camera parameters, poses, the points2D's
+    // point ids, the points' positions and tracks; points the operation deleted leave the dict
+    auto update_from_model = [](PyReconstruction& r, const SparseModel& m) {
+        for (const ModelCamera& mc : m.cameras) r.cameras[py::int_(mc.camera_id)].cast<PyCamera&>().params = mc.params;
+        for (const ModelImage& mi : m.images) {
+            PyImage& im = r.images[py::int_(mi.image_id)].cast<PyImage&>();
+            im.cam_from_world.rotation.xyzw = {{mi.qvec[1], mi.qvec[2], mi.qvec[3], mi.qvec[0]}};
+            im.cam_from_world.translation = {{mi.tvec[0], mi.tvec[1], mi.tvec[2]}};
+            for (size_t k = 0; k < mi.points2D.size() && k < im.points2D.size(); ++k) im.points2D[k].point3D_id = mi.points2D[k].point3D_id;
+        }
+        py::dict kept;
+        for (const ModelPoint3D& mp : m.points3D) {
+            py::object obj = r.points3D[py::int_(mp.point3D_id)];
+            PyPoint3D& p = obj.cast<PyPoint3D&>();
+            p.xyz = {{mp.xyz[0], mp.xyz[1], mp.xyz[2]}};
+            p.track.elements.clear();
+            for (const auto& e : mp.track) p.track.elements.push_back({e.first, e.second});
+            kept[py::int_(mp.point3D_id)] = obj;
+        }
+        r.points3D.attr("clear")();
+        r.points3D.attr("update")(kept);  // the same dict object: references to rec.points3D stay valid
+    };
+    auto checked_model = [to_model](const PyReconstruction& r) {
+        SparseModel m = to_model(r);
+        const std::string bad = CheckModel(m);
+        if (!bad.empty()) throw py::value_error("Reconstruction: " + bad);
+        return m;
+    };
+    auto summary = [checked_model](const PyReconstruction& r) {
+        const SparseModel m = checked_model(r);
+        const size_t nobs = ComputeNumObservations(m);
+        std::ostringstream ss;
+        ss << "Reconstruction:\n\tnum_reg_images = " << m.images.size() << "\n\tnum_cameras = " << m.cameras.size()
+           << "\n\tnum_points3D = " << m.points3D.size() << "\n\tnum_observations = " << nobs
+           << "\n\tmean_track_length = " << ComputeMeanTrackLength(m) << "\n\tmean_observations_per_image = "
+           << (m.images.empty() ? 0.0 : static_cast<double>(nobs) / static_cast<double>(m.images.size()));
+        return ss.str();
+    };
+    auto read_into = [from_model](PyReconstruction& r, const std::string& path, int how) {
+        const SparseModel m = how == 0 ? ReadSparseModel(path) : how == 1 ? ReadSparseModelBin(path) : ReadSparseModelTxt(path);
+        const std::string bad = CheckModel(m);
+        if (!bad.empty()) throw py::value_error(path + ": " + bad);
+        from_model(r, m);
+    };
+    auto deep_copy = [](const PyReconstruction& r) {
+        const py::object deepcopy = py::module_::import("copy").attr("deepcopy");
+        PyReconstruction c;
+        c.cameras = deepcopy(r.cameras);
+        c.images = deepcopy(r.images);
+        c.points3D = deepcopy(r.points3D);
+        return c;
+    };
+    py::class_<PyReconstruction>(m, "Reconstruction")
+        .def(py::init<>())
+        .def(py::init([read_into](const std::string& path) {
+                 PyReconstruction r;
+                 read_into(r, path, 0);
+                 return r;
+             }),
+             "path"_a)
+        .def("read", [read_into](PyReconstruction& r, const std::string& path) { read_into(r, path, 0); }, "path"_a,
+             "Read the model from `path`: the three .bin files when all exist, else the three .txt files.")
+        .def("read_binary", [read_into](PyReconstruction& r, const std::string& path) { read_into(r, path, 1); }, "path"_a)
+        .def("read_text", [read_into](PyReconstruction& r, const std::string& path) { read_into(r, path, 2); }, "path"_a)
+        .def("write", [checked_model](const PyReconstruction& r, const std::string& path) { WriteSparseModelBin(path, checked_model(r)); },
+             "path"_a, "Write cameras.bin, images.bin and points3D.bin into the existing directory `path`, in the maps' order.")
+        .def("write_binary", [checked_model](const PyReconstruction& r, const std::string& path) { WriteSparseModelBin(path, checked_model(r)); },
+             "path"_a)
+        .def("num_cameras", [](const PyReconstruction& r) { return r.cameras.size(); })
+        .def("num_images", [](const PyReconstruction& r) { return r.images.size(); })
+        .def("num_reg_images", [](const PyReconstruction& r) { return r.images.size(); },
+             "Every image of this minimal Reconstruction is registered.")
+        .def("num_points3D", [](const PyReconstruction& r) { return r.points3D.size(); })
+        .def("reg_image_ids", [](const PyReconstruction& r) { return py::list(r.images.attr("keys")()); })
+        .def_property_readonly("cameras", [](const PyReconstruction& r) { return r.cameras; })
+        .def_property_readonly("images", [](const PyReconstruction& r) { return r.images; })
+        .def_property_readonly("points3D", [](const PyReconstruction& r) { return r.points3D; })
+        .def("add_camera", [](PyReconstruction& r, const py::object& camera) {
+                 const PyCamera& c = camera.cast<const PyCamera&>();
+                 c.CheckParams();
+                 if (r.cameras.contains(py::int_(c.camera_id))) throw py::value_error("add_camera: camera_id " + std::to_string(c.camera_id) + " exists");
+                 r.cameras[py::int_(c.camera_id)] = camera;
+             }, "camera"_a)
+        .def("add_image", [](PyReconstruction& r, const py::object& image) {
+                 const PyImage& im = image.cast<const PyImage&>();
+                 if (im.image_id == 0xFFFFFFFFu) throw py::value_error("add_image: the image has no image_id");
+                 if (r.images.contains(py::int_(im.image_id))) throw py::value_error("add_image: image_id " + std::to_string(im.image_id) + " exists");
+                 r.images[py::int_(im.image_id)] = image;
+             }, "image"_a)
+        .def("add_point3D", [](PyReconstruction& r, const std::array<double, 3>& xyz, const PyTrack& track,
+                               const std::array<uint8_t, 3>& color) {
+                 uint64_t id = 1;
+                 for (auto item : r.points3D) id = std::max<uint64_t>(id, item.first.cast<uint64_t>() + 1);
+                 for (const PyTrackElement& e : track.elements) {  // every element first, then the change
+                     if (!r.images.contains(py::int_(e.image_id))) throw py::value_error("add_point3D: image " + std::to_string(e.image_id) + " does not exist");
+                     const PyImage& im = r.images[py::int_(e.image_id)].cast<const PyImage&>();
+                     if (e.point2D_idx >= im.points2D.size()) throw py::value_error("add_point3D: image " + std::to_string(e.image_id) + " has no point2D " + std::to_string(e.point2D_idx));
+                     if (im.points2D[e.point2D_idx].point3D_id != kInvalidPoint3DId) throw py::value_error("add_point3D: point2D " + std::to_string(e.point2D_idx) + " of image " + std::to_string(e.image_id) + " already has a point3D");
+                 }
+                 for (const PyTrackElement& e : track.elements) r.images[py::int_(e.image_id)].cast<PyImage&>().points2D[e.point2D_idx].point3D_id = id;
+                 PyPoint3D p;
+                 p.xyz = xyz;
+                 p.color = color;
+                 p.track = track;
+                 r.points3D[py::int_(id)] = py::cast(p);
+                 return id;
+             }, "xyz"_a, "track"_a, "color"_a = std::array<uint8_t, 3>{{0, 0, 0}})
+        .def("compute_num_observations", [checked_model](const PyReconstruction& r) { return ComputeNumObservations(checked_model(r)); })
+        .def("compute_mean_track_length", [checked_model](const PyReconstruction& r) { return ComputeMeanTrackLength(checked_model(r)); })
+        .def("filter_observations_with_negative_depth", [checked_model, update_from_model](PyReconstruction& r) {
+                 SparseModel m = checked_model(r);
+                 const size_t n = FilterObservationsWithNegativeDepth(&m);
+                 update_from_model(r, m);
+                 return n;
+             })
+        .def("summary", summary)
+        .def("__repr__", [checked_model](const PyReconstruction& r) {
+            const SparseModel m = checked_model(r);
+            return "Reconstruction(num_reg_images=" + std::to_string(m.images.size()) + ", num_cameras=" + std::to_string(m.cameras.size()) +
+                   ", num_points3D=" + std::to_string(m.points3D.size()) + ", num_observations=" + std::to_string(ComputeNumObservations(m)) + ")";
+        })
+        .def("__copy__", deep_copy)
+        .def("__deepcopy__", [deep_copy](const PyReconstruction& r, const py::dict&) { return deep_copy(r); });
+
+    enum class LossFunctionType { TRIVIAL = 0, SOFT_L1 = 1, CAUCHY = 2 };
+    py::enum_<LossFunctionType> PyLoss(m, "LossFunctionType");
+    PyLoss.value("TRIVIAL", LossFunctionType::TRIVIAL).value("SOFT_L1", LossFunctionType::SOFT_L1).value("CAUCHY", LossFunctionType::CAUCHY);
+    PyLoss.def(py::init([](const std::string& s) {
+        if (s == "TRIVIAL") return LossFunctionType::TRIVIAL;
+        if (s == "SOFT_L1") return LossFunctionType::SOFT_L1;
+        if (s == "CAUCHY") return LossFunctionType::CAUCHY;
+        throw py::value_error("Invalid string value " + s + " for enum LossFunctionType");
+    }));
+    py::implicitly_convertible<std::string, LossFunctionType>();
+    struct CeresSolverOptions {
+        double function_tolerance = 0.0, gradient_tolerance = 0.0, parameter_tolerance = 0.0;  // COLMAP's BundleAdjustmentOptions
+        int max_num_iterations = 100, max_linear_solver_iterations = 200, max_num_consecutive_invalid_steps = 10,
+            max_consecutive_nonmonotonic_steps = 10;
+        bool minimizer_progress_to_stdout = false;
+        int num_threads = -1;
+    };
+    py::class_<CeresSolverOptions> PyCeres(m, "CeresSolverOptions");
+    PyCeres.def(py::init<>())
+        .def_readwrite("function_tolerance", &CeresSolverOptions::function_tolerance)
+        .def_readwrite("gradient_tolerance", &CeresSolverOptions::gradient_tolerance)
+        .def_readwrite("parameter_tolerance", &CeresSolverOptions::parameter_tolerance)
+        .def_readwrite("max_num_iterations", &CeresSolverOptions::max_num_iterations)
+        .def_readwrite("max_linear_solver_iterations", &CeresSolverOptions::max_linear_solver_iterations)
+        .def_readwrite("max_num_consecutive_invalid_steps", &CeresSolverOptions::max_num_consecutive_invalid_steps)
+        .def_readwrite("max_consecutive_nonmonotonic_steps", &CeresSolverOptions::max_consecutive_nonmonotonic_steps,
+                       "Accepted, no effect (DESIGN.md 15.9, B9).")
+        .def_readwrite("minimizer_progress_to_stdout", &CeresSolverOptions::minimizer_progress_to_stdout, "Accepted, no effect.")
+        .def_readwrite("num_threads", &CeresSolverOptions::num_threads, "Accepted, no effect: the solver runs on the GPU.");
+    MakeDataclass(PyCeres, {"function_tolerance", "gradient_tolerance", "parameter_tolerance", "max_num_iterations",
+                            "max_linear_solver_iterations", "max_num_consecutive_invalid_steps",
+                            "max_consecutive_nonmonotonic_steps", "minimizer_progress_to_stdout", "num_threads"});
+    struct BundleAdjustmentOptions {
+        LossFunctionType loss_function_type = LossFunctionType::TRIVIAL;
+        double loss_function_scale = 1.0;
+        bool refine_focal_length = true, refine_principal_point = false, refine_extra_params = true, refine_extrinsics = true,
+             print_summary = true;
+        int min_num_residuals_for_multi_threading = 50000;
+        CeresSolverOptions solver_options;
+    };
+    py::class_<BundleAdjustmentOptions> PyBaOpts(m, "BundleAdjustmentOptions");
+    PyBaOpts.def(py::init<>())
+        .def_readwrite("loss_function_type", &BundleAdjustmentOptions::loss_function_type, "Loss function types: Trivial (non-robust) and Cauchy (robust) loss.")
+        .def_readwrite("loss_function_scale", &BundleAdjustmentOptions::loss_function_scale, "Scaling factor determines residual at which robustification takes place.")
+        .def_readwrite("refine_focal_length", &BundleAdjustmentOptions::refine_focal_length, "Whether to refine the focal length parameter group.")
+        .def_readwrite("refine_principal_point", &BundleAdjustmentOptions::refine_principal_point, "Whether to refine the principal point parameter group.")
+        .def_readwrite("refine_extra_params", &BundleAdjustmentOptions::refine_extra_params, "Whether to refine the extra parameter group.")
+        .def_readwrite("refine_extrinsics", &BundleAdjustmentOptions::refine_extrinsics, "Whether to refine the extrinsic parameter group.")
+        .def_readwrite("print_summary", &BundleAdjustmentOptions::print_summary, "Accepted, prints nothing.")
+        .def_readwrite("min_num_residuals_for_multi_threading", &BundleAdjustmentOptions::min_num_residuals_for_multi_threading, "Accepted, no effect.")
+        .def_readwrite("solver_options", &BundleAdjustmentOptions::solver_options, "Ceres-Solver options.");
+    MakeDataclass(PyBaOpts, {"loss_function_type", "loss_function_scale", "refine_focal_length", "refine_principal_point",
+                             "refine_extra_params", "refine_extrinsics", "print_summary",
+                             "min_num_residuals_for_multi_threading", "solver_options"});
+    // the flat problem bundle_adjustment hands to amc_bundle_adjust, after the controller's filter (a test hook: the GPU
+    // tests run Context.bundle_adjust on it)
+    auto flat_problem = [checked_model](const PyReconstruction& r, const BundleAdjustmentOptions& o) {
+        SparseModel model = checked_model(r);
+        FilterObservationsWithNegativeDepth(&model);
+        size_t skipped = 0;
+        const BaRefineFlags flags{o.refine_focal_length, o.refine_principal_point, o.refine_extra_params, o.refine_extrinsics};
+        const FlatBa f = FlattenForBundleAdjustment(model, flags, &skipped);
+        auto arr = [](const auto& v, py::ssize_t cols) {
+            using T = typename std::decay<decltype(v)>::type::value_type;
+            py::array_t<T> a({static_cast<py::ssize_t>(v.size()) / cols, cols});
+            std::copy(v.begin(), v.end(), a.mutable_data());
+            return a;
+        };
+        py::dict d;
+        d["camera_models"] = arr(f.camera_models, 1);
+        d["camera_params"] = arr(f.camera_params, 12);
+        d["camera_const"] = arr(f.camera_const, 12);
+        d["image_cameras"] = arr(f.image_cameras, 1);
+        d["qvec"] = arr(f.qvec, 4);
+        d["tvec"] = arr(f.tvec, 3);
+        d["pose_const"] = arr(f.pose_const, 6);
+        d["xyz"] = arr(f.xyz, 3);
+        d["obs_image"] = arr(f.obs_image, 1);
+        d["obs_point"] = arr(f.obs_point, 1);
+        d["obs_xy"] = arr(f.obs_xy, 2);
+        return d;
+    };
+    m.def("_bundle_adjustment_problem", flat_problem, "reconstruction"_a, "options"_a = BundleAdjustmentOptions(),
+          "The flat problem bundle_adjustment solves (test hook).");
+    m.def(
+        "bundle_adjustment",
+        [checked_model, update_from_model](PyReconstruction& r, const BundleAdjustmentOptions& o) {
+            const auto t0 = std::chrono::steady_clock::now();
+            if (r.images.size() < 2) {
+                const auto f = PythonCallFrame();
+                Logging::Write(Logging::ERROR, f.first, f.second, "Need at least two views.");
+                return;
+            }
+            SparseModel model = checked_model(r);
+            const size_t filtered = FilterObservationsWithNegativeDepth(&model);
+            size_t skipped = 0;
+            const BaRefineFlags flags{o.refine_focal_length, o.refine_principal_point, o.refine_extra_params, o.refine_extrinsics};
+            FlatBa flat = FlattenForBundleAdjustment(model, flags, &skipped);
+            amc_ba_opts opts;
+            amc_ba_opts_default(&opts);
+            opts.loss_function_type = static_cast<int32_t>(o.loss_function_type);
+            opts.loss_function_scale = o.loss_function_scale;
+            opts.max_num_iterations = o.solver_options.max_num_iterations;
+            opts.max_linear_solver_iterations = o.solver_options.max_linear_solver_iterations;
+            opts.max_num_consecutive_invalid_steps = o.solver_options.max_num_consecutive_invalid_steps;
+            opts.function_tolerance = o.solver_options.function_tolerance;
+            opts.gradient_tolerance = o.solver_options.gradient_tolerance;
+            opts.parameter_tolerance = o.solver_options.parameter_tolerance;
+            amc_ba_problem pb = flat.Problem();
+            amc_ba_result res{};
+            {
+                py::gil_scoped_release release;
+                EstimatorCtx& E = TheEstimatorCtx();
+                std::lock_guard<std::mutex> lock(E.mu);
+                EstCheck(amc_bundle_adjust(E.Get(), &pb, &opts, &res), "amc_bundle_adjust");
+            }
+            WriteBackBundleAdjustment(flat, &model);
+            update_from_model(r, model);
+            static const char* const kTermination[] = {"FUNCTION_TOLERANCE", "PARAMETER_TOLERANCE", "GRADIENT_TOLERANCE", "MAX_ITERATIONS",
+                                                       "MIN_RADIUS", "INVALID_STEPS", "NOTHING_TO_REFINE"};
+            py::dict st;
+            st["call"] = "bundle_adjustment";
+            st["num_images"] = res.num_images;
+            st["num_points"] = res.num_points;
+            st["num_observations"] = res.num_observations;
+            st["num_variable_parameters"] = res.num_variable_parameters;
+            st["num_filtered_observations"] = filtered;
+            st["num_skipped_points"] = skipped;
+            st["initial_cost"] = res.initial_cost;
+            st["final_cost"] = res.final_cost;
+            st["num_successful_steps"] = res.num_successful_steps;
+            st["num_unsuccessful_steps"] = res.num_unsuccessful_steps;
+            st["num_pcg_iterations"] = res.num_pcg_iterations;
+            st["termination"] = kTermination[res.termination >= 0 && res.termination < 7 ? res.termination : 5];
+            st["device_ms"] = res.device_ms;
+            st["kernel_ms"] = res.kernel_ms;
+            st["host_ms"] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - res.device_ms;
+            py::module_::import("pycolmap_amd._pycolmap").attr("_last_stats") = st;
+        },
+        "reconstruction"_a, "options"_a = BundleAdjustmentOptions(),
+        "Jointly refine every pose, point and camera of the reconstruction on the GPU, in place (DESIGN.md section 15).");
 
     // ---- estimate_triangulation (/root/reference/pycolmap/estimators/triangulation.h; tri_host.h) ----------------------
     py::class_<TriPointData>(m, "PointData")

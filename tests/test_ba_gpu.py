@@ -1,0 +1,199 @@
+"""Bundle adjustment on the GPU: Context.bundle_adjust equals the CPU reference (tests/ba_ref) and
+its frozen fixture bit for bit on tests/ba_cases.py's cases: poses, points, camera parameters, costs and iteration
+counts; the error paths return AMC_E_INVALID and leave the context usable; bundle_adjustment on a model read from disk
+equals Context.bundle_adjust on the flattened problem, in place."""
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import ba_cases
+import ba_ref_lib as ref
+from pycolmap_amd import _capi
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = Path(__file__).resolve().parent / "golden" / "ba_ref_v1.npz"
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    with _capi.Context(0) as c:
+        yield c
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return np.load(GOLDEN)
+
+
+@pytest.mark.parametrize("name", sorted(ba_cases.CASES))
+def test_bundle_adjust_equals_reference_and_fixture(name, ctx, golden):
+    args, options = ba_cases.case_problem(name)
+    want = ref.bundle_adjust(*args, options=options)
+    got = ctx.bundle_adjust(*args, options=options)
+    for k in ba_cases.RESULT_STATS:
+        assert got[k] == want[k], (k, got[k], want[k])
+    for k in ba_cases.RESULT_ARRAYS:
+        assert np.array_equal(got[k].view(np.uint64), want[k].view(np.uint64)), k
+    assert ba_cases.digest(got) == str(golden[f"{name}/digest"])
+    assert (got["num_images"], got["num_points"], got["num_observations"]) == \
+        (len(args[3]), len(args[7]), len(args[8]))
+    assert got["kernel_ms"] > 0 and got["device_ms"] >= got["kernel_ms"] and got["host_ms"] >= 0
+
+
+def test_inputs_are_not_modified_and_calls_repeat(ctx):
+    args, options = ba_cases.case_problem("wave65")
+    before = [np.array(a, copy=True) for a in (args[4], args[5], args[7])]
+    a = ctx.bundle_adjust(*args, options=options)
+    b = ctx.bundle_adjust(*args, options=options)
+    assert ba_cases.digest(a) == ba_cases.digest(b)
+    for x, y in zip(before, (args[4], args[5], args[7])):
+        assert np.array_equal(x, y)
+
+
+def test_zero_iterations_returns_the_start(ctx):
+    args, _ = ba_cases.case_problem("min2")
+    r = ctx.bundle_adjust(*args, options=dict(max_num_iterations=0))
+    start = _capi.ba_inputs(*args)
+    assert r["termination"] == "MAX_ITERATIONS" and r["initial_cost"] == r["final_cost"] > 0
+    for k, i in (("camera_params", 1), ("qvec", 4), ("tvec", 5), ("xyz", 7)):
+        assert np.array_equal(r[k], start[i])
+
+
+def _bad_problems():
+    args, _ = ba_cases.case_problem("min2")
+
+    def swap(i, v):
+        a = list(args)
+        a[i] = v
+        return a
+    nan_xyz = np.array(args[7], copy=True)
+    nan_xyz[3, 1] = np.nan
+    inf_xy = np.array(args[10], copy=True)
+    inf_xy[0, 0] = np.inf
+    big_point = np.array(args[9], copy=True)
+    big_point[2] = 8
+    big_image = np.array(args[8], copy=True)
+    big_image[1] = 2
+    once = np.array(args[9], copy=True)
+    once[np.flatnonzero(once == 5)[0]] = 4  # point 5 is left with one observation
+    return {"unknown model": swap(0, [11]), "camera index": swap(3, [0, 1]), "nan point": swap(7, nan_xyz),
+            "inf pixel": swap(10, inf_xy), "point index": swap(9, big_point), "image index": swap(8, big_image),
+            "point seen once": swap(9, once)}
+
+
+@pytest.mark.parametrize("what", sorted(_bad_problems()))
+def test_invalid_input_is_refused_and_the_context_stays_usable(what, ctx):
+    with pytest.raises(_capi.AmcError) as e:
+        ctx.bundle_adjust(*_bad_problems()[what])
+    assert e.value.code == _capi.AMC_E_INVALID
+    args, options = ba_cases.case_problem("min2")
+    assert ctx.bundle_adjust(*args, options=options)["num_successful_steps"] >= 1
+
+
+@pytest.mark.parametrize("options", [dict(loss_function_scale=0.0), dict(max_linear_solver_iterations=0),
+                                     dict(function_tolerance=-1.0), dict(loss_function_type=3)])
+def test_invalid_options_are_refused(options, ctx):
+    args, _ = ba_cases.case_problem("min2")
+    with pytest.raises(_capi.AmcError) as e:
+        ctx.bundle_adjust(*args, options=options)
+    assert e.value.code == _capi.AMC_E_INVALID
+
+
+def test_no_observations_is_nothing_to_refine(ctx):
+    args, _ = ba_cases.case_problem("min2")
+    r = ctx.bundle_adjust(*args[:7], np.zeros((0, 3)), [], [], np.zeros((0, 2)))
+    assert r["termination"] == "NOTHING_TO_REFINE" and r["num_observations"] == 0
+
+
+# ---- bundle_adjustment end to end ---------------------------------------------------------------------
+E2E_SCENE = dict(seed=90, nimg=4, npts=30, model=2, cameras="mixed", tracks="mixed", noise=0.3)
+FLAT_ORDER = ("camera_models", "camera_params", "camera_const", "image_cameras", "qvec", "tvec", "pose_const", "xyz",
+              "obs_image", "obs_point", "obs_xy")
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def test_bundle_adjustment_on_a_model_from_disk(tmp_path, ctx):
+    import pycolmap
+    import pycolmap_amd as pc
+    src = tmp_path / "model"
+    src.mkdir()
+    ba_cases.reconstruction(ba_cases.scene(**E2E_SCENE)).write(str(src))
+    rec = pycolmap.Reconstruction(str(src))
+    options = pycolmap.BundleAdjustmentOptions(solver_options=dict(max_num_iterations=4), loss_function_type="CAUCHY",
+                                               loss_function_scale=2.0)
+    flat = pc._pycolmap._bundle_adjustment_problem(rec, options)
+    want = ctx.bundle_adjust(*[flat[k] for k in FLAT_ORDER],
+                             options=dict(max_num_iterations=4, loss_function_type="CAUCHY", loss_function_scale=2.0))
+    assert want["num_successful_steps"] >= 1
+    cams, imgs, pts = dict(rec.cameras), dict(rec.images), dict(rec.points3D)
+    assert pycolmap.bundle_adjustment(rec, options) is None
+    # in place: the same objects, new values, equal to the library call on the flattened problem bit for bit
+    assert all(rec.cameras[k] is v for k, v in cams.items()) and all(rec.images[k] is v for k, v in imgs.items())
+    assert all(rec.points3D[k] is v for k, v in pts.items())
+    for c, cam in enumerate(rec.cameras.values()):
+        assert np.array_equal(_bits(cam.params), _bits(want["camera_params"][c][:len(cam.params)]))
+    for i, im in enumerate(rec.images.values()):
+        assert np.array_equal(_bits(im.cam_from_world.rotation.quat), _bits(want["qvec"][i]))
+        assert np.array_equal(_bits(im.cam_from_world.translation), _bits(want["tvec"][i]))
+    for j, p in enumerate(rec.points3D.values()):
+        assert np.array_equal(_bits(p.xyz), _bits(want["xyz"][j]))
+    assert not np.array_equal(flat["xyz"], want["xyz"]) and not np.array_equal(flat["camera_params"], want["camera_params"])
+    assert np.array_equal(flat["qvec"][0], want["qvec"][0]) and flat["tvec"][1][0] == want["tvec"][1][0]  # the gauge
+    st = pycolmap.last_run_stats()
+    for k in ("num_images", "num_points", "num_observations", "num_variable_parameters", "initial_cost", "final_cost",
+              "num_successful_steps", "num_unsuccessful_steps", "num_pcg_iterations", "termination"):
+        assert st[k] == want[k], k
+    assert st["call"] == "bundle_adjustment" and st["final_cost"] < st["initial_cost"]
+    assert st["kernel_ms"] > 0 and st["device_ms"] >= st["kernel_ms"] and st["host_ms"] >= 0
+    # write / read keeps every bit
+    out = tmp_path / "refined"
+    out.mkdir()
+    rec.write(str(out))
+    back = pycolmap.Reconstruction(str(out))
+    for k, im in rec.images.items():
+        assert np.array_equal(_bits(back.images[k].cam_from_world.rotation.quat), _bits(im.cam_from_world.rotation.quat))
+        assert np.array_equal(_bits(back.images[k].cam_from_world.translation), _bits(im.cam_from_world.translation))
+    for k, p in rec.points3D.items():
+        assert np.array_equal(_bits(back.points3D[k].xyz), _bits(p.xyz))
+    for k, c in rec.cameras.items():
+        assert np.array_equal(_bits(back.cameras[k].params), _bits(c.params))
+
+
+def test_bundle_adjustment_filters_before_it_solves(ctx):
+    """an image turned away loses its observations, length-2 tracks seen by it go whole; the rest is refined"""
+    import pycolmap_amd as pc
+    rec = ba_cases.reconstruction(ba_cases.scene(**E2E_SCENE))
+    n_points, n_obs = rec.num_points3D(), rec.compute_num_observations()
+    rec.images[4].cam_from_world.translation = [0.0, 0.0, -50.0]
+    seen_by_4 = rec.images[4].num_points3D()
+    pc.bundle_adjustment(rec, pc.BundleAdjustmentOptions(solver_options=dict(max_num_iterations=2)))
+    st = pc.last_run_stats()
+    assert st["num_filtered_observations"] == seen_by_4 > 0 and rec.images[4].num_points3D() == 0
+    assert rec.num_points3D() < n_points and st["num_points"] == rec.num_points3D()
+    assert st["num_observations"] == rec.compute_num_observations() < n_obs - seen_by_4
+
+
+def test_bundle_adjustment_error_paths_raise_value_error(ctx):
+    import pycolmap_amd as pc
+    rec = ba_cases.reconstruction(ba_cases.scene(**E2E_SCENE))
+    with pytest.raises(ValueError):
+        pc.bundle_adjustment(rec, pc.BundleAdjustmentOptions(loss_function_scale=0.0))
+    with pytest.raises(ValueError):
+        pc.bundle_adjustment(rec, pc.BundleAdjustmentOptions(solver_options=dict(max_linear_solver_iterations=0)))
+    first = next(iter(rec.points3D.values()))
+    keep = list(first.xyz)
+    first.xyz = [np.nan, 0.0, 1.0]
+    with pytest.raises(ValueError):
+        pc.bundle_adjustment(rec)
+    first.xyz = keep
+    rec.images[2].points2D = rec.images[2].points2D[:1]  # tracks now name points2D that are gone
+    with pytest.raises(ValueError):
+        pc.bundle_adjustment(rec)
+    good = ba_cases.reconstruction(ba_cases.scene(**E2E_SCENE))
+    pc.bundle_adjustment(good, pc.BundleAdjustmentOptions(solver_options=dict(max_num_iterations=2)))
+    assert pc.last_run_stats()["num_successful_steps"] >= 1

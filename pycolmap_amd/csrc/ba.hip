@@ -635,6 +635,9 @@ int run(amc_ctx* ctx, amc_ba_problem* pb, const amc_ba_opts* opts, amc_ba_result
     HIPCHK(up(P[0].X, pb->xyz, npts * 24));
     HIPCHK(up(d.sc_c, ones.data(), (size_t)nred * 8));
     HIPCHK(up(d.sc_p, ones.data(), npts * 24));
+    // with every camera constant no kernel forms the cameras' preconditioner blocks, and precondition() still multiplies
+    // them with the residual's exact zeros: they must be finite for the products to be zero
+    if (!camvar && ncam) HIPCHK(hipMemsetAsync(d.Minv_c, 0, (size_t)kKC * kKC * ncam * 8, st));
 
     int cur = 0;
     Scalars hs{};

@@ -1,7 +1,9 @@
 // ba_plan_fuzz.cc — a stand-alone program for tests/test_ba_cpu.py (built with -fsanitize=address,undefined and run): the
 // host half of bundle adjustment (csrc/ba_plan.h) on a valid problem, on every kind of invalid one (indices out of range
 // in each array, a point seen once, values that are not finite, NULL arrays, an unknown model) and on seeded random
-// problems, valid and corrupted.  The arrays are heap blocks of exactly the stated sizes, so a read past an array's end
+// problems, valid and corrupted; every third of them has an image without observations, every third a camera that no
+// image uses (the empty segments of 15.2's orders), and the cameras' models are drawn one by one, so their parameter counts
+// differ within a problem.  The arrays are heap blocks of exactly the stated sizes, so a read past an array's end
 // or through an unchecked index is an ASan report.  A valid plan is checked: the three CSR orders are permutations with
 // the orders DESIGN.md 15.2 states.  Prints "ok <problems>" and returns 0.
 #include <cstdio>
@@ -39,7 +41,10 @@ struct Owned {
     }
 };
 
-Owned random_problem(std::mt19937& rng, size_t ncam, size_t nimg, size_t npts) {
+constexpr size_t kNone = ~(size_t)0;
+
+// `empty_image` gets no observation, `unused_camera` no image (kNone: whatever the draws give)
+Owned random_problem(std::mt19937& rng, size_t ncam, size_t nimg, size_t npts, size_t empty_image, size_t unused_camera) {
     Owned o;
     std::uniform_real_distribution<double> u(-1.0, 1.0);
     for (size_t c = 0; c < ncam; ++c) o.models.push_back((int32_t)(rng() % 11));
@@ -47,7 +52,11 @@ Owned random_problem(std::mt19937& rng, size_t ncam, size_t nimg, size_t npts) {
     o.cconst.resize(12 * ncam);
     for (double& v : o.cparams) v = u(rng);
     for (uint8_t& v : o.cconst) v = rng() % 2;
-    for (size_t i = 0; i < nimg; ++i) o.icam.push_back((uint32_t)(rng() % ncam));
+    for (size_t i = 0; i < nimg; ++i) {
+        uint32_t c = (uint32_t)(rng() % ncam);
+        if (c == unused_camera) c = (c + 1) % (uint32_t)ncam;
+        o.icam.push_back(c);
+    }
     o.q.resize(4 * nimg);
     o.t.resize(3 * nimg);
     o.pconst.resize(6 * nimg);
@@ -59,7 +68,9 @@ Owned random_problem(std::mt19937& rng, size_t ncam, size_t nimg, size_t npts) {
     for (size_t j = 0; j < npts; ++j) {
         const size_t n = 2 + rng() % 3;
         for (size_t k = 0; k < n; ++k) {
-            o.oi.push_back((uint32_t)(rng() % nimg));
+            uint32_t i = (uint32_t)(rng() % nimg);
+            if (i == empty_image) i = (i + 1) % (uint32_t)nimg;
+            o.oi.push_back(i);
             o.op.push_back((uint32_t)j);
         }
     }
@@ -115,6 +126,30 @@ void check_plan(Owned& o, const amc::ba::Plan& p) {
         }
     for (size_t k = 0; k < 6 * nimg; ++k) nvar += !o.pconst[k];
     REQUIRE(p.num_variable == nvar);
+    uint32_t kc = 0;
+    for (size_t c = 0; c < ncam; ++c) kc = std::max<uint32_t>(kc, (uint32_t)amc::cam::num_params(o.models[c]));
+    REQUIRE(p.kc == kc);
+    for (size_t c = 0; c < ncam; ++c)  // the slots past a narrower camera's parameters hold exact zeros
+        for (int k = amc::cam::num_params(o.models[c]); k < 12; ++k) REQUIRE(p.cparams[12 * c + k] == 0.0);
+}
+
+// what the generator is asked to produce, counted over the valid plans
+int g_empty_images = 0, g_unused_cameras = 0, g_mixed_counts = 0;
+
+void count_edges(const Owned& o, const amc::ba::Plan& p, size_t empty_image, size_t unused_camera) {
+    if (empty_image != kNone) {
+        REQUIRE(p.ioff[empty_image] == p.ioff[empty_image + 1]);
+        ++g_empty_images;
+    }
+    if (unused_camera != kNone) {
+        REQUIRE(p.coff[unused_camera] == p.coff[unused_camera + 1]);
+        ++g_unused_cameras;
+    }
+    for (size_t c = 1; c < o.models.size(); ++c)
+        if (amc::cam::num_params(o.models[c]) != amc::cam::num_params(o.models[0])) {
+            ++g_mixed_counts;
+            break;
+        }
 }
 
 }  // namespace
@@ -124,10 +159,14 @@ int main() {
     amc::ba::Plan plan;
     int problems = 0;
     for (int round = 0; round < 200; ++round) {
-        Owned o = random_problem(rng, 1 + rng() % 3, 2 + rng() % 5, 1 + rng() % 40);
+        const size_t ncam = (round % 3 == 1 ? 2 : 1) + rng() % 3, nimg = 2 + rng() % 5;
+        const size_t empty_image = round % 3 == 0 ? rng() % nimg : kNone;
+        const size_t unused_camera = round % 3 == 1 ? rng() % ncam : kNone;
+        Owned o = random_problem(rng, ncam, nimg, 1 + rng() % 40, empty_image, unused_camera);
         amc_ba_problem v = o.view();
         REQUIRE(amc::ba::make_plan(v, &plan).empty());
         check_plan(o, plan);
+        count_edges(o, plan, empty_image, unused_camera);
         ++problems;
         // one corruption per copy: each must be refused, none may be read through
         for (int kind = 0; kind < 9; ++kind) {
@@ -175,6 +214,8 @@ int main() {
     Owned empty;
     amc_ba_problem e = empty.view();
     REQUIRE(amc::ba::make_plan(e, &plan).empty() && plan.num_variable == 0);
-    std::printf("ok %d\n", problems);
+    REQUIRE(g_empty_images >= 60 && g_unused_cameras >= 60 && g_mixed_counts >= 60);
+    std::printf("ok %d (%d with an image without observations, %d with an unused camera, %d with mixed parameter counts)\n",
+                problems, g_empty_images, g_unused_cameras, g_mixed_counts);
     return 0;
 }

@@ -1,7 +1,8 @@
 """Bundle adjustment without a GPU: the C header and the ctypes view, the pycolmap surface
 (option classes, Reconstruction, the controller's flat problem), the host code under sanitizers, and the CPU reference
 (tests/ba_ref) against central differences of its own residual, a numpy restatement of its summation order, its frozen
-fixture, and scipy's least_squares on the same parametrisation."""
+fixtures (the cases and the edge cases of tests/ba_cases.py, with a check that the edge cases are of the kinds their names
+say), and scipy's least_squares on the same parametrisation."""
 import json
 from pathlib import Path
 
@@ -14,6 +15,7 @@ from pycolmap_amd import _capi
 
 ROOT = Path(__file__).resolve().parent.parent
 GOLDEN = ROOT / "tests" / "golden" / "ba_ref_v1.npz"
+GOLDEN_EDGES = ROOT / "tests" / "golden" / "ba_ref_edges_v1.npz"
 BUDGET = ROOT / "tests" / "ref2" / "ba_deviation_budget.json"
 
 
@@ -465,6 +467,125 @@ def test_observation_order_changes_nothing_but_the_sums_order():
     a = ref.bundle_adjust(*args, options=options)
     b = ref.bundle_adjust(*args[:8], args[8][order], args[9][order], args[10][order], options=options)
     assert ba_cases.digest(a) == ba_cases.digest(b)
+
+
+# ---- the edge cases: shapes and exits that CASES leaves out (15.10) -----------------------------------------------------
+@pytest.fixture(scope="module")
+def golden_edges():
+    return np.load(GOLDEN_EDGES)
+
+
+@pytest.fixture(scope="module")
+def solved_edges():
+    """the reference on every edge case, once"""
+    return {name: ref.bundle_adjust(*ba_cases.edge_problem(name)[0], options=ba_cases.edge_problem(name)[1])
+            for name in ba_cases.EDGE_CASES}
+
+
+def test_edge_fixture_lists_the_edge_cases(golden_edges):
+    assert sorted(golden_edges["names"]) == sorted(ba_cases.EDGE_CASES)
+    assert GOLDEN_EDGES.stat().st_size < 20_000
+
+
+@pytest.mark.parametrize("name", sorted(ba_cases.EDGE_CASES))
+def test_reference_equals_its_edge_fixture_bit_for_bit(name, golden_edges, solved_edges):
+    r = solved_edges[name]
+    stats = np.array([ref.TERMINATIONS.index(r[k]) if k == "termination" else r[k] for k in ba_cases.RESULT_STATS],
+                     np.float64)
+    assert np.array_equal(stats.view(np.uint64), golden_edges[f"{name}/stats"].view(np.uint64))
+    assert ba_cases.digest(r) == str(golden_edges[f"{name}/digest"])
+
+
+def test_edge_cases_cover_the_exits_and_the_paths(solved_edges):
+    """by the reference's own result and the problems' own shapes, so that the list cannot decay"""
+    r = solved_edges
+    steps = lambda n: r[n]["num_successful_steps"] + r[n]["num_unsuccessful_steps"]  # noqa: E731
+    assert r["stop_function_tolerance"]["termination"] == "FUNCTION_TOLERANCE" and steps("stop_function_tolerance") >= 1
+    assert r["stop_parameter_tolerance"]["termination"] == "PARAMETER_TOLERANCE"
+    assert r["stop_parameter_tolerance"]["num_successful_steps"] >= 1
+    assert r["stop_gradient_tolerance"]["termination"] == "GRADIENT_TOLERANCE" and steps("stop_gradient_tolerance") >= 1
+    assert r["stop_gradient_at_start"]["termination"] == "GRADIENT_TOLERANCE" and steps("stop_gradient_at_start") == 0
+    assert r["stop_gradient_at_start"]["final_cost"] == r["stop_gradient_at_start"]["initial_cost"]
+    assert r["stop_gradient_at_start"]["num_pcg_iterations"] == 0
+    inf = r["infinite_start"]
+    assert inf["termination"] == "INVALID_STEPS" and steps("infinite_start") == 0
+    assert inf["initial_cost"] == np.inf and inf["final_cost"] == np.inf  # +inf, not NaN: it compares by value as well
+    start = _capi.ba_inputs(*ba_cases.edge_problem("infinite_start")[0])
+    for k, i in (("camera_params", 1), ("qvec", 4), ("tvec", 5), ("xyz", 7)):
+        assert np.array_equal(inf[k], start[i]), k
+    assert r["long_run"]["num_successful_steps"] >= 10 and r["long_run"]["num_unsuccessful_steps"] >= 5
+    assert ba_cases.EDGE_CASES["long_run"][1] == dict(max_num_iterations=40)
+    # every solve of pcg_breakdown is one iteration; one that ends by neither the residual rule nor the cap is a breakdown
+    b = r["pcg_breakdown"]
+    assert b["num_pcg_iterations"] == steps("pcg_breakdown") == 80
+    assert b["num_pcg_stops_residual"] + b["num_pcg_stops_cap"] < steps("pcg_breakdown")
+    v = r["invalid_step_in_loop"]
+    assert v["termination"] == "INVALID_STEPS" and v["num_successful_steps"] >= 1 and np.isfinite(v["final_cost"])
+    assert steps("invalid_step_in_loop") < ba_cases.EDGE_CASES["invalid_step_in_loop"][1]["max_num_iterations"]
+    shape = {n: ba_cases.edge_problem(n)[0] for n in ba_cases.EDGE_CASES}
+    nimg, ncam, npts = (lambda n: len(shape[n][3])), (lambda n: len(shape[n][0])), (lambda n: len(shape[n][7]))  # noqa: E731
+    assert nimg("many65_per_image") > 64 and ncam("many65_per_image") > 64
+    assert nimg("many70_shared") > 64 and ncam("many70_shared") == 1
+    for n in ("many260_per_image", "many260_cameras_const"):
+        assert nimg(n) > 256 and ncam(n) > 256 and npts(n) < 256
+    assert np.asarray(shape["many260_cameras_const"][2]).all() and not np.asarray(shape["many260_per_image"][2]).all()
+    # both orders of a narrow and the widest camera, and 3-, 4-, 5- and 12-parameter cameras side by side
+    counts = lambda n: [len(p) for p in shape[n][1]]  # noqa: E731
+    small, big = counts("mixed_models_small_first"), counts("mixed_models_big_first")
+    assert small[0] == 3 and max(small) == 12 and {3, 4, 5, 12} <= set(small) and small.index(12) > 0
+    assert big[0] == 12 and min(big) == 3
+    assert np.bincount(shape["mixed_models_small_first"][3]).tolist() == [2, 1, 1, 1, 1, 1]
+    for n, i in (("empty_image_middle", 3), ("empty_image_last", 4)):
+        assert nimg(n) == 5 and i not in set(np.asarray(shape[n][8]).tolist()) and not np.asarray(shape[n][6])[i].any()
+    used = set(np.asarray(shape["camera_without_images"][3]).tolist())
+    assert used == {0, 2} and ncam("camera_without_images") == 3 and len(set(shape["camera_without_images"][0])) >= 2
+    pairs = list(zip(np.asarray(shape["duplicate_observations"][8]).tolist(), np.asarray(shape["duplicate_observations"][9]).tolist()))
+    assert len(pairs) - len(set(pairs)) == 5
+    assert np.asarray(shape["pose_const_pattern"][6]).tolist() == [[1] * 6, [0, 0, 0, 1, 0, 0], [1, 0, 0, 0, 1, 0], [1, 1, 1, 0, 0, 0]]
+
+
+def test_edge_cases_coarse_properties(solved_edges):
+    for name, r in solved_edges.items():
+        if name not in ("infinite_start", "stop_gradient_at_start"):
+            assert r["final_cost"] < r["initial_cost"], name
+    for name, i in (("empty_image_middle", 3), ("empty_image_last", 4)):
+        start = _capi.ba_inputs(*ba_cases.edge_problem(name)[0])
+        r = solved_edges[name]
+        assert np.array_equal(r["qvec"][i].view(np.uint64), start[4][i].view(np.uint64)), name
+        assert np.array_equal(r["tvec"][i].view(np.uint64), start[5][i].view(np.uint64)), name
+        assert not np.array_equal(r["tvec"][2], start[5][2])  # an observed image did move
+    start = _capi.ba_inputs(*ba_cases.edge_problem("camera_without_images")[0])
+    r = solved_edges["camera_without_images"]
+    assert np.array_equal(r["camera_params"][1].view(np.uint64), start[1][1].view(np.uint64))
+    assert not np.array_equal(r["camera_params"][0], start[1][0]) and not np.array_equal(r["camera_params"][2], start[1][2])
+    # pose_const_pattern: constant translation columns are equal and a rotation with all three columns constant is
+    # bit-equal.  A single constant rotation column is a zero entry of each step's tangent d in q_new = Plus(q, d), not
+    # of the composition of several steps (two rotations about y and z compose to one with an x part), so it is read
+    # off one step: Plus is the product (sin|d|/|d| d, cos|d|) * q, hence the vector part of q_new * q^-1 is parallel
+    # to d.  Bound: two quaternion products of entries below 1 in magnitude, four terms each, and one division:
+    # 16 units of double precision.
+    args, _ = ba_cases.edge_problem("pose_const_pattern")
+    start = _capi.ba_inputs(*args)
+    pc = np.asarray(args[6])
+    for r in (solved_edges["pose_const_pattern"], ref.bundle_adjust(*args, options=dict(max_num_iterations=1))):
+        for i in range(pc.shape[0]):
+            assert np.array_equal(r["tvec"][i][pc[i, 3:] != 0], start[5][i][pc[i, 3:] != 0]), i
+            assert not np.array_equal(r["tvec"][i][pc[i, 3:] == 0], start[5][i][pc[i, 3:] == 0]) or pc[i, 3:].all(), i
+            if pc[i, :3].all():
+                assert np.array_equal(r["qvec"][i].view(np.uint64), start[4][i].view(np.uint64)), i
+    assert r["num_successful_steps"] == 1
+
+    def step_tangent(q0, q1):
+        """the vector part of q1 * q0^-1, (x, y, z, w) quaternions"""
+        inv = np.array([-q0[0], -q0[1], -q0[2], q0[3]]) / (q0 @ q0)
+        return np.array([q1[3] * inv[0] + q1[0] * inv[3] + q1[1] * inv[2] - q1[2] * inv[1],
+                         q1[3] * inv[1] - q1[0] * inv[2] + q1[1] * inv[3] + q1[2] * inv[0],
+                         q1[3] * inv[2] + q1[0] * inv[1] - q1[1] * inv[0] + q1[2] * inv[3]])
+
+    d = step_tangent(start[4][2], r["qvec"][2])  # image 2: rotation column 0 constant, 1 and 2 variable
+    assert min(abs(d[1]), abs(d[2])) > 1e-6 and abs(d[0]) <= 16 * np.finfo(np.float64).eps, d
+    d = step_tangent(start[4][1], r["qvec"][1])  # image 1, for contrast: all three rotation columns variable
+    assert np.abs(d).min() > 1e-6, d
 
 
 # ---- accuracy against an independent solver ----------------------------------------------------------------------------

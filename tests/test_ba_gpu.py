@@ -1,6 +1,6 @@
 """Bundle adjustment on the GPU: Context.bundle_adjust equals the CPU reference (tests/ba_ref) and
-its frozen fixture bit for bit on tests/ba_cases.py's cases: poses, points, camera parameters, costs and iteration
-counts; the error paths return AMC_E_INVALID and leave the context usable; bundle_adjustment on a model read from disk
+its frozen fixtures bit for bit on tests/ba_cases.py's cases and edge cases: poses, points, camera parameters, costs and
+iteration counts; the error paths return AMC_E_INVALID and leave the context usable; bundle_adjustment on a model read from disk
 equals Context.bundle_adjust on the flattened problem, in place."""
 from pathlib import Path
 
@@ -14,6 +14,7 @@ from pycolmap_amd import _capi
 pytestmark = pytest.mark.gpu
 
 GOLDEN = Path(__file__).resolve().parent / "golden" / "ba_ref_v1.npz"
+GOLDEN_EDGES = Path(__file__).resolve().parent / "golden" / "ba_ref_edges_v1.npz"
 
 
 @pytest.fixture(scope="module")
@@ -40,6 +41,35 @@ def test_bundle_adjust_equals_reference_and_fixture(name, ctx, golden):
     assert (got["num_images"], got["num_points"], got["num_observations"]) == \
         (len(args[3]), len(args[7]), len(args[8]))
     assert got["kernel_ms"] > 0 and got["device_ms"] >= got["kernel_ms"] and got["host_ms"] >= 0
+
+
+@pytest.fixture(scope="module")
+def golden_edges():
+    return np.load(GOLDEN_EDGES)
+
+
+@pytest.mark.parametrize("name", sorted(ba_cases.EDGE_CASES))
+def test_bundle_adjust_equals_reference_and_fixture_on_edge_cases(name, ctx, golden_edges):
+    """the shapes and exits of ba_cases.EDGE_CASES; the costs by bit pattern, so that a cost that is not finite compares"""
+    args, options = ba_cases.edge_problem(name)
+    want = ref.bundle_adjust(*args, options=options)
+    got = ctx.bundle_adjust(*args, options=options)
+    for k in ba_cases.RESULT_STATS:
+        if k in ("initial_cost", "final_cost"):
+            assert np.float64(got[k]).view(np.uint64) == np.float64(want[k]).view(np.uint64), (k, got[k], want[k])
+        else:
+            assert got[k] == want[k], (k, got[k], want[k])
+    for k in ba_cases.RESULT_ARRAYS:
+        assert np.array_equal(got[k].view(np.uint64), want[k].view(np.uint64)), k
+    assert ba_cases.digest(got) == str(golden_edges[f"{name}/digest"])
+    assert (got["num_images"], got["num_points"], got["num_observations"]) == \
+        (len(args[3]), len(args[7]), len(args[8]))
+
+
+def test_calls_repeat_at_a_multi_block_size(ctx):
+    args, options = ba_cases.edge_problem("many260_per_image")
+    assert ba_cases.digest(ctx.bundle_adjust(*args, options=options)) == \
+        ba_cases.digest(ctx.bundle_adjust(*args, options=options))
 
 
 def test_inputs_are_not_modified_and_calls_repeat(ctx):
@@ -162,6 +192,40 @@ def test_bundle_adjustment_on_a_model_from_disk(tmp_path, ctx):
         assert np.array_equal(_bits(back.points3D[k].xyz), _bits(p.xyz))
     for k, c in rec.cameras.items():
         assert np.array_equal(_bits(back.cameras[k].params), _bits(c.params))
+
+
+def test_bundle_adjustment_with_two_camera_models_and_an_image_without_observations(ctx):
+    """a SIMPLE_RADIAL and an OPENCV camera in one Reconstruction; image 5 has no point2D with a point.  The host layer
+    (csrc/host/ba_host.h) passes every image of the model, observed or not: the unobserved image is in the flat problem
+    with a variable pose and no observation, and comes back where it started, as it does from the flat call."""
+    import pycolmap
+    import pycolmap_amd as pc
+    rec = ba_cases.reconstruction(ba_cases.scene(**ba_cases.E2E_MIXED_SCENE))
+    assert [c.model.name for c in rec.cameras.values()] == ["SIMPLE_RADIAL", "OPENCV"]
+    assert rec.images[5].num_points3D() == 0
+    options = pycolmap.BundleAdjustmentOptions(solver_options=dict(max_num_iterations=4))
+    flat = pc._pycolmap._bundle_adjustment_problem(rec, options)
+    assert flat["camera_models"].ravel().tolist() == [2, 4]
+    assert len(flat["image_cameras"].ravel()) == rec.num_images() == 5 and 4 not in flat["obs_image"].ravel().tolist()
+    assert flat["pose_const"].tolist()[4] == [0] * 6
+    want = ctx.bundle_adjust(*[flat[k] for k in FLAT_ORDER], options=dict(max_num_iterations=4))
+    assert want["num_successful_steps"] >= 1 and want["num_images"] == 5
+    assert pycolmap.bundle_adjustment(rec, options) is None
+    for c, cam in enumerate(rec.cameras.values()):
+        assert np.array_equal(_bits(cam.params), _bits(want["camera_params"][c][:len(cam.params)]))
+        assert not np.array_equal(_bits(cam.params), _bits(flat["camera_params"][c][:len(cam.params)]))
+    for i, im in enumerate(rec.images.values()):
+        assert np.array_equal(_bits(im.cam_from_world.rotation.quat), _bits(want["qvec"][i]))
+        assert np.array_equal(_bits(im.cam_from_world.translation), _bits(want["tvec"][i]))
+    for j, p in enumerate(rec.points3D.values()):
+        assert np.array_equal(_bits(p.xyz), _bits(want["xyz"][j]))
+    assert np.array_equal(_bits(want["qvec"][4]), _bits(flat["qvec"][4]))
+    assert np.array_equal(_bits(want["tvec"][4]), _bits(flat["tvec"][4]))
+    st = pycolmap.last_run_stats()
+    for k in ("num_images", "num_points", "num_observations", "num_variable_parameters", "initial_cost", "final_cost",
+              "num_successful_steps", "num_unsuccessful_steps", "num_pcg_iterations", "termination"):
+        assert st[k] == want[k], k
+    assert st["num_filtered_observations"] == 0
 
 
 def test_bundle_adjustment_filters_before_it_solves(ctx):

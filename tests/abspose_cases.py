@@ -76,3 +76,187 @@ def cases():
     for m in range(11):
         c[f"model{m}"] = (scene(40 + m, 2, 250, outlier_frac=0.3, noise_px=0.5, model=m), {}, {}, m % 2 == 0)
     return c
+
+
+# ---- the edge cases: what cases() does not reach ------------------------------------------------------
+FAST = dict(min_num_trials=30, max_num_trials=2000)  # the trial limits lowered where the defaults are not under test
+FIELDS = ("success", "qvec", "tvec", "num_inliers", "num_trials", "focal_factor", "inlier_mask", "covariance")
+OVERRUN = dict(min_num_trials=20, max_num_trials=100000)  # a first sample stream of 3 * 2000 + 1024 words
+FIRST_STREAM_WORDS = 3 * 2000 + 1024
+FOCAL4 = dict(estimate_focal_length=1, num_focal_length_samples=4, min_num_trials=30, max_num_trials=500)
+TIGHT = dict(gradient_tolerance=0.0)
+
+
+def empty_query():
+    return dict(offsets=np.zeros(2, np.uint64), camera_models=np.zeros(1, np.int32),
+                camera_params=[np.array([1000.0, 500.0, 500.0])], points2D=np.zeros((0, 2)), points3D=np.zeros((0, 3)),
+                qvec=np.array([[0.0, 0.0, 0.0, 1.0]]), tvec=np.zeros((1, 3)), outlier=np.zeros(0, bool))
+
+
+def with_moved(sc, count, seed):
+    """The scene with its first `count` observations moved 200 to 400 pixels away in a seeded direction."""
+    rng = np.random.default_rng(seed)
+    ang, r = rng.uniform(0, 2 * np.pi, count), rng.uniform(200.0, 400.0, count)
+    p2 = sc["points2D"].copy()
+    p2[:count] += np.stack([r * np.cos(ang), r * np.sin(ang)], axis=1)
+    out = sc["outlier"].copy()
+    out[:count] = True
+    return dict(sc, points2D=p2, outlier=out)
+
+
+def collinear(seed, n):
+    """A query whose 3D points lie on one line (the observations stay those of the scene's own points)."""
+    sc = scene(seed, 1, n, outlier_frac=0.0, noise_px=0.0)
+    p3 = np.linspace(0, 1, n)[:, None] * np.array([1.0, 2.0, 3.0]) + sc["points3D"][0]
+    return dict(sc, points3D=p3)
+
+
+def start(sc, seed=0, rot=0.01, trans=0.05, mask=None, count=None):
+    """The scene as a refinement problem: the true poses perturbed as tests/test_abspose_gpu.py's test_refinement_alone
+    does (rot = trans = 0: the true poses), and the mask: given, or `count` seeded correspondences of a one-query
+    scene, or the scene's inliers."""
+    rng = np.random.default_rng(seed)
+    q = sc["qvec"] + rng.normal(scale=rot, size=sc["qvec"].shape) if rot else sc["qvec"].copy()
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    t = sc["tvec"] + rng.normal(scale=trans, size=sc["tvec"].shape) if trans else sc["tvec"].copy()
+    if count is not None:
+        mask = np.zeros(len(sc["outlier"]), bool)
+        mask[np.random.default_rng(seed + 1).permutation(len(mask))[:count]] = True
+    return dict(sc, start_q=q, start_t=t, mask=~sc["outlier"] if mask is None else np.asarray(mask, bool))
+
+
+def tiny_queries(seed, num_queries):
+    """num_queries noise-free three-point SIMPLE_PINHOLE queries, built without a Python loop (scene() has one)."""
+    rng = np.random.default_rng(seed)
+    Q = int(num_queries)
+    q = rng.normal(size=(Q, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    x, y, z, w = q.T
+    R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                  2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                  2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], axis=1).reshape(Q, 3, 3)
+    t = rng.uniform(-5.0, 5.0, size=(Q, 1, 3))
+    uv = rng.uniform(-0.5, 0.5, size=(Q, 3, 2))
+    d = rng.uniform(4.0, 12.0, size=(Q, 3, 1))
+    xc = np.concatenate([uv * d, d], axis=2)
+    p3 = np.einsum("qji,qkj->qki", R, xc - t)  # R^T (xc - t)
+    p2 = 1200.0 * uv + np.array([800.0, 600.0])
+    return dict(offsets=(3 * np.arange(Q + 1)).astype(np.uint64), camera_models=np.zeros(Q, np.int32),
+                camera_params=[np.array([1200.0, 800.0, 600.0])] * Q, points2D=p2.reshape(-1, 2),
+                points3D=p3.reshape(-1, 3), qvec=q, tvec=t.reshape(Q, 3), outlier=np.zeros(3 * Q, bool))
+
+
+def overrun_query():
+    """A query whose RANSAC, under OVERRUN, draws past the first sample stream (2705 trials in the reference)."""
+    return scene(800, 1, 120, outlier_frac=0.85, noise_px=0.3)
+
+
+MIXED_MODELS = (0, 5, 4, 7, 1, 10, 2, 8, 6, 9)
+MIXED_SIZES = (40, 130, 64, 65, 100, 63, 0, 2, 128, 90)
+
+
+def edge_cases():
+    """name -> (kind "estimate" | "refine", scene, estimation options, refinement options, return_covariance); a
+    refine scene also has start_q, start_t and mask.  Every shape is the smallest at which the code path exists: at
+    most 200 correspondences a query under estimation, 129 under refinement.  tests/test_abspose_cpu.py asserts by the
+    reference's own results and trace that each case is of the kind its name says."""
+    c = {}
+    # the lane edges of every sum over correspondences (for k = lane; k < n; k += 64), and of the sums over inliers
+    for n in (63, 64, 65, 127, 128, 129):
+        c[f"n{n}"] = ("estimate", scene(700 + n, 1, n, outlier_frac=0.3), FAST, {}, n % 2 == 1)
+    for k in (64, 65):
+        c[f"inliers{k}"] = ("estimate", with_moved(scene(830 + k, 1, 100, outlier_frac=0.0, noise_px=0.0), 100 - k, k),
+                            FAST, {}, k % 2 == 1)
+    # RANSAC control
+    c["trials_equal"] = ("estimate", scene(840, 1, 100, outlier_frac=0.3), dict(min_num_trials=50, max_num_trials=50),
+                         {}, False)
+    c["one_trial"] = ("estimate", scene(841, 1, 100, outlier_frac=0.0), dict(min_num_trials=0, max_num_trials=1), {},
+                      True)
+    c["ratio_clamp"] = ("estimate", scene(842, 1, 150, outlier_frac=0.6), dict(FAST, min_inlier_ratio=0.5), {}, False)
+    c["confidence0"] = ("estimate", scene(843, 1, 100, outlier_frac=0.3), dict(FAST, confidence=0.0), {}, False)
+    c["confidence1"] = ("estimate", scene(844, 1, 100, outlier_frac=0.3), dict(FAST, confidence=1.0), {}, True)
+    c["overrun_shared_launch"] = ("estimate", concat(scene(801, 1, 40, outlier_frac=0.1), overrun_query(),
+                                                     scene(802, 1, 200, outlier_frac=0.2)), OVERRUN, {}, True)
+    # focal-length estimation: the two-focal models and the models lifted on the host with scaled parameters
+    for m in (1, 4, 5, 7, 8, 10):
+        c[f"focal_model{m}"] = ("estimate", scene(810 + m, 1, 150, outlier_frac=0.2, model=m), FOCAL4, {}, True)
+    c["focal_tie"] = ("estimate", scene(900, 1, 80, outlier_frac=0.0, noise_px=0.0),
+                      dict(FAST, estimate_focal_length=1, num_focal_length_samples=6, min_focal_length_ratio=0.9,
+                           max_focal_length_ratio=1.1, max_error=200.0), {}, True)
+    c["focal_all_fail"] = ("estimate", concat(scene(901, 1, 2, outlier_frac=0.0, noise_px=0.0), collinear(902, 60)),
+                           FOCAL4, {}, True)
+    c["focal_mixed_batch"] = ("estimate",
+                              concat(*[scene(910 + i, 1, n, outlier_frac=0.2 if n > 2 else 0.0, model=m)
+                                       for i, (m, n) in enumerate(zip(MIXED_MODELS, MIXED_SIZES))]), FOCAL4, {}, True)
+    # refinement alone
+    for m in range(11):
+        c[f"refine_model{m}"] = ("refine", start(scene(920 + m, 1, 120, outlier_frac=0.2, noise_px=1.0, model=m), m),
+                                 None, {}, m % 2 == 0)
+    for k in (0, 1, 2, 3, 4, 64, 65):
+        sc = start(scene(940, 1, 100, outlier_frac=0.0, noise_px=1.0, model=4), 40, count=k)
+        c[f"refine_count{k}"] = ("refine", sc, None, {}, False)
+        c[f"refine_count{k}_cov"] = ("refine", sc, None, {}, True)
+    for n in (63, 64, 65, 129):
+        c[f"refine_n{n}"] = ("refine", start(scene(950 + n, 1, n, outlier_frac=0.0, noise_px=1.0), n), None, {},
+                             n % 2 == 1)
+    c["refine_empty_between"] = ("refine", start(concat(scene(960, 1, 50, outlier_frac=0.2), empty_query(),
+                                                        scene(961, 1, 70, outlier_frac=0.2)), 60), None, {}, True)
+    sc = start(scene(962, 2, 60, outlier_frac=0.2), 62)
+    q = sc["start_q"].copy()
+    q[0, 2] = np.nan
+    c["refine_nan_quat"] = ("refine", dict(sc, start_q=q), None, {}, True)
+    for where in ("in", "outside"):
+        k = int(np.flatnonzero(sc["mask"] if where == "in" else ~sc["mask"])[3])  # (in the first query)
+        p3 = sc["points3D"].copy()
+        p3[k, 1] = np.nan
+        c[f"refine_nan_point_{where}_mask"] = ("refine", dict(sc, points3D=p3), None, {}, True)
+    # the exits of the solver, each with the options that force it
+    near = start(scene(970, 1, 100, outlier_frac=0.2, noise_px=1.0, model=2), 70)
+    for it in (0, 1, 3):
+        c[f"refine_iterations{it}"] = ("refine", near, None, dict(TIGHT, max_num_iterations=it), True)
+    c["refine_far_start"] = ("refine", start(scene(971, 1, 100, outlier_frac=0.2, noise_px=1.0), 71, rot=0.5, trans=2.0),
+                             None, TIGHT, True)
+    c["refine_at_optimum"] = ("refine", start(scene(972, 1, 100, outlier_frac=0.0, noise_px=0.0), 72, rot=0, trans=0),
+                              None, {}, True)
+    c["refine_function_tolerance"] = ("refine", near, None, TIGHT, True)
+    c["refine_parameter_tolerance"] = ("refine", start(scene(973, 1, 100, outlier_frac=0.0, noise_px=0.0), 73), None,
+                                       TIGHT, True)
+    # a start this far off has steps that raise the cost (a start perturbed by 0.5 and 2 has none)
+    c["refine_rejected_then_accepted"] = ("refine", start(scene(974, 1, 100, outlier_frac=0.2, noise_px=1.0, model=4),
+                                                          74, rot=2.0, trans=10.0), None, TIGHT, False)
+    # a loss this narrow leaves a gradient of about 1e-197: it moves a translation of exactly zero, so the gradient
+    # test does not stop the run, and the model cost change of every step underflows to zero: five invalid steps
+    sc = start(scene(975, 1, 60, outlier_frac=0.0, noise_px=1.0), 75)
+    c["refine_invalid_steps"] = ("refine", dict(sc, start_t=np.zeros((1, 3))), None,
+                                 dict(TIGHT, loss_function_scale=1e-120), True)
+    # one observation 1e40 pixels away under a loss wide enough to stay quadratic there: no step lowers the cost, and
+    # the steps stay above the parameter tolerance until the 15th rejection takes the radius below 1e-32
+    sc = start(scene(981, 1, 60, outlier_frac=0.0, noise_px=1.0), 75)
+    p2 = sc["points2D"].copy()
+    p2[0] += 1e40
+    c["refine_min_radius"] = ("refine", dict(sc, points2D=p2), None, dict(TIGHT, loss_function_scale=1e60), True)
+    return c
+
+
+EDGE_CASES = edge_cases()
+
+
+def edge_run(name, estimate, refine):
+    """The case through `estimate` / `refine`: the reference's functions or a Context's methods."""
+    kind, sc, est, rf, cov = EDGE_CASES[name]
+    args = (sc["offsets"], sc["camera_models"], sc["camera_params"], sc["points2D"], sc["points3D"])
+    if kind == "estimate":
+        return estimate(*args, est, rf, cov)
+    return refine(*args, sc["start_q"], sc["start_t"], sc["mask"], rf, cov)
+
+
+def digest(result) -> str:
+    """sha256 over the result's FIELDS, each as name, dtype, shape and bytes."""
+    import hashlib
+    h = hashlib.sha256()
+    for k in FIELDS:
+        if k in result:
+            a = np.ascontiguousarray(result[k])
+            h.update(f"{k}:{a.dtype.str}:{a.shape}:".encode())
+            h.update(a.tobytes())
+    return h.hexdigest()

@@ -1103,19 +1103,42 @@ double GradNorm(const double* q, const double* t, const double* g) {
     for (int i = 0; i < 3; ++i) m = std::max(m, std::fabs(t[i] - (t[i] + (-g[3 + i]))));
     return m;
 }
-// returns usable; q, t updated in place; cov (36) when asked
+// What a refinement did, for the tests alone (the product exports none of it): recorded, never read back.
+enum Exit : int32_t {
+    GRADIENT_AT_START, GRADIENT_AFTER_STEP, MAX_ITERATIONS, PARAMETER_TOLERANCE, FUNCTION_TOLERANCE, INVALID_STEPS,
+    MIN_RADIUS, NOT_FINITE_START, NOTHING_TO_REFINE
+};
+struct Trace {
+    int32_t iterations = 0;  // trips of the loop begun
+    int32_t accepted = 0;    // steps taken
+    int32_t rejected = 0;    // steps evaluated and not taken
+    int32_t invalid = 0;     // steps without a positive model cost change
+    int32_t exit = MAX_ITERATIONS;
+    int32_t rank_failed = 0;  // the covariance's rank test
+};
+// returns usable; q, t updated in place; cov (36) when asked; tr filled when given
 bool Refine(const RefOpts& o, double* q, double* t, const double* xy, const double* X, const std::vector<char>& mask,
-            double* cov) {
+            double* cov, Trace* tr = nullptr) {
+    Trace local;
+    Trace& T = tr ? *tr : local;
+    T = Trace();
     if (cov) std::fill(cov, cov + 36, 0.0);
-    if (std::count(mask.begin(), mask.end(), 1) == 0) return true;  // A9
+    if (std::count(mask.begin(), mask.end(), 1) == 0) {  // A9
+        T.exit = NOTHING_TO_REFINE;
+        return true;
+    }
     Eval ev = Evaluate(o, q, t, xy, X, mask, true);
-    if (!std::isfinite(ev.cost)) return false;
+    if (!std::isfinite(ev.cost)) {
+        T.exit = NOT_FINITE_START;
+        return false;
+    }
     double sc[6];
     for (int i = 0; i < 6; ++i) sc[i] = 1.0 / (1.0 + std::sqrt(ev.H[i][i]));
     double radius = 1e4, decrease = 2.0;
     int invalid = 0;
     if (!(GradNorm(q, t, ev.g) <= o.gtol)) {
         for (int64_t it = 1; it <= o.iters; ++it) {
+            T.iterations = static_cast<int32_t>(it);
             double Hs[36], A[36], y[6];
             for (int i = 0; i < 6; ++i) {
                 for (int j = 0; j < 6; ++j) Hs[6 * i + j] = sc[i] * ev.H[i][j] * sc[j];
@@ -1139,8 +1162,15 @@ bool Refine(const RefOpts& o, double* q, double* t, const double* xy, const doub
             if (!valid) {
                 radius = radius / decrease;
                 decrease = 2.0 * decrease;
-                if (++invalid >= 5) return false;
-                if (radius < 1e-32) break;
+                ++T.invalid;
+                if (++invalid >= 5) {
+                    T.exit = INVALID_STEPS;
+                    return false;
+                }
+                if (radius < 1e-32) {
+                    T.exit = MIN_RADIUS;
+                    break;
+                }
                 continue;
             }
             invalid = 0;
@@ -1151,10 +1181,16 @@ bool Refine(const RefOpts& o, double* q, double* t, const double* xy, const doub
             double sn = 0.0, xn = 0.0;
             for (int i = 0; i < 4; ++i) { sn = sn + (q[i] - qn[i]) * (q[i] - qn[i]); xn = xn + q[i] * q[i]; }
             for (int i = 0; i < 3; ++i) { sn = sn + (t[i] - tn[i]) * (t[i] - tn[i]); xn = xn + t[i] * t[i]; }
-            if (std::sqrt(sn) <= 1e-8 * (std::sqrt(xn) + 1e-8)) break;
+            if (std::sqrt(sn) <= 1e-8 * (std::sqrt(xn) + 1e-8)) {
+                T.exit = PARAMETER_TOLERANCE;
+                break;
+            }
             const double cand = Evaluate(o, qn, tn, xy, X, mask, false).cost;
             const double change = ev.cost - (std::isfinite(cand) ? cand : DBL_MAX);
-            if (std::fabs(change) <= 1e-6 * ev.cost) break;
+            if (std::fabs(change) <= 1e-6 * ev.cost) {
+                T.exit = FUNCTION_TOLERANCE;
+                break;
+            }
             const double rel = change / mcc;
             if (rel > 1e-3) {
                 std::memcpy(q, qn, sizeof qn);
@@ -1163,13 +1199,23 @@ bool Refine(const RefOpts& o, double* q, double* t, const double* xy, const doub
                 const double z = 2.0 * rel - 1.0, f = 1.0 - z * z * z;
                 radius = std::min(radius / std::max(f, 1.0 / 3.0), 1e16);
                 decrease = 2.0;
-                if (GradNorm(q, t, ev.g) <= o.gtol) break;
+                ++T.accepted;
+                if (GradNorm(q, t, ev.g) <= o.gtol) {
+                    T.exit = GRADIENT_AFTER_STEP;
+                    break;
+                }
             } else {
                 radius = radius / decrease;
                 decrease = 2.0 * decrease;
-                if (radius < 1e-32) break;
+                ++T.rejected;
+                if (radius < 1e-32) {
+                    T.exit = MIN_RADIUS;
+                    break;
+                }
             }
         }
+    } else {
+        T.exit = GRADIENT_AT_START;
     }
     if (!o.cov) return true;
     double H[36], V[36];
@@ -1181,7 +1227,10 @@ bool Refine(const RefOpts& o, double* q, double* t, const double* xy, const doub
         lmin = std::min(lmin, H[7 * i]);
         lmax = std::max(lmax, H[7 * i]);
     }
-    if (!(lmax > 0.0) || !(lmin > 1e-28 * lmax) || !std::isfinite(lmax)) return false;
+    if (!(lmax > 0.0) || !(lmin > 1e-28 * lmax) || !std::isfinite(lmax)) {
+        T.rank_failed = 1;
+        return false;
+    }
     for (int i = 0; i < 6; ++i)
         for (int j = 0; j < 6; ++j) {
             double s = 0.0;
@@ -1316,10 +1365,11 @@ int abspose_ref_estimate(const uint64_t* off, size_t nq, const int32_t* models, 
     return 0;
 }
 
-int abspose_ref_refine(const uint64_t* off, size_t nq, const int32_t* models, const double* cparams, const double* p2,
-                       const double* p3, const double* init_q, const double* init_t, const uint8_t* in_mask,
-                       const double* ref, int want_cov, uint8_t* success, double* qvec, double* tvec,
-                       double* covariance) {
+// trace: 6 int32 per query (iterations, accepted, rejected, invalid, exit, rank test failed), or null
+int abspose_ref_refine_trace(const uint64_t* off, size_t nq, const int32_t* models, const double* cparams,
+                             const double* p2, const double* p3, const double* init_q, const double* init_t,
+                             const uint8_t* in_mask, const double* ref, int want_cov, uint8_t* success, double* qvec,
+                             double* tvec, double* covariance, int32_t* trace) {
     for (size_t qi = 0; qi < nq; ++qi) {
         const size_t c0 = off[qi], n = off[qi + 1] - off[qi];
         double prm[12] = {};
@@ -1329,10 +1379,23 @@ int abspose_ref_refine(const uint64_t* off, size_t nq, const int32_t* models, co
         std::memcpy(qvec + 4 * qi, init_q + 4 * qi, 4 * sizeof(double));
         std::memcpy(tvec + 3 * qi, init_t + 3 * qi, 3 * sizeof(double));
         const RefOpts ro{models[qi], prm, ref[0], ref[2], static_cast<int64_t>(ref[1]), want_cov != 0};
+        Trace tr;
         success[qi] = Refine(ro, qvec + 4 * qi, tvec + 3 * qi, p2 + 2 * c0, p3 + 3 * c0, m,
-                             covariance ? covariance + 36 * qi : nullptr) ? 1 : 0;
+                             covariance ? covariance + 36 * qi : nullptr, &tr) ? 1 : 0;
+        if (trace) {
+            const int32_t row[6] = {tr.iterations, tr.accepted, tr.rejected, tr.invalid, tr.exit, tr.rank_failed};
+            std::memcpy(trace + 6 * qi, row, sizeof row);
+        }
     }
     return 0;
+}
+
+int abspose_ref_refine(const uint64_t* off, size_t nq, const int32_t* models, const double* cparams, const double* p2,
+                       const double* p3, const double* init_q, const double* init_t, const uint8_t* in_mask,
+                       const double* ref, int want_cov, uint8_t* success, double* qvec, double* tvec,
+                       double* covariance) {
+    return abspose_ref_refine_trace(off, nq, models, cparams, p2, p3, init_q, init_t, in_mask, ref, want_cov, success,
+                                    qvec, tvec, covariance, nullptr);
 }
 
 }  // extern "C"

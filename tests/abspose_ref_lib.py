@@ -43,6 +43,8 @@ def load() -> C.CDLL:
     lib.abspose_ref_estimate.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 8
     lib.abspose_ref_refine.restype = C.c_int
     lib.abspose_ref_refine.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 8 + [C.c_int] + [C.c_void_p] * 4
+    lib.abspose_ref_refine_trace.restype = C.c_int
+    lib.abspose_ref_refine_trace.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 8 + [C.c_int] + [C.c_void_p] * 5
     _lib = lib
     return lib
 
@@ -95,8 +97,16 @@ def estimate(offsets, camera_models, camera_params, points2D, points3D, estimati
     return _finish(r, nq, n, return_covariance)
 
 
+# the exit codes of abspose_ref_refine_trace, in the order of abspose_ref.cc's enum Exit
+EXITS = ("GRADIENT_AT_START", "GRADIENT_AFTER_STEP", "MAX_ITERATIONS", "PARAMETER_TOLERANCE", "FUNCTION_TOLERANCE",
+         "INVALID_STEPS", "MIN_RADIUS", "NOT_FINITE_START", "NOTHING_TO_REFINE")
+TRACE_FIELDS = ("iterations", "accepted", "rejected", "invalid", "exit", "rank_failed")
+
+
 def refine(offsets, camera_models, camera_params, points2D, points3D, qvec, tvec, inlier_mask, refinement=None,
-           return_covariance=False):
+           return_covariance=False, trace=False):
+    """The reference's refinement alone.  With trace, (result, trace): per query what the solver did, (Q,) int32 arrays
+    by TRACE_FIELDS, `exit` an index into EXITS.  The product has no such output."""
     off, models, prm, p2, p3 = abspose_inputs(offsets, camera_models, camera_params, points2D, points3D)
     _, ro = abspose_options(None, refinement)
     nq, n = off.size - 1, int(off[-1])
@@ -106,16 +116,19 @@ def refine(offsets, camera_models, camera_params, points2D, points3D, qvec, tvec
     r = dict(success=np.zeros(nq, np.uint8), qvec=np.zeros((nq, 4)), tvec=np.zeros((nq, 3)),
              covariance=np.zeros((max(nq, 1), 36)))
     _check_opts(None, ro)
-    rc = load().abspose_ref_refine(_p(off), nq, _p(models), _p(prm), _p(p2), _p(p3), _p(q), _p(t), _p(m),
-                                   _p(_ref_vec(ro)), int(bool(return_covariance)), _p(r["success"]), _p(r["qvec"]), _p(r["tvec"]),
-                                   _p(r["covariance"]) if return_covariance else None)
+    args = (_p(off), nq, _p(models), _p(prm), _p(p2), _p(p3), _p(q), _p(t), _p(m), _p(_ref_vec(ro)),
+            int(bool(return_covariance)), _p(r["success"]), _p(r["qvec"]), _p(r["tvec"]),
+            _p(r["covariance"]) if return_covariance else None)
+    rows = np.zeros((max(nq, 1), len(TRACE_FIELDS)), np.int32)
+    rc = load().abspose_ref_refine_trace(*args, _p(rows)) if trace else load().abspose_ref_refine(*args)
     if rc != 0:
         raise ValueError("abspose_ref_refine: invalid options")
     r["num_inliers"] = np.array([int(m[int(off[i]):int(off[i + 1])].sum()) for i in range(nq)], np.uint32)
     r["num_trials"] = np.zeros(nq, np.uint64)
     r["focal_factor"] = np.ones(nq)
     r["inlier_mask"] = m
-    return _finish(r, nq, n, return_covariance)
+    r = _finish(r, nq, n, return_covariance)
+    return (r, {k: rows[:nq, i].copy() for i, k in enumerate(TRACE_FIELDS)}) if trace else r
 
 
 def _est_vec(eo):

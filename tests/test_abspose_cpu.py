@@ -329,3 +329,187 @@ def test_agreement_with_recorded_pycolmap():
     print(f"pycolmap agreement: {poses} of {both} poses within 1e-6, inlier-mask agreement {np.mean(agree):.4f}")
     assert np.mean(agree) > 0.95
     assert poses >= 0.9 * both
+
+
+# ---- the edge cases: what abspose_cases.cases() leaves out ---------------------------------------------
+GOLDEN_EDGES = ROOT / "tests" / "golden" / "abspose_ref_edges_v1.npz"
+EDGES = abspose_cases.EDGE_CASES
+
+
+def maker():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("mk", ROOT / "tests" / "golden" / "make_abspose_ref_golden.py")
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    return mk
+
+
+@pytest.fixture(scope="module")
+def golden_edges():
+    return maker().load_edges()
+
+
+@pytest.fixture(scope="module")
+def solved_edges():
+    """the reference on every edge case, once: name -> (result, trace rows or None)"""
+    mk = maker()
+    return {name: mk.edge_reference(name) for name in EDGES}
+
+
+def test_edge_fixture_lists_the_edge_cases(golden_edges):
+    assert sorted(golden_edges) == sorted(EDGES)
+    assert GOLDEN_EDGES.stat().st_size < 20_000
+    assert len(abspose_cases.cases()) == 23
+
+
+@pytest.mark.parametrize("name", sorted(EDGES))
+def test_reference_equals_its_edge_fixture_bit_for_bit(name, golden_edges, solved_edges):
+    r, tr = solved_edges[name]
+    want_digest, want_trace = golden_edges[name]
+    assert abspose_cases.digest(r) == want_digest
+    assert (tr is None) == (want_trace is None) and (tr is None or np.array_equal(tr, want_trace))
+
+
+def test_trace_records_and_does_not_compute(solved_edges):
+    for name in ("refine_model4", "refine_count1_cov", "refine_nan_quat", "refine_min_radius"):
+        plain = abspose_cases.edge_run(name, ref.estimate, ref.refine)
+        assert abspose_cases.digest(plain) == abspose_cases.digest(solved_edges[name][0]), name
+
+
+def test_edge_cases_reach_the_exits_and_paths(solved_edges):
+    """by the reference's own results and trace and the cases' own shapes, so that the list cannot decay"""
+    res = {n: solved_edges[n][0] for n in EDGES}
+    trace = {n: dict(zip(ref.TRACE_FIELDS, solved_edges[n][1].T)) for n in EDGES if solved_edges[n][1] is not None}
+    exits = lambda n: [ref.EXITS[e] for e in trace[n]["exit"]]  # noqa: E731
+    sizes = lambda n: np.diff(EDGES[n][1]["offsets"].astype(np.int64)).tolist()  # noqa: E731
+    kinds = {n: EDGES[n][0] for n in EDGES}
+    assert set(trace) == {n for n in EDGES if kinds[n] == "refine"}
+    for n in EDGES:
+        assert max(sizes(n)) <= (200 if kinds[n] == "estimate" else 129), n
+
+    # the lane edges
+    for n in (63, 64, 65, 127, 128, 129):
+        kind, _, est, _, cov = EDGES[f"n{n}"]
+        assert sizes(f"n{n}") == [n] and est == abspose_cases.FAST and cov == (n % 2 == 1)
+        assert res[f"n{n}"]["success"].all()
+    for k in (64, 65):
+        sc = EDGES[f"inliers{k}"][1]
+        assert sizes(f"inliers{k}") == [100] and int(sc["outlier"].sum()) == 100 - k
+        assert res[f"inliers{k}"]["num_inliers"].tolist() == [k] and res[f"inliers{k}"]["success"].all()
+        assert np.array_equal(res[f"inliers{k}"]["inlier_mask"], ~sc["outlier"])
+
+    # RANSAC control
+    assert EDGES["trials_equal"][2] == dict(min_num_trials=50, max_num_trials=50)
+    assert res["trials_equal"]["num_trials"].tolist() == [50] and res["trials_equal"]["success"].all()
+    assert EDGES["one_trial"][2]["max_num_trials"] == 1 and res["one_trial"]["num_trials"].tolist() == [1]
+    est = EDGES["ratio_clamp"][2]
+    eo, _ = ref.abspose_options(est, None)
+    clamp = math.ceil(math.log(1.0 - eo.confidence) / math.log(1.0 - est["min_inlier_ratio"] ** 3)
+                      * eo.dyn_num_trials_multiplier)
+    assert est["min_inlier_ratio"] == 0.5 and abs(EDGES["ratio_clamp"][1]["outlier"].mean() - 0.6) < 0.1
+    assert res["ratio_clamp"]["num_trials"].tolist() == [clamp] and clamp < est["max_num_trials"]
+    # confidence 0: ComputeNumTrials is 0 for every inlier count, so the constructor's clamp leaves no trial at all;
+    # confidence 1: it is the largest count, so nothing stops a run before max_num_trials
+    assert EDGES["confidence0"][2]["confidence"] == 0.0 and EDGES["confidence1"][2]["confidence"] == 1.0
+    assert res["confidence0"]["num_trials"].tolist() == [0] and not res["confidence0"]["success"].any()
+    assert res["confidence1"]["num_trials"].tolist() == [abspose_cases.FAST["max_num_trials"]]
+    assert res["confidence1"]["success"].all()
+    # the sample stream's overrun: the middle query alone draws past the first table
+    assert EDGES["overrun_shared_launch"][2] == abspose_cases.OVERRUN and sizes("overrun_shared_launch") == [40, 120, 200]
+    assert abspose_cases.FIRST_STREAM_WORDS == 3 * 2000 + 1024
+    assert (3 * res["overrun_shared_launch"]["num_trials"] > abspose_cases.FIRST_STREAM_WORDS).tolist() == \
+        [False, True, False]
+    assert res["overrun_shared_launch"]["success"].all()
+    sc, est, rf, cov = abspose_cases.cases()["outliers80"]
+    r80 = ref.estimate(sc["offsets"], sc["camera_models"], sc["camera_params"], sc["points2D"], sc["points3D"], est, rf,
+                       cov)
+    assert est == {} and (3 * r80["num_trials"] > abspose_cases.FIRST_STREAM_WORDS).all()
+
+    # focal-length estimation
+    for m in (1, 4, 5, 7, 8, 10):
+        kind, sc, est, _, cov = EDGES[f"focal_model{m}"]
+        assert sc["camera_models"].tolist() == [m] and sizes(f"focal_model{m}") == [150] and cov
+        assert est == dict(estimate_focal_length=1, num_focal_length_samples=4, min_num_trials=30, max_num_trials=500)
+        assert res[f"focal_model{m}"]["success"].all() and res[f"focal_model{m}"]["focal_factor"][0] != 1.0
+    kind, sc, est, rf, cov = EDGES["focal_tie"]
+    factors = ref.focal_factors(**{k: v for k, v in est.items() if "focal" in k})
+    assert len(factors) == 7 and factors[0] == 0.9 and sizes("focal_tie") == [80]
+    alone = dict({k: v for k, v in est.items() if "focal" not in k})
+    for f in factors:  # each factor alone, as a camera scaled beforehand: all count every correspondence
+        prm = [sc["camera_params"][0] * np.array([f, 1.0, 1.0])]
+        one = ref.estimate(sc["offsets"], sc["camera_models"], prm, sc["points2D"], sc["points3D"], alone, rf, cov)
+        assert one["success"].all() and one["num_inliers"].tolist() == [80], f
+    assert res["focal_tie"]["focal_factor"].tolist() == [0.9] and res["focal_tie"]["num_inliers"].tolist() == [80]
+    assert res["focal_tie"]["success"].all()
+    r = res["focal_all_fail"]
+    assert EDGES["focal_all_fail"][2]["estimate_focal_length"] == 1 and sizes("focal_all_fail") == [2, 60]
+    assert not r["success"].any() and r["focal_factor"].tolist() == [0.0, 0.0] and not r["inlier_mask"].any()
+    assert r["num_inliers"].tolist() == [0, 0] and not r["qvec"].any() and not r["tvec"].any()
+    sc = EDGES["focal_mixed_batch"][1]
+    assert sc["camera_models"].tolist() == [0, 5, 4, 7, 1, 10, 2, 8, 6, 9]
+    n = sizes("focal_mixed_batch")
+    assert n[6] == 0 and n[7] == 2 and all(40 <= v <= 130 for i, v in enumerate(n) if i not in (6, 7))
+    assert EDGES["focal_mixed_batch"][2]["num_focal_length_samples"] == 4
+    assert res["focal_mixed_batch"]["success"].tolist() == [i not in (6, 7) for i in range(10)]
+
+    # refinement alone
+    for m in range(11):
+        assert EDGES[f"refine_model{m}"][1]["camera_models"].tolist() == [m] and sizes(f"refine_model{m}") == [120]
+        assert res[f"refine_model{m}"]["success"].all() and trace[f"refine_model{m}"]["accepted"][0] > 0
+    for k in (0, 1, 2, 3, 4, 64, 65):
+        for suffix, cov in (("", False), ("_cov", True)):
+            name = f"refine_count{k}{suffix}"
+            sc = EDGES[name][1]
+            assert sc["camera_models"].tolist() == [4] and sizes(name) == [100] and EDGES[name][4] == cov
+            assert int(sc["mask"].sum()) == k and res[name]["num_inliers"].tolist() == [k]
+            assert res[name]["success"].tolist() == [not (cov and k in (1, 2))], name
+            assert trace[name]["rank_failed"].tolist() == [int(cov and k in (1, 2))], name
+        assert exits(f"refine_count{k}") == exits(f"refine_count{k}_cov")
+    for suffix in ("", "_cov"):
+        name = f"refine_count0{suffix}"
+        assert exits(name) == ["NOTHING_TO_REFINE"]
+        assert np.array_equal(res[name]["qvec"].view(np.uint64), EDGES[name][1]["start_q"].view(np.uint64))
+        assert np.array_equal(res[name]["tvec"].view(np.uint64), EDGES[name][1]["start_t"].view(np.uint64))
+    assert not res["refine_count0_cov"]["covariance"].any() and not res["refine_count1_cov"]["covariance"].any()
+    for n in (63, 64, 65, 129):
+        assert sizes(f"refine_n{n}") == [n] and EDGES[f"refine_n{n}"][1]["mask"].all()
+        assert res[f"refine_n{n}"]["success"].all()
+    assert sizes("refine_empty_between")[1] == 0 and min(sizes("refine_empty_between")[::2]) > 0
+    assert res["refine_empty_between"]["success"].all() and exits("refine_empty_between")[1] == "NOTHING_TO_REFINE"
+    assert trace["refine_empty_between"]["accepted"][[0, 2]].min() > 0
+    assert np.isnan(EDGES["refine_nan_quat"][1]["start_q"][0]).any()
+    for name, ok in (("refine_nan_quat", False), ("refine_nan_point_in_mask", False),
+                     ("refine_nan_point_outside_mask", True)):
+        assert res[name]["success"].tolist() == [ok, True], name
+        assert (exits(name)[0] == "NOT_FINITE_START") == (not ok), name
+    for name, inside in (("refine_nan_point_in_mask", True), ("refine_nan_point_outside_mask", False)):
+        sc = EDGES[name][1]
+        bad = np.isnan(sc["points3D"]).any(axis=1)
+        assert bad.sum() == 1 and bad[:60].any() and sc["mask"][bad].tolist() == [inside]
+
+    # the exits
+    for it in (0, 1, 3):
+        name = f"refine_iterations{it}"
+        assert EDGES[name][3] == dict(gradient_tolerance=0.0, max_num_iterations=it)
+        assert exits(name) == ["MAX_ITERATIONS"] and trace[name]["iterations"].tolist() == [it]
+    moved = lambda name: (np.abs(res[name]["tvec"] - EDGES[name][1]["start_t"]).max())  # noqa: E731
+    assert moved("refine_iterations0") == 0.0 and moved("refine_iterations1") > 0.0
+    assert EDGES["refine_far_start"][3] == dict(gradient_tolerance=0.0) and trace["refine_far_start"]["accepted"][0] >= 5
+    assert np.abs(EDGES["refine_far_start"][1]["start_t"] - EDGES["refine_far_start"][1]["tvec"]).max() > 1.0
+    assert EDGES["refine_at_optimum"][3] == {} and exits("refine_at_optimum") == ["GRADIENT_AT_START"]
+    assert trace["refine_at_optimum"]["iterations"].tolist() == [0] and moved("refine_at_optimum") == 0.0
+    assert exits("refine_function_tolerance") == ["FUNCTION_TOLERANCE"]
+    assert exits("refine_parameter_tolerance") == ["PARAMETER_TOLERANCE"]
+    assert trace["refine_function_tolerance"]["accepted"][0] > 0 and trace["refine_parameter_tolerance"]["accepted"][0] > 0
+    t = trace["refine_rejected_then_accepted"]
+    assert t["accepted"][0] > 0 and t["rejected"][0] > 0 and res["refine_rejected_then_accepted"]["success"].all()
+    assert exits("refine_invalid_steps") == ["INVALID_STEPS"] and trace["refine_invalid_steps"]["invalid"].tolist() == [5]
+    assert not res["refine_invalid_steps"]["success"].any() and moved("refine_invalid_steps") == 0.0
+    assert exits("refine_min_radius") == ["MIN_RADIUS"] and trace["refine_min_radius"]["rejected"].tolist() == [15]
+    assert res["refine_min_radius"]["success"].all() and moved("refine_min_radius") == 0.0
+    reached = {e for n in trace for e in exits(n)}
+    assert reached == set(ref.EXITS), sorted(set(ref.EXITS) - reached)
+    assert any(trace[n]["exit"][i] == ref.EXITS.index("GRADIENT_AFTER_STEP") and trace[n]["accepted"][i] > 0
+               for n in trace for i in range(len(trace[n]["exit"])))
+    assert any(t["rank_failed"].any() for t in trace.values())
+    assert any(((t["accepted"] > 0) & (t["rejected"] > 0)).any() for t in trace.values())

@@ -2,7 +2,12 @@
 pycolmap_amd.absolute_pose_estimation / pose_refinement) against its CPU reference (tests/abspose_ref): success,
 pose bits, inlier and trial counts, masks, focal factors and covariance bits identical over clean, noisy and outlier
 queries, 3 to 20,000 correspondences, all eleven camera models, focal-length estimation, trial caps, error limits,
-degenerate input, refinement alone and batches in any order or split."""
+degenerate input, refinement alone and batches in any order or split; and the same over abspose_cases.EDGE_CASES: the
+lane edges, the RANSAC limits, a sample-stream rerun beside queries that need none, focal-length estimation on every
+kind of camera, a tie and a failure of every factor, refinement alone through every exit of its solver, and a split on
+the query count."""
+from pathlib import Path
+
 import numpy as np
 import pytest
 
@@ -45,6 +50,8 @@ def test_bit_exact_to_reference(amc_ctx, name):
     assert got["device_ms"] > 0 and got["num_batches"] == 1
     if name in ("clean", "noisy", "outliers30", "outliers60") or name.startswith("model"):
         assert got["success"].all()
+    if name == "outliers80":  # every query draws past the first sample stream: the batch is rerun on a longer one
+        assert (3 * got["num_trials"] > abspose_cases.FIRST_STREAM_WORDS).all()
 
 
 def test_large_query_20000(amc_ctx):
@@ -134,3 +141,72 @@ def test_focal_estimation_scales_camera_in_place(amc_ctx):
     assert np.asarray(cam.params)[0] == wrong[0] * want["focal_factor"][0]
     assert abs(np.asarray(cam.params)[0] / 1200.0 - 1.0) < 0.2
     assert np.array_equal(np.asarray(cam.params)[1:], wrong[1:])
+
+
+# ---- the edge cases -----------------------------------------------------------------------------------
+EDGES = abspose_cases.EDGE_CASES
+MAKER = Path(__file__).resolve().parent / "golden" / "make_abspose_ref_golden.py"  # (it reads the edge fixture)
+FAST_BATCH = sorted(n for n in EDGES if EDGES[n][0] == "estimate" and EDGES[n][2] == abspose_cases.FAST)
+
+
+@pytest.fixture(scope="module")
+def golden_edges():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("mk", MAKER)
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    return mk.load_edges()
+
+
+@pytest.mark.parametrize("name", sorted(EDGES))
+def test_edge_case_bit_exact_to_reference_and_fixture(amc_ctx, golden_edges, name):
+    got = abspose_cases.edge_run(name, amc_ctx.estimate_absolute_poses, amc_ctx.refine_absolute_poses)
+    want = abspose_cases.edge_run(name, ref.estimate, ref.refine)
+    assert_same(got, want, name)
+    assert abspose_cases.digest(got) == golden_edges[name][0]
+    assert got["num_batches"] == 1
+
+
+def test_edge_cases_as_one_batch_in_any_order(amc_ctx):
+    assert len(FAST_BATCH) >= 8
+    each = [gpu(amc_ctx, EDGES[n][1], abspose_cases.FAST, None, True) for n in FAST_BATCH]
+    for order in (np.arange(len(FAST_BATCH)), np.random.default_rng(2).permutation(len(FAST_BATCH))):
+        whole = gpu(amc_ctx, abspose_cases.concat(*[EDGES[FAST_BATCH[i]][1] for i in order]), abspose_cases.FAST, None,
+                    True)
+        lens = [len(each[i]["inlier_mask"]) for i in order]
+        ends = np.cumsum(lens)
+        for j, i in enumerate(order):
+            part = {k: whole[k][j:j + 1] for k in FIELDS if k != "inlier_mask"}
+            part["inlier_mask"] = whole["inlier_mask"][ends[j] - lens[j]:ends[j]]
+            assert_same(part, {k: each[i][k] for k in FIELDS}, f"{FAST_BATCH[i]} at {j}")
+
+
+def test_split_on_query_count(amc_ctx):
+    # 2^16 queries fill one device batch: the 65,537th, whose RANSAC outruns the first sample stream, is a batch of its own
+    last = abspose_cases.overrun_query()
+    sc = abspose_cases.concat(abspose_cases.tiny_queries(7, 1 << 16), last)
+    got = gpu(amc_ctx, sc, abspose_cases.OVERRUN)
+    assert got["num_batches"] >= 2
+    want = cpu(sc, abspose_cases.OVERRUN)
+    assert 3 * want["num_trials"][-1] > abspose_cases.FIRST_STREAM_WORDS >= 3 * want["num_trials"][:-1].max()
+    assert want["success"].all()
+    assert_same(got, want, "65,537 queries")
+    one = gpu(amc_ctx, last, abspose_cases.OVERRUN)
+    part = {k: got[k][-1:] for k in FIELDS if k in got and k != "inlier_mask"}
+    part["inlier_mask"] = got["inlier_mask"][-len(one["inlier_mask"]):]
+    assert_same(part, {k: one[k] for k in FIELDS if k in one}, "the last query alone")
+
+
+def test_no_queries(amc_ctx):
+    none = (np.zeros(1, np.uint64), np.zeros(0, np.int32), [], np.zeros((0, 2)), np.zeros((0, 3)))
+    for cov in (False, True):
+        for got in (amc_ctx.estimate_absolute_poses(*none, None, None, cov),
+                    amc_ctx.refine_absolute_poses(*none, np.zeros((0, 4)), np.zeros((0, 3)), np.zeros(0, bool), None, cov)):
+            assert got["num_batches"] == 0
+            for k in FIELDS:
+                if k == "covariance" and not cov:
+                    assert k not in got
+                else:
+                    assert len(got[k]) == 0, k
+            assert got["qvec"].shape == (0, 4) and got["tvec"].shape == (0, 3)
+            assert not cov or got["covariance"].shape == (0, 6, 6)

@@ -387,18 +387,30 @@ Eval RigEvaluate(const RigRefOpts& o, const RigProblem& pr, const double* q, con
     for (int i = 0; i < 6; ++i) e.g[i] = s[22 + i];
     return e;
 }
-// 12.7 / 12.8 with the rig residual: returns usable; q, t updated in place; cov (36) when asked
-bool RigRefine(const RigRefOpts& o, const RigProblem& pr, double* q, double* t, const std::vector<char>& mask, double* cov) {
+// 12.7 / 12.8 with the rig residual: returns usable; q, t updated in place; cov (36) when asked; tr (abspose_ref.cc's
+// Trace: recorded, never read back) filled when given
+bool RigRefine(const RigRefOpts& o, const RigProblem& pr, double* q, double* t, const std::vector<char>& mask, double* cov,
+               Trace* tr = nullptr) {
+    Trace local;
+    Trace& T = tr ? *tr : local;
+    T = Trace();
     if (cov) std::fill(cov, cov + 36, 0.0);
-    if (std::count(mask.begin(), mask.end(), 1) == 0) return true;
+    if (std::count(mask.begin(), mask.end(), 1) == 0) {
+        T.exit = NOTHING_TO_REFINE;
+        return true;
+    }
     Eval ev = RigEvaluate(o, pr, q, t, mask, true);
-    if (!std::isfinite(ev.cost)) return false;
+    if (!std::isfinite(ev.cost)) {
+        T.exit = NOT_FINITE_START;
+        return false;
+    }
     double sc[6];
     for (int i = 0; i < 6; ++i) sc[i] = 1.0 / (1.0 + std::sqrt(ev.H[i][i]));
     double radius = 1e4, decrease = 2.0;
     int invalid = 0;
     if (!(GradNorm(q, t, ev.g) <= o.gtol)) {
         for (int64_t it = 1; it <= o.iters; ++it) {
+            T.iterations = static_cast<int32_t>(it);
             double Hs[36], A[36], y[6];
             for (int i = 0; i < 6; ++i) {
                 for (int j = 0; j < 6; ++j) Hs[6 * i + j] = sc[i] * ev.H[i][j] * sc[j];
@@ -422,8 +434,15 @@ bool RigRefine(const RigRefOpts& o, const RigProblem& pr, double* q, double* t, 
             if (!valid) {
                 radius = radius / decrease;
                 decrease = 2.0 * decrease;
-                if (++invalid >= 5) return false;
-                if (radius < 1e-32) break;
+                ++T.invalid;
+                if (++invalid >= 5) {
+                    T.exit = INVALID_STEPS;
+                    return false;
+                }
+                if (radius < 1e-32) {
+                    T.exit = MIN_RADIUS;
+                    break;
+                }
                 continue;
             }
             invalid = 0;
@@ -434,10 +453,16 @@ bool RigRefine(const RigRefOpts& o, const RigProblem& pr, double* q, double* t, 
             double sn = 0.0, xn = 0.0;
             for (int i = 0; i < 4; ++i) { sn = sn + (q[i] - qn[i]) * (q[i] - qn[i]); xn = xn + q[i] * q[i]; }
             for (int i = 0; i < 3; ++i) { sn = sn + (t[i] - tn[i]) * (t[i] - tn[i]); xn = xn + t[i] * t[i]; }
-            if (std::sqrt(sn) <= 1e-8 * (std::sqrt(xn) + 1e-8)) break;
+            if (std::sqrt(sn) <= 1e-8 * (std::sqrt(xn) + 1e-8)) {
+                T.exit = PARAMETER_TOLERANCE;
+                break;
+            }
             const double cand = RigEvaluate(o, pr, qn, tn, mask, false).cost;
             const double change = ev.cost - (std::isfinite(cand) ? cand : DBL_MAX);
-            if (std::fabs(change) <= 1e-6 * ev.cost) break;
+            if (std::fabs(change) <= 1e-6 * ev.cost) {
+                T.exit = FUNCTION_TOLERANCE;
+                break;
+            }
             const double rel = change / mcc;
             if (rel > 1e-3) {
                 std::memcpy(q, qn, sizeof qn);
@@ -446,13 +471,23 @@ bool RigRefine(const RigRefOpts& o, const RigProblem& pr, double* q, double* t, 
                 const double z = 2.0 * rel - 1.0, f = 1.0 - z * z * z;
                 radius = std::min(radius / std::max(f, 1.0 / 3.0), 1e16);
                 decrease = 2.0;
-                if (GradNorm(q, t, ev.g) <= o.gtol) break;
+                ++T.accepted;
+                if (GradNorm(q, t, ev.g) <= o.gtol) {
+                    T.exit = GRADIENT_AFTER_STEP;
+                    break;
+                }
             } else {
                 radius = radius / decrease;
                 decrease = 2.0 * decrease;
-                if (radius < 1e-32) break;
+                ++T.rejected;
+                if (radius < 1e-32) {
+                    T.exit = MIN_RADIUS;
+                    break;
+                }
             }
         }
+    } else {
+        T.exit = GRADIENT_AT_START;
     }
     if (!o.cov) return true;
     double H[36], V[36];
@@ -464,7 +499,10 @@ bool RigRefine(const RigRefOpts& o, const RigProblem& pr, double* q, double* t, 
         lmin = std::min(lmin, H[7 * i]);
         lmax = std::max(lmax, H[7 * i]);
     }
-    if (!(lmax > 0.0) || !(lmin > 1e-28 * lmax) || !std::isfinite(lmax)) return false;
+    if (!(lmax > 0.0) || !(lmin > 1e-28 * lmax) || !std::isfinite(lmax)) {
+        T.rank_failed = 1;
+        return false;
+    }
     for (int i = 0; i < 6; ++i)
         for (int j = 0; j < 6; ++j) {
             double s = 0.0;
@@ -505,6 +543,12 @@ void rigpose_ref_support(size_t n, size_t ncam, const int32_t* models, const dou
     for (size_t k = 0; k < n; ++k) mask[k] = m[k];
 }
 
+// the point ids (13.2) of n world points
+void rigpose_ref_point_ids(size_t n, const double* X, uint32_t* ids) {
+    const std::vector<uint32_t> id = PointIds(n, X);
+    std::copy(id.begin(), id.end(), ids);
+}
+
 // is the support a (cnt, uniq, sum) better than b
 int rigpose_ref_better(const double* a, const double* b) {
     RigSupport x, y;
@@ -528,12 +572,13 @@ void rigpose_ref_residual(int model, const double* cparams, const double* rig, c
 }
 
 // est: max_error, min_inlier_ratio, confidence, dyn_num_trials_multiplier, min_num_trials, max_num_trials; ref:
-// gradient_tolerance, max_num_iterations, loss_function_scale (all as doubles)
-int rigpose_ref_estimate(const uint64_t* off, size_t nq, const uint64_t* coff, const int32_t* models,
+// gradient_tolerance, max_num_iterations, loss_function_scale (all as doubles); trace: 6 int32 per query (iterations,
+// accepted, rejected, invalid, exit, rank test failed; exit -1 where no refinement ran), or null
+int rigpose_ref_estimate_trace(const uint64_t* off, size_t nq, const uint64_t* coff, const int32_t* models,
                          const double* cparams, const double* rigs, const int32_t* cidx, const double* p2,
                          const double* p3, const double* est, const double* ref, int want_cov, uint8_t* success,
                          double* qvec, double* tvec, uint32_t* num_inliers, uint32_t* num_all_inliers,
-                         uint64_t* num_trials, double* covariance, uint8_t* mask) {
+                               uint64_t* num_trials, double* covariance, uint8_t* mask, int32_t* trace) {
     const uint64_t min_t = static_cast<uint64_t>(est[4]);
     const uint64_t max_t = std::min(static_cast<uint64_t>(est[5]),
                                     NumTrials(static_cast<uint64_t>(est[1] * 100000), 100000, est[2], est[3]));
@@ -544,6 +589,10 @@ int rigpose_ref_estimate(const uint64_t* off, size_t nq, const uint64_t* coff, c
         const int32_t* ci = cidx + c0;
         double* cv = covariance ? covariance + 36 * qi : nullptr;
         if (cv) std::fill(cv, cv + 36, 0.0);
+        if (trace) {
+            const int32_t row[6] = {0, 0, 0, 0, -1, 0};
+            std::memcpy(trace + 6 * qi, row, sizeof row);
+        }
         std::vector<double> uv(2 * n);
         double sum = 0.0;
         for (size_t k = 0; k < n; ++k) {
@@ -570,9 +619,22 @@ int rigpose_ref_estimate(const uint64_t* off, size_t nq, const uint64_t* coff, c
         double* t = tvec + 3 * qi;
         if (!ModelToPose(r.model, q, t)) continue;
         const RigRefOpts ro{ref[0], ref[2], static_cast<int64_t>(ref[1]), want_cov != 0};
-        success[qi] = RigRefine(ro, RigProblem{cams.data(), ci, p2 + 2 * c0, p3 + 3 * c0}, q, t, r.mask, cv) ? 1 : 0;
+        Trace tr;
+        success[qi] = RigRefine(ro, RigProblem{cams.data(), ci, p2 + 2 * c0, p3 + 3 * c0}, q, t, r.mask, cv, &tr) ? 1 : 0;
+        if (trace) {
+            const int32_t row[6] = {tr.iterations, tr.accepted, tr.rejected, tr.invalid, tr.exit, tr.rank_failed};
+            std::memcpy(trace + 6 * qi, row, sizeof row);
+        }
     }
     return 0;
+}
+int rigpose_ref_estimate(const uint64_t* off, size_t nq, const uint64_t* coff, const int32_t* models,
+                         const double* cparams, const double* rigs, const int32_t* cidx, const double* p2,
+                         const double* p3, const double* est, const double* ref, int want_cov, uint8_t* success,
+                         double* qvec, double* tvec, uint32_t* num_inliers, uint32_t* num_all_inliers,
+                         uint64_t* num_trials, double* covariance, uint8_t* mask) {
+    return rigpose_ref_estimate_trace(off, nq, coff, models, cparams, rigs, cidx, p2, p3, est, ref, want_cov, success, qvec,
+                                      tvec, num_inliers, num_all_inliers, num_trials, covariance, mask, nullptr);
 }
 
 }  // extern "C"

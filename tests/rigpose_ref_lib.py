@@ -40,6 +40,10 @@ def load() -> C.CDLL:
     lib.rigpose_ref_residual.argtypes = [C.c_int] + [C.c_void_p] * 8
     lib.rigpose_ref_estimate.restype = C.c_int
     lib.rigpose_ref_estimate.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 9 + [C.c_int] + [C.c_void_p] * 8
+    lib.rigpose_ref_estimate_trace.restype = C.c_int
+    lib.rigpose_ref_estimate_trace.argtypes = lib.rigpose_ref_estimate.argtypes + [C.c_void_p]
+    lib.rigpose_ref_point_ids.restype = None
+    lib.rigpose_ref_point_ids.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -77,6 +81,14 @@ def support(camera_models, camera_params, cams_from_rig, camera_idxs, uv, X, mod
     return int(out[0]), int(out[1]), float(out[2]), mask[:idx.size].astype(bool)
 
 
+def point_ids(X):
+    """The point ids (13.2) of world points X (N, 3): for each the index of the first point equal to it."""
+    X = _f(X, (-1, 3))
+    ids = np.zeros(max(len(X), 1), np.uint32)
+    load().rigpose_ref_point_ids(len(X), _p(X), _p(ids))
+    return ids[:len(X)]
+
+
 def better(a, b) -> bool:
     """Is the support a = (num_inliers, num_unique_inliers, residual_sum) better than b (13.5)."""
     return bool(load().rigpose_ref_better(_p(_f(a, (3,))), _p(_f(b, (3,)))))
@@ -92,9 +104,18 @@ def residual(model, params, cam_from_rig, q, t, X, xy):
     return res, jac
 
 
+# the exit codes of rigpose_ref_estimate_trace, in the order of abspose_ref.cc's enum Exit; -1 (EXITS[-1]): no refinement
+# ran, the RANSAC having failed
+EXITS = ("GRADIENT_AT_START", "GRADIENT_AFTER_STEP", "MAX_ITERATIONS", "PARAMETER_TOLERANCE", "FUNCTION_TOLERANCE",
+         "INVALID_STEPS", "MIN_RADIUS", "NOT_FINITE_START", "NOTHING_TO_REFINE", "NOT_REFINED")
+TRACE_FIELDS = ("iterations", "accepted", "rejected", "invalid", "exit", "rank_failed")
+
+
 def estimate(offsets, camera_offsets, camera_models, camera_params, cams_from_rig, camera_idxs, points2D, points3D,
-             estimation=None, refinement=None, return_covariance=False):
-    """The reference on a batch, in Context.estimate_rig_absolute_poses' result form (without the timings)."""
+             estimation=None, refinement=None, return_covariance=False, trace=False):
+    """The reference on a batch, in Context.estimate_rig_absolute_poses' result form (without the timings).  With trace,
+    (result, trace): per query what the refinement did, (Q,) int32 arrays by TRACE_FIELDS, `exit` an index into EXITS.
+    The product has no such output."""
     off, coff, models, prm, rigs, idx, p2, p3 = rigpose_inputs(offsets, camera_offsets, camera_models, camera_params,
                                                                cams_from_rig, camera_idxs, points2D, points3D)
     eo, ro = rigpose_options(estimation, refinement)
@@ -115,14 +136,16 @@ def estimate(offsets, camera_offsets, camera_models, camera_params, cams_from_ri
     est = np.array([eo.max_error, eo.min_inlier_ratio, eo.confidence, eo.dyn_num_trials_multiplier, eo.min_num_trials,
                     eo.max_num_trials], np.float64)
     ref = np.array([ro.gradient_tolerance, ro.max_num_iterations, ro.loss_function_scale], np.float64)
-    load().rigpose_ref_estimate(_p(off), nq, _p(coff), _p(models), _p(prm), _p(rigs), _p(idx), _p(p2), _p(p3), _p(est),
-                                _p(ref), int(bool(return_covariance)), _p(r["success"]), _p(r["qvec"]), _p(r["tvec"]),
-                                _p(r["num_inliers"]), _p(r["num_all_inliers"]), _p(r["num_trials"]),
-                                _p(r["covariance"]) if return_covariance else None, _p(r["inlier_mask"]))
+    rows = np.zeros((max(nq, 1), len(TRACE_FIELDS)), np.int32)
+    fn = load().rigpose_ref_estimate_trace if trace else load().rigpose_ref_estimate
+    fn(_p(off), nq, _p(coff), _p(models), _p(prm), _p(rigs), _p(idx), _p(p2), _p(p3), _p(est),
+       _p(ref), int(bool(return_covariance)), _p(r["success"]), _p(r["qvec"]), _p(r["tvec"]),
+       _p(r["num_inliers"]), _p(r["num_all_inliers"]), _p(r["num_trials"]),
+       _p(r["covariance"]) if return_covariance else None, _p(r["inlier_mask"]), *([_p(rows)] if trace else []))
     r["success"] = r["success"].astype(bool)
     r["inlier_mask"] = r["inlier_mask"][:n].astype(bool)
     if return_covariance:
         r["covariance"] = r["covariance"][:nq].reshape(nq, 6, 6)
     else:
         del r["covariance"]
-    return r
+    return (r, {k: rows[:nq, i].copy() for i, k in enumerate(TRACE_FIELDS)}) if trace else r

@@ -1,7 +1,10 @@
 """Rig absolute pose without a GPU: the pycolmap surface (names, defaults, the reference's shifted keyword names, every
 THROW_CHECK error, N = 0, the out-of-scope options), the C header, and the CPU reference (tests/rigpose_ref) against its
 frozen fixture, an independent numpy restatement of the generalised P3P, hand-built unique-inlier supports, central
-differences and numpy's covariance."""
+differences and numpy's covariance; and the edge cases of rigpose_cases.edge_cases(): that each
+is of the kind its name says, by the reference's own results and refinement trace, and that the reference still gives
+what tests/golden/rigpose_ref_edges_v1.npz holds."""
+import math
 from pathlib import Path
 
 import numpy as np
@@ -331,3 +334,273 @@ def test_covariance_matches_numpy_on_a_small_problem():
     cond = np.linalg.cond(J.T @ J)
     assert np.abs(got - want).max() <= 100 * cond * np.finfo(np.float64).eps * np.abs(want).max()
     assert np.all(np.linalg.eigvalsh(got) > 0)
+
+
+# ---- the edge cases: what rigpose_cases.cases() leaves out --------------------------------------------
+GOLDEN_EDGES = ROOT / "tests" / "golden" / "rigpose_ref_edges_v1.npz"
+EDGES = rigpose_cases.EDGE_CASES
+
+
+def maker():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("mk_rig", ROOT / "tests" / "golden" / "make_rigpose_ref_golden.py")
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    return mk
+
+
+@pytest.fixture(scope="module")
+def golden_edges():
+    return maker().load_edges()
+
+
+@pytest.fixture(scope="module")
+def solved_edges():
+    """the reference on every edge case, once: name -> (result, trace rows)"""
+    mk = maker()
+    return {name: mk.edge_reference(name) for name in EDGES}
+
+
+def test_edge_fixture_lists_the_edge_cases(golden_edges):
+    assert sorted(golden_edges) == sorted(EDGES)
+    assert GOLDEN_EDGES.stat().st_size < 20_000
+
+
+@pytest.mark.parametrize("name", sorted(EDGES))
+def test_reference_equals_its_edge_fixture_bit_for_bit(name, golden_edges, solved_edges):
+    r, tr = solved_edges[name]
+    want_digest, want_trace = golden_edges[name]
+    assert rigpose_cases.digest(r) == want_digest
+    assert np.array_equal(tr, want_trace)
+
+
+def test_trace_records_and_does_not_compute(solved_edges):
+    for name in ("refine_tight_noisy", "refine_min_radius", "refine_rank_two_points", "stream_batch", "nan_rig"):
+        sc, est, rf, cov = EDGES[name]
+        plain = ref.estimate(*rigpose_cases.args(sc), est, rf, cov)
+        assert rigpose_cases.digest(plain) == rigpose_cases.digest(solved_edges[name][0]), name
+
+
+def numpy_point_ids(X):
+    """13.2's rule, stated plainly: the id of a correspondence is the index of the first correspondence whose three
+    points3D doubles compare == to its own (itself where none before it does)."""
+    ids = np.arange(len(X))
+    for k in range(len(X)):
+        for j in range(k):
+            if X[j, 0] == X[k, 0] and X[j, 1] == X[k, 1] and X[j, 2] == X[k, 2]:
+                ids[k] = j
+                break
+    return ids
+
+
+def test_point_ids_are_the_first_equal_match(solved_edges):
+    for name in ("signed_zero", "nan_twins", "chain3_first_out", "chain3_middle_out", "coincident_samples"):
+        X = EDGES[name][0]["points3D"]
+        ids = numpy_point_ids(X)
+        assert np.array_equal(ref.point_ids(X), ids), name
+        r = solved_edges[name][0]
+        assert r["num_inliers"][0] == len(set(ids[r["inlier_mask"]])) and r["num_all_inliers"][0] == r["inlier_mask"].sum()
+    X = EDGES["signed_zero"][0]["points3D"]
+    assert np.signbit(X[[0, 30, 31], 0]).tolist() == [False, True, False] and not X[[0, 30, 31], 0].any()
+    assert numpy_point_ids(X)[[30, 31]].tolist() == [0, 0]
+    X = EDGES["nan_twins"][0]["points3D"]
+    assert np.array_equal(X[0].view(np.uint64), X[30].view(np.uint64)) and np.isnan(X[0, 2])
+    assert numpy_point_ids(X)[[0, 30, 31]].tolist() == [0, 30, 31]
+    assert numpy_point_ids(EDGES["chain3_first_out"][0]["points3D"])[[30, 31]].tolist() == [0, 0]
+
+
+def test_edge_cases_reach_their_paths(solved_edges):
+    """by the reference's own results and trace and the cases' own shapes, so that the list cannot decay"""
+    res = {n: solved_edges[n][0] for n in EDGES}
+    trace = {n: dict(zip(ref.TRACE_FIELDS, solved_edges[n][1].T)) for n in EDGES}
+    exits = lambda n: [ref.EXITS[e] for e in trace[n]["exit"]]  # noqa: E731
+    sizes = lambda n: np.diff(EDGES[n][0]["offsets"].astype(np.int64)).tolist()  # noqa: E731
+    ncams = lambda n: np.diff(EDGES[n][0]["camera_offsets"].astype(np.int64)).tolist()  # noqa: E731
+    trials = lambda n: res[n]["num_trials"].tolist()  # noqa: E731
+    for n in EDGES:
+        assert max(sizes(n)) <= 200, n
+
+    # the end of the sample stream: a trial takes three words, so trials 0 .. 2340 have words; a query whose walk ends
+    # on trial t reports t + 2 trials; the default round of 64 that holds trial 2341 is 2304 .. 2367
+    assert rigpose_cases.FIRST_STREAM_WORDS == 7024 and rigpose_cases.LAST_TRIAL_WITH_WORDS == 2340
+    last = rigpose_cases.LAST_TRIAL_WITH_WORDS
+    first_of_round, last_of_round = 64 * (last // 64), 64 * (last // 64) + 63
+    assert (first_of_round, last_of_round) == (2304, 2367)
+    for name, (seed, n, k) in rigpose_cases.STREAM_WINDOWS.items():
+        sc, est, rf, cov = EDGES[name]
+        assert est == rigpose_cases.OVERRUN == dict(min_num_trials=20, max_num_trials=100000) and rf == {}
+        assert sizes(name) == [n] and ncams(name) == [2] and int((~sc["outlier"]).sum()) == k
+        assert res[name]["success"].all() and res[name]["num_all_inliers"].tolist() == [k]
+        assert np.array_equal(res[name]["inlier_mask"], ~sc["outlier"])
+    for name in ("stream_before_end", "stream_near_end"):  # no rerun: the walk never reaches a trial without words
+        assert first_of_round + 2 <= trials(name)[0] <= last + 2, name
+    assert trials("stream_last_trial") == [last + 2]
+    assert trials("stream_first_without") == [last + 3]
+    assert last + 3 <= trials("stream_same_round")[0] <= last_of_round + 2
+    assert trials("stream_next_round")[0] > last_of_round + 2
+    order = sorted(rigpose_cases.STREAM_WINDOWS)
+    assert sizes("stream_batch")[1::2] == [0, 2, 3, 40, 64, 65] and EDGES["stream_batch"][1] == rigpose_cases.OVERRUN
+    assert trials("stream_batch")[0::2] == [trials(n)[0] for n in order]
+    assert max(trials("stream_batch")[1::2]) < 64
+    assert res["stream_batch"]["success"].tolist() == [True, False, True, False] + [True] * 8
+    # a table that doubles twice: 7,024 -> 14,048 -> 28,096 words for 5,000 trials of three words
+    sc, est, _, _ = EDGES["double_twice"]
+    assert est == dict(min_num_trials=20, max_num_trials=5000) and sizes("double_twice") == [36] and sc["outlier"].all()
+    assert trials("double_twice") == [5000] and 2 * rigpose_cases.FIRST_STREAM_WORDS < 3 * 5000 <= 4 * 7024
+    assert res["double_twice"]["num_all_inliers"][0] <= 5
+
+    # RANSAC control
+    assert EDGES["trials_equal"][1] == dict(min_num_trials=50, max_num_trials=50)
+    assert trials("trials_equal") == [50] and res["trials_equal"]["success"].all()
+    # no trial: the loop's counter is never advanced, so num_trials is 0, and nothing is found
+    assert EDGES["zero_trials"][1]["max_num_trials"] == 0 and trials("zero_trials") == [0]
+    assert not res["zero_trials"]["success"].any() and not res["zero_trials"]["inlier_mask"].any()
+    assert EDGES["one_trial"][1]["max_num_trials"] == 1 and trials("one_trial") == [1] and res["one_trial"]["success"].all()
+    est = EDGES["ratio_clamp"][1]
+    eo, _ = _capi.rigpose_options(est, None)
+    clamp = math.ceil(math.log(1.0 - eo.confidence) / math.log(1.0 - est["min_inlier_ratio"] ** 3)
+                      * eo.dyn_num_trials_multiplier)
+    assert est["min_inlier_ratio"] == 0.5 and abs(EDGES["ratio_clamp"][0]["outlier"].mean() - 0.6) < 0.1
+    assert trials("ratio_clamp") == [clamp] and clamp < est["max_num_trials"] and res["ratio_clamp"]["success"].all()
+    # confidence 0: ComputeNumTrials is 0 for every inlier count, so the constructor's clamp leaves no trial at all;
+    # confidence 1: it is the largest count, so nothing stops a run before max_num_trials
+    assert EDGES["confidence0"][1]["confidence"] == 0.0 and EDGES["confidence1"][1]["confidence"] == 1.0
+    assert trials("confidence0") == [0] and not res["confidence0"]["success"].any()
+    assert trials("confidence1") == [rigpose_cases.FAST["max_num_trials"]] and res["confidence1"]["success"].all()
+
+    # degenerate geometry
+    sc = EDGES["zero_baseline"][0]
+    assert ncams("zero_baseline") == [3] and not sc["cams_from_rig"][:, 4:].any() and res["zero_baseline"]["success"].all()
+    assert len(set(sc["camera_idxs"].tolist())) == 3
+    sc = EDGES["coincident_samples"][0]
+    assert sizes("coincident_samples") == [12] and len({tuple(x) for x in sc["points3D"]}) == 5
+    r = res["coincident_samples"]
+    assert r["success"].all() and (r["num_inliers"][0], r["num_all_inliers"][0]) == (5, 12)
+    X = EDGES["collinear"][0]["points3D"]
+    assert sizes("collinear") == [40] and np.linalg.matrix_rank(X - X.mean(axis=0), tol=1e-9) == 1
+    assert not res["collinear"]["success"].any() and trials("collinear") == [rigpose_cases.FAST["max_num_trials"]]
+    assert exits("collinear") == ["NOT_REFINED"] and not res["collinear"]["inlier_mask"].any()
+    for name, key in (("nan_pixel", "points2D"), ("nan_point", "points3D")):
+        bad = np.isnan(EDGES[name][0][key]).any(axis=1)
+        assert bad.sum() == 1 and not EDGES[name][0]["outlier"][bad].any()
+        assert res[name]["success"].all() and not res[name]["inlier_mask"][bad].any(), name
+        assert res[name]["inlier_mask"].sum() >= 0.7 * len(bad)
+    sc = EDGES["nan_rig"][0]
+    bad = np.isnan(sc["cams_from_rig"]).any(axis=1)
+    assert bad.tolist() == [False, True, False] and ncams("nan_rig") == [3]
+    of_bad = sc["camera_idxs"] == 1
+    assert of_bad.sum() >= 10 and res["nan_rig"]["success"].all() and not res["nan_rig"]["inlier_mask"][of_bad].any()
+    assert res["nan_rig"]["inlier_mask"][~of_bad & ~sc["outlier"]].all()
+    r = res["signed_zero"]
+    assert sizes("signed_zero") == [32] and r["success"].all() and r["inlier_mask"].all()
+    assert (r["num_inliers"][0], r["num_all_inliers"][0]) == (30, 32)
+    r = res["nan_twins"]
+    assert r["success"].all() and (r["num_inliers"][0], r["num_all_inliers"][0]) == (30, 30)
+    assert r["inlier_mask"].tolist() == [False] + [True] * 29 + [False, True]
+    r = res["chain3_first_out"]
+    assert r["success"].all() and (r["num_inliers"][0], r["num_all_inliers"][0]) == (30, 31)
+    assert r["inlier_mask"].tolist() == [False] + [True] * 31
+    assert len(set(EDGES["chain3_first_out"][0]["camera_idxs"][[0, 30, 31]].tolist())) == 3
+    r = res["chain3_middle_out"]
+    assert r["success"].all() and (r["num_inliers"][0], r["num_all_inliers"][0]) == (30, 31)
+    assert r["inlier_mask"].tolist() == [True] * 30 + [False, True]
+    for k in (64, 65):
+        sc = EDGES[f"inliers{k}"][0]
+        assert sizes(f"inliers{k}") == [100] and int(sc["outlier"].sum()) == 100 - k
+        assert res[f"inliers{k}"]["num_all_inliers"].tolist() == [k] and res[f"inliers{k}"]["success"].all()
+        assert np.array_equal(res[f"inliers{k}"]["inlier_mask"], ~sc["outlier"])
+    sc = EDGES["unused_camera"][0]
+    assert ncams("unused_camera") == [3] and set(sc["camera_idxs"].tolist()) == {0, 2}
+    assert res["unused_camera"]["success"].all()
+    assert sizes("empty_between") == [50, 0, 70] and ncams("empty_between") == [2, 2, 3]
+    assert res["empty_between"]["success"].tolist() == [True, False, True] and trials("empty_between")[1] == 0
+
+    # refinement through the rig entry
+    bits = lambda n: np.concatenate([res[n]["qvec"], res[n]["tvec"]], axis=1).view(np.uint64)  # noqa: E731
+    near = EDGES["refine_iterations0"][0]
+    for n in ("refine_gradient_huge", "refine_tight_noisy", "refine_scale_tiny", "refine_scale_huge",
+              "refine_scale_subnormal", "refine_scale_zero"):
+        assert EDGES[n][0] is near and EDGES[n][1] == rigpose_cases.FAST, n
+    assert EDGES["refine_iterations0"][2] == dict(gradient_tolerance=0.0, max_num_iterations=0)
+    assert exits("refine_iterations0") == ["MAX_ITERATIONS"] and trace["refine_iterations0"]["iterations"].tolist() == [0]
+    assert EDGES["refine_gradient_huge"][2] == dict(gradient_tolerance=1e10)
+    assert exits("refine_gradient_huge") == ["GRADIENT_AT_START"]
+    assert EDGES["refine_scale_huge"][2] == dict(gradient_tolerance=0.0, loss_function_scale=1e60)
+    assert exits("refine_scale_huge") == ["FUNCTION_TOLERANCE"] and trace["refine_scale_huge"]["accepted"].tolist() == [0]
+    # these three leave the RANSAC pose as it is; gradient_tolerance = 0 alone moves it
+    assert np.array_equal(bits("refine_iterations0"), bits("refine_gradient_huge"))
+    assert np.array_equal(bits("refine_iterations0"), bits("refine_scale_huge"))
+    assert EDGES["refine_tight_noisy"][2] == dict(gradient_tolerance=0.0)
+    assert exits("refine_tight_noisy") == ["FUNCTION_TOLERANCE"] and trace["refine_tight_noisy"]["accepted"][0] > 0
+    assert not np.array_equal(bits("refine_iterations0"), bits("refine_tight_noisy"))
+    assert not EDGES["refine_tight_exact"][0]["outlier"].any() and EDGES["refine_tight_exact"][2] == dict(gradient_tolerance=0.0)
+    assert exits("refine_tight_exact") == ["PARAMETER_TOLERANCE"]
+    # a loss of scale 1e-120 leaves a gradient that underflows against the start's translation: the gradient test stops
+    # the run before the loop although the tolerance is zero
+    assert EDGES["refine_scale_tiny"][2] == dict(gradient_tolerance=0.0, loss_function_scale=1e-120)
+    assert exits("refine_scale_tiny") == ["GRADIENT_AT_START"] and res["refine_scale_tiny"]["success"].all()
+    assert np.abs(res["refine_scale_tiny"]["covariance"]).max() > 1e200
+    assert np.isfinite(res["refine_scale_tiny"]["covariance"]).all()
+    r = res["refine_three_inliers"]
+    assert EDGES["refine_three_inliers"][3] and r["success"].all() and r["num_all_inliers"].tolist() == [3]
+    assert trace["refine_three_inliers"]["rank_failed"].tolist() == [0] and np.abs(r["covariance"]).max() > 0
+    assert exits("refine_min_radius") == ["MIN_RADIUS"] and trace["refine_min_radius"]["rejected"].tolist() == [15]
+    assert trace["refine_min_radius"]["accepted"].tolist() == [0] and res["refine_min_radius"]["success"].all()
+    assert res["refine_min_radius"]["inlier_mask"].all() and EDGES["refine_min_radius"][0]["points2D"][0, 0] > 1e39
+    # the RANSAC succeeds and the refinement fails: success is false while num_inliers and the mask are set
+    r = res["refine_rank_two_points"]
+    assert sizes("refine_rank_two_points") == [3] and EDGES["refine_rank_two_points"][3]
+    assert len({tuple(x) for x in EDGES["refine_rank_two_points"][0]["points3D"]}) == 2
+    assert trace["refine_rank_two_points"]["rank_failed"].tolist() == [1] and not r["success"].any()
+    assert (r["num_inliers"][0], r["num_all_inliers"][0]) == (2, 3) and r["inlier_mask"].all() and not r["covariance"].any()
+    sc, est, rf, cov = EDGES["refine_invalid_steps"]
+    assert [p[0] for p in sc["camera_params"]] == [1e154, 1e154] and est == dict(rigpose_cases.FAST, max_error=1.2e152)
+    assert rf == dict(gradient_tolerance=0.0) and cov and sizes("refine_invalid_steps") == [100]
+    r = res["refine_invalid_steps"]
+    assert exits("refine_invalid_steps") == ["INVALID_STEPS"] and not r["success"].any()
+    assert trace["refine_invalid_steps"]["invalid"].tolist() == [5] == trace["refine_invalid_steps"]["iterations"].tolist()
+    assert trace["refine_invalid_steps"]["accepted"].tolist() == [0] == trace["refine_invalid_steps"]["rejected"].tolist()
+    assert (r["num_inliers"][0], r["num_all_inliers"][0]) == (100, 100) and r["inlier_mask"].all()
+    assert np.isfinite(r["qvec"]).all() and r["qvec"].any() and not r["covariance"].any()
+    for n in ("refine_scale_subnormal", "refine_scale_zero"):
+        scale = EDGES[n][2]["loss_function_scale"]
+        assert scale * scale < np.finfo(np.float64).tiny and math.isinf(1.0 / (scale * scale)) if scale else scale == 0.0
+        assert exits(n) == ["NOT_FINITE_START"] and not res[n]["success"].any(), n
+        assert res[n]["num_inliers"][0] == res[n]["inlier_mask"].sum() == res["refine_iterations0"]["num_inliers"][0] > 3
+        assert np.array_equal(bits(n), bits("refine_iterations0"))
+    assert EDGES["refine_scale_subnormal"][3] and not res["refine_scale_subnormal"]["covariance"].any()
+    # the gradient test after an accepted step, under the default tolerance: the no-consensus query's few inliers
+    assert EDGES["double_twice"][2] == {} and exits("double_twice") == ["GRADIENT_AFTER_STEP"]
+    assert trace["double_twice"]["accepted"][0] > 0 and res["double_twice"]["success"].all()
+    # every exit but the one no input to this entry reaches (DESIGN.md 13.11)
+    reached = {e for n in trace for e in exits(n)}
+    assert reached == set(ref.EXITS) - {"NOTHING_TO_REFINE"}, sorted(reached)
+
+
+def test_bulk_batches_have_the_shapes_the_gpu_tests_need():
+    sc, est, where = rigpose_cases.reuse_batch()
+    n = np.diff(sc["offsets"].astype(np.int64))
+    ncam = np.diff(sc["camera_offsets"].astype(np.int64))
+    small = np.zeros(len(n), bool)
+    small[where] = True
+    assert len(n) == 2048 + 64 and (n[~small] == 40).all() and (n[small] < 40).all() and est == rigpose_cases.NO_CONSENSUS
+    # the size order of rigpose.hip (a stable sort, largest first): the 64 small queries are entries 2048 .. 2111, the
+    # second queries of blocks 0 .. 63
+    order = np.argsort(-n, kind="stable")
+    assert sorted(order[2048:].tolist()) == sorted(where)
+    off = sc["offsets"].astype(np.int64)
+    repeats = np.array([len({tuple(x) for x in sc["points3D"][off[i]:off[i + 1]]}) < n[i] for i in range(len(n))])
+    assert repeats[~small][::2].all() and not repeats[~small][1::2].any()
+    tail = order[2048:]
+    assert sorted(n[tail].tolist())[:3] == [0, 2, 3] and 36 in n[tail]
+    assert any(repeats[a] != repeats[b] for a, b in zip(tail[:-1], tail[1:]))
+    assert any({ncam[a], ncam[b]} == {1, 3} for a, b in zip(tail[:-1], tail[1:]))
+    sc, est = rigpose_cases.query_count_batch()
+    n = np.diff(sc["offsets"].astype(np.int64))
+    assert len(n) == (1 << 16) + 1 and n[0] == n[-1] == 141 and (n[1:-1] == 4).all() and est == rigpose_cases.OVERRUN
+    # tiny_rig_queries' own geometry: the true pose reprojects every point onto its pixel
+    tiny = rigpose_cases.tiny_rig_queries(3, 50, 7)
+    r = ref.estimate(*rigpose_cases.args(tiny), rigpose_cases.FAST)
+    assert r["success"].all() and r["inlier_mask"].all()
+    assert np.abs(np.abs((r["qvec"] * tiny["qvec"]).sum(axis=1)) - 1.0).max() < 1e-9
+    assert np.abs(r["tvec"] - tiny["tvec"]).max() < 1e-6

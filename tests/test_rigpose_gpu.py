@@ -2,8 +2,11 @@
 against its CPU reference (tests/rigpose_ref) and the frozen fixture: success, pose bits, both inlier counts, trial
 counts, masks and covariance bits identical over the lane boundaries, one to five cameras of all eleven models,
 duplicated 3D points, outliers, aborts inside and after the first round of trials, a trial limit below a round, a
-sample-stream overrun, any round size, and batches in any order or split."""
+sample-stream overrun, any round size, and batches in any order or split; and the edge cases of
+rigpose_cases.edge_cases(), a batch in which 64 blocks take a second query, a batch split on the query count and an
+empty batch."""
 import os
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -131,3 +134,105 @@ def test_pycolmap_binding_equals_context(amc_ctx):
     two = CASES["n2"][0]
     assert pycolmap.rig_absolute_pose_estimation(two["points2D"], two["points3D"], two["camera_idxs"], rigs[:2],
                                                  cams[:2]) is None
+
+
+# ---- the edge cases -----------------------------------------------------------------------------------
+EDGES = rigpose_cases.EDGE_CASES
+MAKER = Path(__file__).resolve().parent / "golden" / "make_rigpose_ref_golden.py"  # (it reads the edge fixture)
+FAST_BATCH = sorted(n for n in EDGES if EDGES[n][1] == rigpose_cases.FAST and EDGES[n][2] == {})
+STREAM = sorted(rigpose_cases.STREAM_WINDOWS) + ["stream_batch"]
+
+
+@pytest.fixture(scope="module")
+def golden_edges():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("mk_rig", MAKER)
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    return mk.load_edges()
+
+
+def queries(res, sc, q0, q1):
+    """the queries q0 .. q1 - 1 of a batch's result as a result of their own"""
+    off = sc["offsets"].astype(np.int64)
+    part = {k: res[k][q0:q1] for k in FIELDS if k in res and k != "inlier_mask"}
+    part["inlier_mask"] = res["inlier_mask"][off[q0]:off[q1]]
+    return part
+
+
+@pytest.mark.parametrize("name", sorted(EDGES))
+def test_edge_case_bit_exact_to_reference_and_fixture(amc_ctx, golden_edges, name):
+    sc, est, rf, cov = EDGES[name]
+    got = gpu(amc_ctx, sc, est, rf, cov)
+    assert_same(got, cpu(sc, est, rf, cov), name)
+    assert rigpose_cases.digest(got) == golden_edges[name][0]
+    assert got["num_batches"] == 1
+
+
+@pytest.mark.parametrize("round_size", ["1", "37"])
+def test_stream_windows_do_not_depend_on_the_round_size(amc_ctx, golden_edges, monkeypatch, round_size):
+    # a round of 1 never holds a trial without words; under 37, round 63 is trials 2331 .. 2367, so the table's end at
+    # trial 2341 falls at lane 10 instead of lane 37
+    monkeypatch.setenv("AMC_RIGPOSE_ROUND", round_size)
+    for name in STREAM:
+        sc, est, rf, cov = EDGES[name]
+        assert rigpose_cases.digest(gpu(amc_ctx, sc, est, rf, cov)) == golden_edges[name][0], name
+
+
+def test_blocks_that_take_a_second_query(amc_ctx):
+    sc, est, where = rigpose_cases.reuse_batch()
+    got = gpu(amc_ctx, sc, est, None, True)
+    want = cpu(sc, est, None, True)
+    assert got["num_batches"] == 1 and len(want["success"]) == 2048 + 64
+    n = np.diff(sc["offsets"].astype(np.int64))
+    overrun = 3 * want["num_trials"].astype(np.int64) > rigpose_cases.FIRST_STREAM_WORDS
+    assert overrun.sum() == 1 and n[overrun].tolist() == [36] and want["num_trials"][overrun].tolist() == [5000]
+    assert_same(got, want, "2,048 + 64 queries")
+    for i in where:
+        one = gpu(amc_ctx, rigpose_cases.subset(sc, [i]), est, None, True)
+        assert_same(queries(got, sc, i, i + 1), {k: one[k] for k in FIELDS}, f"query {i} alone")
+
+
+def test_split_on_query_count(amc_ctx):
+    # 2^16 queries fill one device batch: the first, whose RANSAC outruns the first sample stream, doubles the table, and
+    # the 65,537th, the same query, is a batch of its own that starts on the doubled table
+    sc, est = rigpose_cases.query_count_batch()
+    got = gpu(amc_ctx, sc, est)
+    assert got["num_batches"] >= 2
+    want = cpu(sc, est)
+    words = 3 * want["num_trials"].astype(np.int64)
+    assert words[0] == words[-1] > rigpose_cases.FIRST_STREAM_WORDS >= words[1:-1].max()
+    assert want["success"].all()
+    assert_same(got, want, "65,537 queries")
+    last = len(want["success"]) - 1
+    one = gpu(amc_ctx, rigpose_cases.subset(sc, [last]), est)
+    assert one["num_batches"] == 1
+    assert_same(queries(got, sc, last, last + 1), {k: one[k] for k in FIELDS if k in one}, "the last query alone")
+
+
+def test_edge_cases_as_one_batch_in_any_order(amc_ctx):
+    assert len(FAST_BATCH) >= 8
+    scenes = [EDGES[n][0] for n in FAST_BATCH]
+    each = [gpu(amc_ctx, sc, rigpose_cases.FAST, None, True) for sc in scenes]
+    for order in (np.arange(len(FAST_BATCH)), np.random.default_rng(2).permutation(len(FAST_BATCH))):
+        sc = rigpose_cases.concat(*[scenes[i] for i in order])
+        whole = gpu(amc_ctx, sc, rigpose_cases.FAST, None, True)
+        ends = np.cumsum([len(each[i]["success"]) for i in order])
+        for j, i in enumerate(order):
+            assert_same(queries(whole, sc, ends[j] - len(each[i]["success"]), ends[j]), {k: each[i][k] for k in FIELDS},
+                        f"{FAST_BATCH[i]} at {j}")
+
+
+def test_no_queries(amc_ctx):
+    none = (np.zeros(1, np.uint64), np.zeros(1, np.uint64), np.zeros(0, np.int32), [], np.zeros((0, 7)),
+            np.zeros(0, np.int32), np.zeros((0, 2)), np.zeros((0, 3)))
+    for cov in (False, True):
+        got = amc_ctx.estimate_rig_absolute_poses(*none, None, None, cov)
+        assert got["num_batches"] == 0
+        for k in FIELDS:
+            if k == "covariance" and not cov:
+                assert k not in got
+            else:
+                assert len(got[k]) == 0, k
+        assert got["qvec"].shape == (0, 4) and got["tvec"].shape == (0, 3)
+        assert not cov or got["covariance"].shape == (0, 6, 6)

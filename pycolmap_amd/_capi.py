@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "amc_estimate_rig_absolute_poses", "amc_rigpose_result_free",
     "amc_undistort_opts_default", "amc_undistort_camera", "amc_undistort_points", "amc_undistort_images",
     "amc_ba_opts_default", "amc_bundle_adjust",
+    "amc_filter_opts_default", "amc_filter_points3d", "amc_filter_result_free",
 ]
 COMM_ID_BYTES = 128
 RANSAC_F, RANSAC_H, RANSAC_E = 0, 1, 2
@@ -286,6 +287,68 @@ def ba_inputs(camera_models, camera_params, camera_const, image_cameras, qvec, t
         if a.size and (a.min() < 0 or a.max() > 0xffffffff):
             raise ValueError(f"bundle adjustment: {name} has an index outside 0 .. 2^32 - 1")
     return (models, prm, cc, icam.astype(np.uint32), q, t, pc, X, oi.astype(np.uint32), op.astype(np.uint32), xy)
+
+
+class FilterOpts(C.Structure):  # amc_filter_opts (include/amc_filter.h)
+    _fields_ = [("max_reproj_error", C.c_double), ("min_tri_angle", C.c_double), ("errors_only", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class FilterProblem(C.Structure):  # amc_filter_problem
+    _fields_ = [("num_cameras", C.c_size_t), ("camera_models", C.c_void_p), ("camera_params", C.c_void_p),
+                ("num_images", C.c_size_t), ("image_cameras", C.c_void_p), ("qvec", C.c_void_p), ("tvec", C.c_void_p),
+                ("num_points", C.c_size_t), ("xyz", C.c_void_p), ("track_offsets", C.c_void_p),
+                ("obs_image", C.c_void_p), ("obs_xy", C.c_void_p), ("selected", C.c_void_p)]
+
+
+class FilterResult(C.Structure):  # amc_filter_result
+    _fields_ = [("num_points", C.c_uint64), ("num_observations", C.c_uint64), ("num_filtered", C.c_uint64),
+                ("obs_sq_error", C.POINTER(C.c_double)), ("obs_deleted", C.POINTER(C.c_uint8)),
+                ("point_verdict", C.POINTER(C.c_uint8)), ("point_error", C.POINTER(C.c_double)),
+                ("num_batches", C.c_uint32), ("reserved", C.c_uint32), ("host_ms", C.c_double),
+                ("device_ms", C.c_double), ("kernel_ms", C.c_double), ("copy_ms", C.c_double),
+                ("alloc_ms", C.c_double)]
+
+
+FILTER_VERDICTS = ("KEPT", "NOT_SELECTED", "SHORT_TRACK", "REPROJECTION", "ANGLE")
+
+
+def filter_inputs(camera_models, camera_params, image_cameras, qvec, tvec, xyz, track_offsets, obs_image, obs_xy,
+                  selected=None):
+    """The flat problem of amc_filter_points3d as contiguous arrays (copies: the caller's arrays are not touched):
+    models (C,) int32, params (C, 12), image_cameras (I,) uint32, qvec (I, 4) x y z w, tvec (I, 3), xyz (P, 3),
+    track_offsets (P + 1,) uint64, obs_image (N,) uint32, obs_xy (N, 2), selected (P,) uint8 or None."""
+    models = np.array(camera_models, dtype=np.int32).reshape(-1)
+    if len(camera_params) != models.size:
+        raise ValueError(f"filter_points3d: {models.size} camera models, {len(camera_params)} parameter sets")
+    prm = np.zeros((models.size, 12), np.float64)
+    for i, p in enumerate(camera_params):
+        p = np.asarray(p, dtype=np.float64).reshape(-1)
+        if p.size > 12:
+            raise ValueError(f"filter_points3d: camera {i} has {p.size} parameters (at most 12)")
+        prm[i, :p.size] = p
+    icam = np.array(image_cameras, dtype=np.int64).reshape(-1)
+    q = np.array(qvec, dtype=np.float64).reshape(-1, 4)
+    t = np.array(tvec, dtype=np.float64).reshape(-1, 3)
+    X = np.array(xyz, dtype=np.float64).reshape(-1, 3)
+    off = np.array(track_offsets, dtype=np.int64).reshape(-1)
+    oi = np.array(obs_image, dtype=np.int64).reshape(-1)
+    xy = np.array(obs_xy, dtype=np.float64).reshape(-1, 2)
+    if q.shape[0] != icam.size or t.shape[0] != icam.size or off.size != X.shape[0] + 1 or xy.shape[0] != oi.size:
+        raise ValueError(f"filter_points3d: {icam.size} images by image_cameras, {q.shape[0]} rotations, {t.shape[0]} "
+                         f"translations; {X.shape[0]} points, {off.size} offsets; {oi.size} observations by obs_image, "
+                         f"{xy.shape[0]} pixels")
+    if off.min() < 0 or int(off[-1]) != oi.size:
+        raise ValueError(f"filter_points3d: track_offsets ends at {int(off[-1])}, {oi.size} observations")
+    for name, a in (("image_cameras", icam), ("obs_image", oi)):
+        if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+            raise ValueError(f"filter_points3d: {name} has an index outside 0 .. 2^32 - 1")
+    sel = None
+    if selected is not None:
+        sel = np.ascontiguousarray(np.asarray(selected).reshape(-1) != 0, dtype=np.uint8)
+        if sel.size != X.shape[0]:
+            raise ValueError(f"filter_points3d: {X.shape[0]} points, {sel.size} selection flags")
+    return models, prm, icam.astype(np.uint32), q, t, X, off.astype(np.uint64), oi.astype(np.uint32), xy, sel
 
 
 class RigPoseResult(C.Structure):  # amc_rigpose_result (include/amc_rigpose.h)
@@ -561,6 +624,14 @@ def load() -> C.CDLL:
         lib.amc_ba_opts_default.restype = None
         lib.amc_bundle_adjust.argtypes = [C.c_void_p, C.POINTER(BaProblem), C.POINTER(BaOpts), C.POINTER(BaResult)]
         lib.amc_bundle_adjust.restype = C.c_int
+    if hasattr(lib, "amc_filter_points3d"):  # (absent from a library built from an older revision)
+        lib.amc_filter_opts_default.argtypes = [C.POINTER(FilterOpts)]
+        lib.amc_filter_opts_default.restype = None
+        lib.amc_filter_points3d.argtypes = [C.c_void_p, C.POINTER(FilterProblem), C.POINTER(FilterOpts),
+                                            C.POINTER(FilterResult)]
+        lib.amc_filter_points3d.restype = C.c_int
+        lib.amc_filter_result_free.argtypes = [C.POINTER(FilterResult)]
+        lib.amc_filter_result_free.restype = None
     if hasattr(lib, "amc_triangulate_tracks"):  # (absent from a library built from an older revision)
         lib.amc_tri_opts_default.argtypes = [C.POINTER(TriOpts)]
         lib.amc_tri_opts_default.restype = None
@@ -997,6 +1068,36 @@ class Context:
         out = {k: getattr(res, k) for k, _ in BaResult._fields_}
         out["termination"] = BA_TERMINATIONS[res.termination]
         out.update(camera_params=prm, qvec=q, tvec=t, xyz=X)
+        return out
+
+    def filter_points3d(self, camera_models, camera_params, image_cameras, qvec, tvec, xyz, track_offsets, obs_image,
+                        obs_xy, selected=None, max_reproj_error=4.0, min_tri_angle=1.5, errors_only=False):
+        """amc_filter_points3d: COLMAP's FilterPoints3D on a flat model.  camera_models (C,),
+        camera_params: C parameter vectors; image_cameras (I,), qvec (I, 4) x y z w, tvec (I, 3); xyz (P, 3);
+        track_offsets (P + 1,) CSR over the observations in track order, obs_image (N,), obs_xy (N, 2) pixels;
+        selected (P,) non-zero = the point is filtered, None = every point.  errors_only: no thresholds and no
+        verdicts, point_error is the mean over the whole track.  The inputs are not modified.  Returns a dict:
+        obs_sq_error (N,), obs_deleted (N,) bool, point_verdict (P,) uint8 (FILTER_VERDICTS), point_error (P,),
+        num_filtered, num_batches, host_ms, device_ms, kernel_ms, copy_ms, alloc_ms."""
+        models, prm, icam, q, t, X, off, oi, xy, sel = filter_inputs(camera_models, camera_params, image_cameras, qvec,
+                                                                     tvec, xyz, track_offsets, obs_image, obs_xy,
+                                                                     selected)
+        o = FilterOpts(float(max_reproj_error), float(min_tri_angle), int(bool(errors_only)), 0)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        pb = FilterProblem(models.size, ptr(models), ptr(prm), icam.size, ptr(icam), ptr(q), ptr(t), X.shape[0], ptr(X),
+                           ptr(off), ptr(oi), ptr(xy), None if sel is None else ptr(sel))
+        res = FilterResult()
+        _check(self._lib.amc_filter_points3d(self._h, C.byref(pb), C.byref(o), C.byref(res)))
+        try:
+            n, npts = oi.size, X.shape[0]
+            a = lambda p, k: np.ctypeslib.as_array(p, (max(k, 1),))[:k].copy()  # noqa: E731
+            out = {"obs_sq_error": a(res.obs_sq_error, n), "obs_deleted": a(res.obs_deleted, n).astype(bool),
+                   "point_verdict": a(res.point_verdict, npts), "point_error": a(res.point_error, npts),
+                   "num_filtered": int(res.num_filtered), "num_batches": int(res.num_batches),
+                   "host_ms": res.host_ms, "device_ms": res.device_ms, "kernel_ms": res.kernel_ms,
+                   "copy_ms": res.copy_ms, "alloc_ms": res.alloc_ms}
+        finally:
+            self._lib.amc_filter_result_free(C.byref(res))
         return out
 
     def estimate_rig_absolute_poses(self, offsets, camera_offsets, camera_models, camera_params, cams_from_rig,

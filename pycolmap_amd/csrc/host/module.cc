@@ -30,6 +30,7 @@
 #include <fstream>
 #include <sstream>
 #include <thread>
+#include <unordered_set>
 
 #include "controller.h"
 #include "py_types.h"
@@ -1089,6 +1090,86 @@ PYBIND11_MODULE(_pycolmap, m) {
         if (!bad.empty()) throw py::value_error("Reconstruction: " + bad);
         return m;
     };
+    // update_from_model plus the points' errors (the point filter and update_point3D_errors write them; bundle_adjustment
+    // does not)
+    auto update_with_errors = [update_from_model](PyReconstruction& r, const SparseModel& m) {
+        update_from_model(r, m);
+        for (const ModelPoint3D& mp : m.points3D) r.points3D[py::int_(mp.point3D_id)].cast<PyPoint3D&>().error = mp.error;
+    };
+    // One amc_filter_points3d call on the checked model: ids == nullptr filters every point.  Nothing
+    // of r changes unless the call succeeds.  Without a device the call raises pycolmap_amd._capi.AmcError.
+    auto filter_model = [checked_model, update_with_errors](PyReconstruction& r, const std::vector<uint64_t>* ids, const std::vector<uint32_t>* image_ids,
+                                                            double max_reproj_error, double min_tri_angle, bool errors_only) -> size_t {
+        const auto t0 = std::chrono::steady_clock::now();
+        SparseModel model = checked_model(r);
+        std::vector<uint64_t> in_images;
+        if (image_ids) {
+            in_images = Point3DIdsInImages(model, *image_ids);
+            ids = &in_images;
+        }
+        const FlatFilter flat = FlattenForFilter(model, ids);
+        amc_filter_opts opts;
+        amc_filter_opts_default(&opts);
+        opts.max_reproj_error = max_reproj_error;
+        opts.min_tri_angle = min_tri_angle;
+        opts.errors_only = errors_only ? 1 : 0;
+        const amc_filter_problem pb = flat.Problem();
+        amc_filter_result res{};
+        int rc = AMC_OK;
+        std::string err;
+        {
+            py::gil_scoped_release release;
+            EstimatorCtx& E = TheEstimatorCtx();
+            std::lock_guard<std::mutex> lock(E.mu);
+            amc_ctx* ctx = nullptr;
+            try {
+                ctx = E.Get();
+            } catch (const std::runtime_error& e) {
+                rc = AMC_E_HIP;
+                err = e.what();
+            }
+            if (ctx) {
+                rc = amc_filter_points3d(ctx, &pb, &opts, &res);
+                if (rc != AMC_OK) err = std::string("amc_filter_points3d: ") + amc_last_error();
+            }
+        }
+        if (rc == AMC_E_INVALID) throw std::invalid_argument(err);
+        if (rc != AMC_OK) {
+            const py::object cls = py::module_::import("pycolmap_amd._capi").attr("AmcError");
+            const py::object exc = cls(rc, err);
+            PyErr_SetObject(cls.ptr(), exc.ptr());
+            throw py::error_already_set();
+        }
+        // the result's scalars are copied and its arrays freed before anything else can throw
+        const amc_filter_result stats = res;
+        size_t count = 0;
+        try {
+            if (errors_only)
+                ApplyPointErrors(flat, res.point_error, &model);
+            else
+                count = ApplyFilterResult(flat, res.point_verdict, res.obs_deleted, res.point_error, &model);
+        } catch (...) {
+            amc_filter_result_free(&res);
+            throw;
+        }
+        amc_filter_result_free(&res);
+        const uint64_t by_library = stats.num_filtered;
+        const double device_ms = stats.device_ms;
+        py::dict st;
+        st["call"] = errors_only ? "update_point3D_errors" : "filter_points3D";
+        st["num_points"] = stats.num_points;
+        st["num_observations"] = stats.num_observations;
+        st["num_filtered"] = stats.num_filtered;
+        st["num_batches"] = stats.num_batches;
+        st["device_ms"] = stats.device_ms;
+        st["kernel_ms"] = stats.kernel_ms;
+        st["copy_ms"] = stats.copy_ms;
+        if (!errors_only && by_library != count) throw std::runtime_error("filter_points3D: the library counted " + std::to_string(by_library) + ", the write-back " + std::to_string(count));
+        update_with_errors(r, model);
+        st["host_ms"] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - device_ms;
+        py::module_::import("pycolmap_amd._pycolmap").attr("_last_stats") = st;
+        return count;
+    };
     auto summary = [checked_model](const PyReconstruction& r) {
         const SparseModel m = checked_model(r);
         const size_t nobs = ComputeNumObservations(m);
@@ -1176,6 +1257,61 @@ PYBIND11_MODULE(_pycolmap, m) {
                  update_from_model(r, m);
                  return n;
              })
+        .def("point3D_ids", [](const PyReconstruction& r) {
+                 py::set ids;
+                 for (auto item : r.points3D) ids.add(item.first);
+                 return ids;
+             })
+        .def("exists_camera", [](const PyReconstruction& r, uint32_t camera_id) { return r.cameras.contains(py::int_(camera_id)); }, "camera_id"_a)
+        .def("exists_image", [](const PyReconstruction& r, uint32_t image_id) { return r.images.contains(py::int_(image_id)); }, "image_id"_a)
+        .def("exists_point3D", [](const PyReconstruction& r, uint64_t point3D_id) { return r.points3D.contains(py::int_(point3D_id)); }, "point3D_id"_a)
+        .def("delete_point3D", [checked_model, update_with_errors](PyReconstruction& r, uint64_t point3D_id) {
+                 SparseModel m = checked_model(r);
+                 DeletePoint3D(&m, point3D_id);
+                 update_with_errors(r, m);
+             }, "point3D_id"_a, "Delete a 3D point, and all its references in the observed images.")
+        .def("delete_observation", [checked_model, update_with_errors](PyReconstruction& r, uint32_t image_id, uint32_t point2D_idx) {
+                 SparseModel m = checked_model(r);
+                 DeleteObservation(&m, image_id, point2D_idx);
+                 update_with_errors(r, m);
+             }, "image_id"_a, "point2D_idx"_a,
+             "Delete one observation from an image and the corresponding 3D point.\n"
+             "Note that this deletes the entire 3D point, if the track has two elements\n"
+             "prior to calling this method.")
+        .def("filter_points3D", [filter_model](PyReconstruction& r, double max_reproj_error, double min_tri_angle, const std::unordered_set<uint64_t>& point3D_ids) {
+                 const std::vector<uint64_t> ids(point3D_ids.begin(), point3D_ids.end());
+                 return filter_model(r, &ids, nullptr, max_reproj_error, min_tri_angle, false);
+             }, "max_reproj_error"_a, "min_tri_angle"_a, "point3D_ids"_a,
+             "Filter 3D points with large reprojection error, negative depth, or\n"
+             "insufficient triangulation angle.\n\n"
+             "@param max_reproj_error    The maximum reprojection error.\n"
+             "@param min_tri_angle       The minimum triangulation angle.\n"
+             "@param point3D_ids         The points to be filtered.\n\n"
+             "@return                    The number of filtered observations.")
+        .def("filter_points3D_in_images", [filter_model](PyReconstruction& r, double max_reproj_error, double min_tri_angle, const std::unordered_set<uint32_t>& image_ids) {
+                 const std::vector<uint32_t> ids(image_ids.begin(), image_ids.end());
+                 return filter_model(r, nullptr, &ids, max_reproj_error, min_tri_angle, false);
+             }, "max_reproj_error"_a, "min_tri_angle"_a, "image_ids"_a,
+             "Filter 3D points with large reprojection error, negative depth, or\n"
+             "insufficient triangulation angle.\n\n"
+             "@param max_reproj_error    The maximum reprojection error.\n"
+             "@param min_tri_angle       The minimum triangulation angle.\n"
+             "@param image_ids           The the image ids in which the points3D are filtered.\n\n"
+             "@return                    The number of filtered observations.")
+        .def("filter_all_points3D", [filter_model](PyReconstruction& r, double max_reproj_error, double min_tri_angle) {
+                 return filter_model(r, nullptr, nullptr, max_reproj_error, min_tri_angle, false);
+             }, "max_reproj_error"_a, "min_tri_angle"_a,
+             "Filter 3D points with large reprojection error, negative depth, or\n"
+             "insufficient triangulation angle.\n\n"
+             "@param max_reproj_error    The maximum reprojection error.\n"
+             "@param min_tri_angle       The minimum triangulation angle.\n\n"
+             "@return                    The number of filtered observations.")
+        .def("update_point3D_errors", [filter_model](PyReconstruction& r) { filter_model(r, nullptr, nullptr, 0.0, 0.0, true); },
+             "Set every 3D point's error to the mean reprojection error over its track, on the GPU (DESIGN.md section 16).")
+        .def("update_point_3d_errors", [filter_model](PyReconstruction& r) { filter_model(r, nullptr, nullptr, 0.0, 0.0, true); },
+             "Later pycolmap's spelling of update_point3D_errors.")
+        .def("compute_mean_observations_per_reg_image", [checked_model](const PyReconstruction& r) { return ComputeMeanObservationsPerRegImage(checked_model(r)); })
+        .def("compute_mean_reprojection_error", [checked_model](const PyReconstruction& r) { return ComputeMeanReprojectionError(checked_model(r)); })
         .def("summary", summary)
         .def("__repr__", [checked_model](const PyReconstruction& r) {
             const SparseModel m = checked_model(r);

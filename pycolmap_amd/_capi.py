@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "amc_undistort_opts_default", "amc_undistort_camera", "amc_undistort_points", "amc_undistort_images",
     "amc_ba_opts_default", "amc_bundle_adjust",
     "amc_filter_opts_default", "amc_filter_points3d", "amc_filter_result_free",
+    "amc_triobs_opts_default", "amc_triangulate_observations", "amc_triobs_result_free",
 ]
 COMM_ID_BYTES = 128
 RANSAC_F, RANSAC_H, RANSAC_E = 0, 1, 2
@@ -351,6 +352,69 @@ def filter_inputs(camera_models, camera_params, image_cameras, qvec, tvec, xyz, 
     return models, prm, icam.astype(np.uint32), q, t, X, off.astype(np.uint64), oi.astype(np.uint32), xy, sel
 
 
+class TriobsOpts(C.Structure):  # amc_triobs_opts (include/amc_triobs.h)
+    _fields_ = [("create_max_angle_error", C.c_double), ("continue_max_angle_error", C.c_double),
+                ("min_angle", C.c_double), ("reserved", C.c_double)]
+
+
+class TriobsProblem(C.Structure):  # amc_triobs_problem
+    _fields_ = [("num_cameras", C.c_size_t), ("camera_models", C.c_void_p), ("camera_params", C.c_void_p),
+                ("num_images", C.c_size_t), ("image_cameras", C.c_void_p), ("qvec", C.c_void_p), ("tvec", C.c_void_p),
+                ("num_items", C.c_size_t), ("item_offsets", C.c_void_p), ("cand_image", C.c_void_p),
+                ("cand_xy", C.c_void_p), ("cand_has_point", C.c_void_p), ("cand_xyz", C.c_void_p),
+                ("no_create_two_view", C.c_void_p)]
+
+
+class TriobsResult(C.Structure):  # amc_triobs_result
+    _fields_ = [("num_items", C.c_uint64), ("num_candidates", C.c_uint64), ("num_created", C.c_uint64),
+                ("num_continued", C.c_uint64), ("continued", C.POINTER(C.c_int32)),
+                ("cand_round", C.POINTER(C.c_uint32)), ("round_offsets", C.POINTER(C.c_uint64)),
+                ("round_xyz", C.POINTER(C.c_double)), ("num_batches", C.c_uint32), ("reserved", C.c_uint32),
+                ("host_ms", C.c_double), ("device_ms", C.c_double), ("kernel_ms", C.c_double), ("copy_ms", C.c_double),
+                ("alloc_ms", C.c_double)]
+
+
+def triobs_inputs(camera_models, camera_params, image_cameras, qvec, tvec, item_offsets, cand_image, cand_xy,
+                  cand_has_point, cand_xyz, no_create_two_view=None):
+    """The flat problem of amc_triangulate_observations as contiguous arrays (copies: the caller's arrays are not
+    touched): models (C,) int32, params (C, 12), image_cameras (I,) uint32, qvec (I, 4) x y z w, tvec (I, 3),
+    item_offsets (T + 1,) uint64, cand_image (N,) uint32, cand_xy (N, 2), cand_has_point (N,) uint8, cand_xyz (N, 3),
+    no_create_two_view (T,) uint8 or None."""
+    who = "triangulate_observations"
+    models = np.array(camera_models, dtype=np.int32).reshape(-1)
+    if len(camera_params) != models.size:
+        raise ValueError(f"{who}: {models.size} camera models, {len(camera_params)} parameter sets")
+    prm = np.zeros((models.size, 12), np.float64)
+    for i, p in enumerate(camera_params):
+        p = np.asarray(p, dtype=np.float64).reshape(-1)
+        if p.size > 12:
+            raise ValueError(f"{who}: camera {i} has {p.size} parameters (at most 12)")
+        prm[i, :p.size] = p
+    icam = np.array(image_cameras, dtype=np.int64).reshape(-1)
+    q = np.array(qvec, dtype=np.float64).reshape(-1, 4)
+    t = np.array(tvec, dtype=np.float64).reshape(-1, 3)
+    off = np.array(item_offsets, dtype=np.int64).reshape(-1)
+    ci = np.array(cand_image, dtype=np.int64).reshape(-1)
+    xy = np.array(cand_xy, dtype=np.float64).reshape(-1, 2)
+    has = np.ascontiguousarray(np.asarray(cand_has_point).reshape(-1) != 0, dtype=np.uint8)
+    X = np.array(cand_xyz, dtype=np.float64).reshape(-1, 3)
+    if q.shape[0] != icam.size or t.shape[0] != icam.size or off.size < 1 or not (xy.shape[0] == has.size == X.shape[0] == ci.size):
+        raise ValueError(f"{who}: {icam.size} images by image_cameras, {q.shape[0]} rotations, {t.shape[0]} translations; "
+                         f"{off.size} offsets; {ci.size} candidates by cand_image, {xy.shape[0]} pixels, {has.size} flags, "
+                         f"{X.shape[0]} points")
+    if off.min() < 0 or int(off[-1]) != ci.size:
+        raise ValueError(f"{who}: item_offsets ends at {int(off[-1])}, {ci.size} candidates")
+    for name, a in (("image_cameras", icam), ("cand_image", ci)):
+        if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+            raise ValueError(f"{who}: {name} has an index outside 0 .. 2^32 - 1")
+    two = None
+    if no_create_two_view is not None:
+        two = np.ascontiguousarray(np.asarray(no_create_two_view).reshape(-1) != 0, dtype=np.uint8)
+        if two.size != off.size - 1:
+            raise ValueError(f"{who}: {off.size - 1} items, {two.size} two-view flags")
+    return models, prm, icam.astype(np.uint32), q, t, off.astype(np.uint64), ci.astype(np.uint32), xy, has, X, two
+
+
 class RigPoseResult(C.Structure):  # amc_rigpose_result (include/amc_rigpose.h)
     _fields_ = [("nqueries", C.c_size_t), ("ncorr", C.c_size_t), ("success", C.POINTER(C.c_uint8)),
                 ("qvec", C.POINTER(C.c_double)), ("tvec", C.POINTER(C.c_double)),
@@ -632,6 +696,14 @@ def load() -> C.CDLL:
         lib.amc_filter_points3d.restype = C.c_int
         lib.amc_filter_result_free.argtypes = [C.POINTER(FilterResult)]
         lib.amc_filter_result_free.restype = None
+    if hasattr(lib, "amc_triangulate_observations"):  # (absent from a library built from an older revision)
+        lib.amc_triobs_opts_default.argtypes = [C.POINTER(TriobsOpts)]
+        lib.amc_triobs_opts_default.restype = None
+        lib.amc_triangulate_observations.argtypes = [C.c_void_p, C.POINTER(TriobsProblem), C.POINTER(TriobsOpts),
+                                                     C.POINTER(TriobsResult)]
+        lib.amc_triangulate_observations.restype = C.c_int
+        lib.amc_triobs_result_free.argtypes = [C.POINTER(TriobsResult)]
+        lib.amc_triobs_result_free.restype = None
     if hasattr(lib, "amc_triangulate_tracks"):  # (absent from a library built from an older revision)
         lib.amc_tri_opts_default.argtypes = [C.POINTER(TriOpts)]
         lib.amc_tri_opts_default.restype = None
@@ -1098,6 +1170,37 @@ class Context:
                    "copy_ms": res.copy_ms, "alloc_ms": res.alloc_ms}
         finally:
             self._lib.amc_filter_result_free(C.byref(res))
+        return out
+
+    def triangulate_observations(self, camera_models, camera_params, image_cameras, qvec, tvec, item_offsets, cand_image,
+                                 cand_xy, cand_has_point, cand_xyz, no_create_two_view=None, create_max_angle_error=2.0,
+                                 continue_max_angle_error=2.0, min_angle=1.5):
+        """amc_triangulate_observations: Continue and the Create rounds of COLMAP's TriangulateImage for a batch of
+        points2D.  camera_models (C,), camera_params: C parameter vectors; image_cameras (I,),
+        qvec (I, 4) x y z w, tvec (I, 3); item_offsets (T + 1,) CSR over the candidates, an item's correspondences in
+        Find's order and its reference observation last; cand_image (N,), cand_xy (N, 2) pixels, cand_has_point (N,),
+        cand_xyz (N, 3); no_create_two_view (T,) or None.  The angles are in degrees.  The inputs are not modified.
+        Returns a dict: continued (T,) int32 item-local candidate or -1, cand_round (N,) uint32, round_offsets (T + 1,),
+        round_xyz (R, 3), num_created, num_continued, num_batches, host_ms, device_ms, kernel_ms, copy_ms, alloc_ms."""
+        models, prm, icam, q, t, off, ci, xy, has, X, two = triobs_inputs(
+            camera_models, camera_params, image_cameras, qvec, tvec, item_offsets, cand_image, cand_xy, cand_has_point,
+            cand_xyz, no_create_two_view)
+        o = TriobsOpts(float(create_max_angle_error), float(continue_max_angle_error), float(min_angle), 0.0)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        pb = TriobsProblem(models.size, ptr(models), ptr(prm), icam.size, ptr(icam), ptr(q), ptr(t), off.size - 1,
+                           ptr(off), ptr(ci), ptr(xy), ptr(has), ptr(X), None if two is None else ptr(two))
+        res = TriobsResult()
+        _check(self._lib.amc_triangulate_observations(self._h, C.byref(pb), C.byref(o), C.byref(res)))
+        try:
+            nit, n, nr = off.size - 1, ci.size, int(res.num_created)
+            a = lambda p, k: np.ctypeslib.as_array(p, (max(k, 1),))[:k].copy()  # noqa: E731
+            out = {"continued": a(res.continued, nit), "cand_round": a(res.cand_round, n),
+                   "round_offsets": a(res.round_offsets, nit + 1), "round_xyz": a(res.round_xyz, 3 * nr).reshape(nr, 3),
+                   "num_created": nr, "num_continued": int(res.num_continued), "num_batches": int(res.num_batches),
+                   "host_ms": res.host_ms, "device_ms": res.device_ms, "kernel_ms": res.kernel_ms,
+                   "copy_ms": res.copy_ms, "alloc_ms": res.alloc_ms}
+        finally:
+            self._lib.amc_triobs_result_free(C.byref(res))
         return out
 
     def estimate_rig_absolute_poses(self, offsets, camera_offsets, camera_models, camera_params, cams_from_rig,

@@ -42,6 +42,7 @@
 #include "undistort_host.h"
 #include "ba_host.h"
 #include "reconstruction.h"
+#include "triangulator_host.h"
 
 namespace py = pybind11;
 using namespace pybind11::literals;
@@ -1462,6 +1463,263 @@ PYBIND11_MODULE(_pycolmap, m) {
         },
         "reconstruction"_a, "options"_a = BundleAdjustmentOptions(),
         "Jointly refine every pose, point and camera of the reconstruction on the GPU, in place (DESIGN.md section 15).");
+
+    // ---- CorrespondenceGraph and IncrementalTriangulator (the reference's pycolmap/scene/correspondence_graph.h and
+    // pycolmap/sfm/incremental_triangulator.h; correspondence_graph.h, triangulator_host.h) ----
+    py::class_<Correspondence>(m, "Correspondence")
+        .def(py::init<>())
+        .def(py::init<uint32_t, uint32_t>(), "image_id"_a, "point2D_idx"_a)
+        .def_readwrite("image_id", &Correspondence::image_id)
+        .def_readwrite("point2D_idx", &Correspondence::point2D_idx)
+        .def("__copy__", [](const Correspondence& c) { return Correspondence(c); })
+        .def("__deepcopy__", [](const Correspondence& c, const py::dict&) { return Correspondence(c); })
+        .def("__repr__", [](const Correspondence& c) {
+            return "Correspondence(image_id=" + std::to_string(c.image_id) + ", point2D_idx=" + std::to_string(c.point2D_idx) + ")";
+        });
+    py::class_<CorrespondenceGraph, std::shared_ptr<CorrespondenceGraph>>(m, "CorrespondenceGraph")
+        .def(py::init<>())
+        .def("num_images", &CorrespondenceGraph::NumImages)
+        .def("num_image_pairs", &CorrespondenceGraph::NumImagePairs)
+        .def("exists_image", &CorrespondenceGraph::ExistsImage, "image_id"_a)
+        .def("num_observations_for_image", &CorrespondenceGraph::NumObservationsForImage, "image_id"_a)
+        .def("num_correspondences_for_image", &CorrespondenceGraph::NumCorrespondencesForImage, "image_id"_a)
+        .def("num_correspondences_between_images", &CorrespondenceGraph::NumCorrespondencesBetweenImages, "image_id1"_a, "image_id2"_a)
+        .def("finalize", &CorrespondenceGraph::Finalize)
+        .def("add_image", &CorrespondenceGraph::AddImage, "image_id"_a, "num_points2D"_a)
+        .def("add_correspondences", [](CorrespondenceGraph& g, uint32_t image_id1, uint32_t image_id2, const py::object& matches) {
+                 const auto arr = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>::ensure(matches);
+                 if (!arr) throw py::value_error("add_correspondences: matches must be convertible to an N x 2 uint32 array");
+                 if (!(arr.ndim() == 2 && arr.shape(1) == 2) && arr.size() != 0)
+                     throw py::value_error("add_correspondences: expected an N x 2 array of point2D indices");
+                 const auto frame = PythonCallFrame();
+                 for (const std::string& w : g.AddCorrespondences(image_id1, image_id2, arr.data(), static_cast<size_t>(arr.size() / 2)))
+                     Logging::Write(Logging::WARNING, frame.first, frame.second, w);
+             }, "image_id1"_a, "image_id2"_a, "correspondences"_a)
+        .def("extract_correspondences", [](const CorrespondenceGraph& g, uint32_t image_id, uint32_t point2D_idx) {
+                 return g.ExtractCorrespondences(image_id, point2D_idx);
+             }, "image_id"_a, "point2D_idx"_a)
+        .def("extract_transitive_correspondences", [](const CorrespondenceGraph& g, uint32_t image_id, uint32_t point2D_idx, size_t transitivity) {
+                 std::vector<Correspondence> found;
+                 g.ExtractTransitiveCorrespondences(image_id, point2D_idx, transitivity, &found);
+                 return found;
+             }, "image_id"_a, "point2D_idx"_a, "transitivity"_a)
+        .def("find_correspondences_between_images", [](const CorrespondenceGraph& g, uint32_t image_id1, uint32_t image_id2) {
+                 const std::vector<uint32_t> v = g.FindCorrespondencesBetweenImages(image_id1, image_id2);
+                 py::array_t<uint32_t> a({static_cast<py::ssize_t>(v.size() / 2), static_cast<py::ssize_t>(2)});
+                 std::copy(v.begin(), v.end(), a.mutable_data());
+                 return a;
+             }, "image_id1"_a, "image_id2"_a)
+        .def("has_correspondences", &CorrespondenceGraph::HasCorrespondences, "image_id"_a, "point2D_idx"_a)
+        .def("is_two_view_observation", &CorrespondenceGraph::IsTwoViewObservation, "image_id"_a, "point2D_idx"_a)
+        .def("__copy__", [](const CorrespondenceGraph& g) { return std::make_shared<CorrespondenceGraph>(g); })
+        .def("__deepcopy__", [](const CorrespondenceGraph& g, const py::dict&) { return std::make_shared<CorrespondenceGraph>(g); })
+        .def("__repr__", [](const CorrespondenceGraph& g) {
+            return "CorrespondenceGraph(num_images=" + std::to_string(g.NumImages()) + ", num_image_pairs=" + std::to_string(g.NumImagePairs()) + ")";
+        });
+
+    py::class_<TriangulatorOptions> PyTrgOpts(m, "IncrementalTriangulatorOptions");
+    PyTrgOpts.def(py::init<>())
+        .def_readwrite("max_transitivity", &TriangulatorOptions::max_transitivity, "Maximum transitivity to search for correspondences.")
+        .def_readwrite("create_max_angle_error", &TriangulatorOptions::create_max_angle_error, "Maximum angular error to create new triangulations.")
+        .def_readwrite("continue_max_angle_error", &TriangulatorOptions::continue_max_angle_error, "Maximum angular error to continue existing triangulations.")
+        .def_readwrite("merge_max_reproj_error", &TriangulatorOptions::merge_max_reproj_error, "Maximum reprojection error in pixels to merge triangulations.")
+        .def_readwrite("complete_max_reproj_error", &TriangulatorOptions::complete_max_reproj_error, "Maximum reprojection error to complete an existing triangulation.")
+        .def_readwrite("complete_max_transitivity", &TriangulatorOptions::complete_max_transitivity, "Maximum transitivity for track completion.")
+        .def_readwrite("re_max_angle_error", &TriangulatorOptions::re_max_angle_error, "Maximum angular error to re-triangulate under-reconstructed image pairs.")
+        .def_readwrite("re_min_ratio", &TriangulatorOptions::re_min_ratio, "Minimum ratio of common triangulations between an image pair over the number of correspondences between that image pair to be considered as under-reconstructed.")
+        .def_readwrite("re_max_trials", &TriangulatorOptions::re_max_trials, "Maximum number of trials to re-triangulate an image pair.")
+        .def_readwrite("min_angle", &TriangulatorOptions::min_angle, "Minimum pairwise triangulation angle for a stable triangulation.")
+        .def_readwrite("ignore_two_view_tracks", &TriangulatorOptions::ignore_two_view_tracks, "Whether to ignore two-view tracks.")
+        .def_readwrite("min_focal_length_ratio", &TriangulatorOptions::min_focal_length_ratio, "Thresholds for bogus camera parameters: images with bogus camera parameters are ignored in triangulation.")
+        .def_readwrite("max_focal_length_ratio", &TriangulatorOptions::max_focal_length_ratio)
+        .def_readwrite("max_extra_param", &TriangulatorOptions::max_extra_param);
+    MakeDataclass(PyTrgOpts, {"max_transitivity", "create_max_angle_error", "continue_max_angle_error", "merge_max_reproj_error",
+                              "complete_max_reproj_error", "complete_max_transitivity", "re_max_angle_error", "re_min_ratio",
+                              "re_max_trials", "min_angle", "ignore_two_view_tracks", "min_focal_length_ratio",
+                              "max_focal_length_ratio", "max_extra_param"});
+
+    // keeps the caller's graph and reconstruction alive and works on that reconstruction in place
+    struct PyTriangulator {
+        py::object graph, reconstruction;
+        std::set<uint64_t> modified;
+    };
+    // the outcome of triangulate_image back into r: the created points as new objects first, then update_with_errors
+    auto update_with_new_points = [update_with_errors](PyReconstruction& r, const SparseModel& m) {
+        for (const ModelPoint3D& mp : m.points3D) {
+            if (r.points3D.contains(py::int_(mp.point3D_id))) continue;
+            PyPoint3D p;
+            p.color = {{mp.rgb[0], mp.rgb[1], mp.rgb[2]}};
+            r.points3D[py::int_(mp.point3D_id)] = py::cast(p);
+        }
+        update_with_errors(r, m);
+    };
+    // TriangulateImage: one amc_triangulate_observations call per run of points2D.  Nothing of
+    // the reconstruction or of the modified set changes unless every call succeeds.  Without a device the call raises
+    // pycolmap_amd._capi.AmcError.
+    // solver: None, or a callable that stands in for the library (a test hook: the CPU tests pass the reference): it
+    // takes the flat problem as a dict of arrays and returns continued, cand_round, round_offsets and round_xyz.
+    auto triangulate_image_with = [checked_model, update_with_new_points](PyTriangulator& t, const TriangulatorOptions& o, uint32_t image_id,
+                                                                          const py::object& solver) -> size_t {
+        const auto t0 = std::chrono::steady_clock::now();
+        const std::string bad = o.Check();
+        if (!bad.empty()) throw py::value_error(CheckMessage(__FILE__, __LINE__, bad));
+        PyReconstruction& r = t.reconstruction.cast<PyReconstruction&>();
+        const CorrespondenceGraph& graph = t.graph.cast<const CorrespondenceGraph&>();
+        SparseModel model = checked_model(r);
+        ModelIndex ix(model, o);
+        const auto self = ix.image.find(image_id);
+        if (self == ix.image.end()) throw py::value_error(CheckMessage(__FILE__, __LINE__, "reconstruction.exists_image(image_id)", "image_id=" + std::to_string(image_id)));
+        (void)graph.NumPoints2D(image_id);  // an image the graph does not hold: the graph's ValueError
+        std::set<uint64_t> modified = t.modified;
+        TriobsApplied total;
+        uint64_t items = 0, observations = 0, calls = 0;
+        double device_ms = 0, kernel_ms = 0, copy_ms = 0;
+        if (!ix.image_bogus[self->second]) {
+            FlatTriobs flat = FlattenModelForTriobs(model, ix);
+            amc_triobs_opts opts;
+            amc_triobs_opts_default(&opts);
+            opts.create_max_angle_error = o.create_max_angle_error;
+            opts.continue_max_angle_error = o.continue_max_angle_error;
+            opts.min_angle = o.min_angle;
+            const size_t npoints2D = model.images[self->second].points2D.size();
+            for (size_t begin = 0; begin < npoints2D;) {
+                begin = PlanTriangulationRun(graph, model, ix, o, image_id, begin, &flat);
+                if (flat.NumItems() == 0) continue;
+                if (!solver.is_none()) {
+                    auto arr = [](const auto& v, py::ssize_t cols) {
+                        using T = typename std::decay<decltype(v)>::type::value_type;
+                        py::array_t<T> a({static_cast<py::ssize_t>(v.size()) / cols, cols});
+                        std::copy(v.begin(), v.end(), a.mutable_data());
+                        return a;
+                    };
+                    py::dict d;
+                    d["camera_models"] = arr(flat.camera_models, 1);
+                    d["camera_params"] = arr(flat.camera_params, 12);
+                    d["image_cameras"] = arr(flat.image_cameras, 1);
+                    d["qvec"] = arr(flat.qvec, 4);
+                    d["tvec"] = arr(flat.tvec, 3);
+                    d["item_offsets"] = arr(flat.item_offsets, 1);
+                    d["cand_image"] = arr(flat.cand_image, 1);
+                    d["cand_xy"] = arr(flat.cand_xy, 2);
+                    d["cand_has_point"] = arr(flat.cand_has_point, 1);
+                    d["cand_xyz"] = arr(flat.cand_xyz, 3);
+                    d["no_create_two_view"] = arr(flat.no_create_two_view, 1);
+                    d["create_max_angle_error"] = o.create_max_angle_error;
+                    d["continue_max_angle_error"] = o.continue_max_angle_error;
+                    d["min_angle"] = o.min_angle;
+                    const py::dict out = solver(d);
+                    const auto cont = py::array_t<int32_t, py::array::c_style | py::array::forcecast>::ensure(out["continued"]);
+                    const auto rnd = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>::ensure(out["cand_round"]);
+                    const auto roff = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>::ensure(out["round_offsets"]);
+                    const auto rxyz = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(out["round_xyz"]);
+                    if (!cont || !rnd || !roff || !rxyz || static_cast<size_t>(cont.size()) != flat.NumItems() ||
+                        static_cast<size_t>(rnd.size()) != flat.cand_image.size() || static_cast<size_t>(roff.size()) != flat.NumItems() + 1 ||
+                        static_cast<uint64_t>(rxyz.size()) != 3 * roff.data()[flat.NumItems()])
+                        throw py::value_error("triangulate_image: the solver's result does not have the problem's shape");
+                    items += flat.NumItems();
+                    observations += flat.cand_image.size();
+                    calls += 1;
+                    const TriobsApplied a = ApplyTriobsResult(flat, cont.data(), rnd.data(), roff.data(), rxyz.data(), &model, &ix, &modified);
+                    total.num_tris += a.num_tris;
+                    total.num_created += a.num_created;
+                    total.num_continued += a.num_continued;
+                    continue;
+                }
+                const amc_triobs_problem pb = flat.Problem();
+                amc_triobs_result res{};
+                int rc = AMC_OK;
+                std::string err;
+                {
+                    py::gil_scoped_release release;
+                    EstimatorCtx& E = TheEstimatorCtx();
+                    std::lock_guard<std::mutex> lock(E.mu);
+                    amc_ctx* ctx = nullptr;
+                    try {
+                        ctx = E.Get();
+                    } catch (const std::runtime_error& e) {
+                        rc = AMC_E_HIP;
+                        err = e.what();
+                    }
+                    if (ctx) {
+                        rc = amc_triangulate_observations(ctx, &pb, &opts, &res);
+                        if (rc != AMC_OK) err = std::string("amc_triangulate_observations: ") + amc_last_error();
+                    }
+                }
+                if (rc == AMC_E_INVALID) throw std::invalid_argument(err);
+                if (rc != AMC_OK) {
+                    const py::object cls = py::module_::import("pycolmap_amd._capi").attr("AmcError");
+                    const py::object exc = cls(rc, err);
+                    PyErr_SetObject(cls.ptr(), exc.ptr());
+                    throw py::error_already_set();
+                }
+                items += res.num_items;
+                observations += res.num_candidates;
+                calls += 1;
+                device_ms += res.device_ms;
+                kernel_ms += res.kernel_ms;
+                copy_ms += res.copy_ms;
+                try {
+                    const TriobsApplied a = ApplyTriobsResult(flat, res.continued, res.cand_round, res.round_offsets, res.round_xyz, &model, &ix, &modified);
+                    total.num_tris += a.num_tris;
+                    total.num_created += a.num_created;
+                    total.num_continued += a.num_continued;
+                } catch (...) {
+                    amc_triobs_result_free(&res);
+                    throw;
+                }
+                amc_triobs_result_free(&res);
+            }
+        }
+        update_with_new_points(r, model);
+        t.modified.swap(modified);
+        py::dict st;
+        st["call"] = "triangulate_image";
+        st["num_items"] = items;
+        st["num_observations"] = observations;
+        st["num_created_points"] = total.num_created;
+        st["num_continued_observations"] = total.num_continued;
+        st["num_device_calls"] = calls;
+        st["device_ms"] = device_ms;
+        st["kernel_ms"] = kernel_ms;
+        st["copy_ms"] = copy_ms;
+        st["host_ms"] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - device_ms;
+        py::module_::import("pycolmap_amd._pycolmap").attr("_last_stats") = st;
+        return total.num_tris;
+    };
+    py::class_<PyTriangulator>(m, "IncrementalTriangulator")
+        .def(py::init([](const py::object& graph, const py::object& reconstruction) {
+                 if (!py::isinstance<CorrespondenceGraph>(graph) || !py::isinstance<PyReconstruction>(reconstruction))
+                     throw py::type_error("IncrementalTriangulator(correspondence_graph: CorrespondenceGraph, reconstruction: Reconstruction)");
+                 return PyTriangulator{graph, reconstruction, {}};
+             }), "correspondence_graph"_a, "reconstruction"_a)
+        .def("_triangulate_image_with", triangulate_image_with, "options"_a, "image_id"_a, "solver"_a,
+             "triangulate_image with a callable in the library's place (test hook).")
+        .def("triangulate_image", [triangulate_image_with](PyTriangulator& t, const TriangulatorOptions& o, uint32_t image_id) {
+                 return triangulate_image_with(t, o, image_id, py::none());
+             }, "options"_a, "image_id"_a,
+             "Triangulate observations of image: continue the tracks its correspondences carry and create new ones, on the\n"
+             "GPU (DESIGN.md section 17).  Returns the number of triangulated observations.")
+        .def("add_modified_point3D", [](PyTriangulator& t, uint64_t point3D_id) { t.modified.insert(point3D_id); }, "point3D_id"_a)
+        .def("clear_modified_points3D", [](PyTriangulator& t) { t.modified.clear(); })
+        .def("get_modified_points3D", [](const PyTriangulator& t) {
+                 const PyReconstruction& r = t.reconstruction.cast<const PyReconstruction&>();
+                 py::set ids;
+                 for (uint64_t id : t.modified)
+                     if (r.points3D.contains(py::int_(id))) ids.add(py::int_(id));
+                 return ids;
+             }, "The recorded ids of changed points that still exist.")
+        .def_property_readonly("correspondence_graph", [](const PyTriangulator& t) { return t.graph; })
+        .def_property_readonly("reconstruction", [](const PyTriangulator& t) { return t.reconstruction; })
+        .def("__copy__", [](const PyTriangulator& t) { return PyTriangulator(t); })
+        .def("__deepcopy__", [](const PyTriangulator& t, const py::dict& memo) {
+                 const py::object deepcopy = py::module_::import("copy").attr("deepcopy");
+                 return PyTriangulator{deepcopy(t.graph, memo), deepcopy(t.reconstruction, memo), t.modified};
+             })
+        .def("__repr__", [](const PyTriangulator& t) {
+            const PyReconstruction& r = t.reconstruction.cast<const PyReconstruction&>();
+            return "IncrementalTriangulator(num_images=" + std::to_string(r.images.size()) + ", num_points3D=" + std::to_string(r.points3D.size()) +
+                   ", num_modified_points3D=" + std::to_string(t.modified.size()) + ")";
+        });
 
     // ---- estimate_triangulation (/root/reference/pycolmap/estimators/triangulation.h; tri_host.h) ----------------------
     py::class_<TriPointData>(m, "PointData")

@@ -8,7 +8,8 @@
 // (a counting sort, "binning"), so that the 64 tracks of a wave have the same length and finish together; a track's
 // result depends on its own observations only, never on its neighbours, the batch or the order.  No atomics, no LDS,
 // no scratch: the lane's state is a few dozen registers, and the inlier set of a local optimisation is kept in the
-// track's own bytes of the output mask until the final mask overwrites them.
+// track's own bytes of the output mask until the final mask overwrites them.  The device functions live in tri_core.h,
+// which the incremental triangulator's kernel (triobs.hip) includes too.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -18,34 +19,26 @@
 
 #include "amc_internal.h"
 #include "pose_math.h"
-#include "tri_angle.h"
+#include "tri_core.h"
 #include "../../include/amc_tri.h"
 
 using namespace amc;
 
 namespace {
 
-using tvg::dsqrt;
-using tri::tri_acos;
-using tri::tri_angle;
+using tri::kNoTable;
+using tri::TriPose;
+using tri::TriSupport;
 
-constexpr uint64_t kNoTable = ~(uint64_t)0;
 constexpr int kBlock = 256;
 // device batch bounds: a call with more observations or tracks is split into several launches on the same buffers
 constexpr uint64_t kMaxBatchObs = (uint64_t)1 << 23;
 constexpr uint64_t kMaxBatchTracks = (uint64_t)1 << 20;
 
-// one pose: cam_from_world [R | t] row-major, the projection centre -R^T t, padding to 128 bytes
-struct TriPose {
-    double P[12];
-    double C[3];
-    double pad;
-};
-
 struct TriParams {
     const uint64_t* off;      // batch tracks + 1: the caller's observation offsets (obs_base = the batch's first)
     const uint32_t* order;    // batch tracks: batch-local track index, longest tracks first
-    const uint32_t* pose;     // the batch's observations, batch-local index
+    const uint32_t* pose_idx; // the batch's observations, batch-local index
     const double* xy;         // 2 per observation
     const TriPose* poses;
     const uint64_t* dyn_off;  // by track length (< dyn_n): start of its dyn_max_num_trials row in dyn_tab, or kNoTable
@@ -62,145 +55,13 @@ struct TriParams {
     uint64_t* num_trials;
     uint8_t* success;
     uint8_t* mask;            // the batch's observations
+    // tri_core.h's view of the batch's observations
+    __device__ __forceinline__ double x(uint64_t o) const { return xy[2 * o]; }
+    __device__ __forceinline__ double y(uint64_t o) const { return xy[2 * o + 1]; }
+    __device__ __forceinline__ const TriPose& pose(uint64_t o) const { return poses[this->pose_idx[o]]; }
 };
 
-// ---- numerics (acos and the triangulation angle: tri_angle.h) -----------------------------------------
-// P.row(2) . [X; 1]
-__device__ __forceinline__ double tri_depth(const double* P, const double* X) {
-    return P[8] * X[0] + P[9] * X[1] + P[10] * X[2] + P[11];
-}
-
-// squared angular error of observation (x, y) under pose P for the point X
-__device__ __forceinline__ double tri_residual(double x, double y, const double* P, const double* X) {
-    const double na = dsqrt(x * x + y * y + 1.0);
-    const double a0 = x / na, a1 = y / na, a2 = 1.0 / na;
-    const double q0 = P[0] * X[0] + P[1] * X[1] + P[2] * X[2] + P[3];
-    const double q1 = P[4] * X[0] + P[5] * X[1] + P[6] * X[2] + P[7];
-    const double q2 = P[8] * X[0] + P[9] * X[1] + P[10] * X[2] + P[11];
-    const double nb = dsqrt(q0 * q0 + q1 * q1 + q2 * q2);
-    const double c = a0 * (q0 / nb) + a1 * (q1 / nb) + a2 * (q2 / nb);
-    const double e = tri_acos(c);
-    return e * e;
-}
-
-// eigenvector of the smallest eigenvalue of the symmetric 4 x 4 `a` (first minimum of the Jacobi diagonal), dehomogenised
-__device__ __forceinline__ void tri_smallest_dehom(double (&a)[16], double* X) {
-    double v[16];
-    tvg::jacobi_eigen_t<4>(a, v);
-    double dmin = a[0];
-    double e0 = v[0], e1 = v[4], e2 = v[8], w = v[12];
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-        if (a[5 * i] < dmin) { dmin = a[5 * i]; e0 = v[i]; e1 = v[4 + i]; e2 = v[8 + i]; w = v[12 + i]; }
-    X[0] = e0 / w; X[1] = e1 / w; X[2] = e2 / w;
-}
-
-// ---- the estimator ------------------------------------------------------------------------------------
-// two observations: DLT rows x P2 - P0, y P2 - P1 of both views, A^T A, smallest eigenvector; then both depths and the
-// angle
-__device__ __forceinline__ bool tri_estimate_two(const TriParams& p, uint64_t i, uint64_t j, double* X) {
-    const double xi = p.xy[2 * i], yi = p.xy[2 * i + 1], xj = p.xy[2 * j], yj = p.xy[2 * j + 1];
-    const TriPose& Pi = p.poses[p.pose[i]];
-    const TriPose& Pj = p.poses[p.pose[j]];
-    double A[4][4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        A[0][c] = xi * Pi.P[8 + c] - Pi.P[c];
-        A[1][c] = yi * Pi.P[8 + c] - Pi.P[4 + c];
-        A[2][c] = xj * Pj.P[8 + c] - Pj.P[c];
-        A[3][c] = yj * Pj.P[8 + c] - Pj.P[4 + c];
-    }
-    double ata[16];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s += A[k][r] * A[k][c];
-            ata[4 * r + c] = s;
-        }
-    tri_smallest_dehom(ata, X);
-    return tri_depth(Pi.P, X) >= DBL_EPSILON && tri_depth(Pj.P, X) >= DBL_EPSILON &&
-           tri_angle(Pi.C, Pj.C, X) >= p.min_tri_angle;
-}
-
-// (observation indices below are batch-local)
-// the local estimator on the inlier set marked in mask[o0 .. o0 + n) (cnt >= 2 members): two members -> the two-view
-// estimator; more -> A = sum term^T term, term = P - p p^T P, p = normalized([x, y, 1]); every depth, then any pair
-// (i, j < i) with the angle
-__device__ __forceinline__ bool tri_estimate_set(const TriParams& p, uint64_t o0, uint64_t n, uint32_t cnt, double* X) {
-    const uint8_t* set = p.mask + o0;
-    if (cnt == 2) {
-        uint64_t i = 0;
-        while (!set[i]) ++i;
-        uint64_t j = i + 1;
-        while (!set[j]) ++j;
-        return tri_estimate_two(p, o0 + i, o0 + j, X);
-    }
-    double A[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) A[k] = 0.0;
-    for (uint64_t k = 0; k < n; ++k) {
-        if (!set[k]) continue;
-        const uint64_t o = o0 + k;
-        const double x = p.xy[2 * o], y = p.xy[2 * o + 1];
-        const double* P = p.poses[p.pose[o]].P;
-        const double nrm = dsqrt(x * x + y * y + 1.0);
-        const double h[3] = {x / nrm, y / nrm, 1.0 / nrm};
-        double T[3][4];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const double m = h[r] * h[0] * P[c] + h[r] * h[1] * P[4 + c] + h[r] * h[2] * P[8 + c];
-                T[r][c] = P[4 * r + c] - m;
-            }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) A[4 * r + c] = A[4 * r + c] + (T[0][r] * T[0][c] + T[1][r] * T[1][c] + T[2][r] * T[2][c]);
-    }
-    tri_smallest_dehom(A, X);
-    for (uint64_t k = 0; k < n; ++k)
-        if (set[k] && !(tri_depth(p.poses[p.pose[o0 + k]].P, X) >= DBL_EPSILON)) return false;
-    for (uint64_t i = 1; i < n; ++i) {
-        if (!set[i]) continue;
-        const double* ci = p.poses[p.pose[o0 + i]].C;
-        for (uint64_t j = 0; j < i; ++j) {
-            if (!set[j]) continue;
-            if (tri_angle(ci, p.poses[p.pose[o0 + j]].C, X) >= p.min_tri_angle) return true;
-        }
-    }
-    return false;
-}
-
-// InlierSupportMeasurer::Evaluate: inliers have residual <= max_residual (NaN is an outlier); the residual sum adds
-// the inliers' residuals in observation order.  mark: also write the inlier flags to the track's mask bytes.
-struct TriSupport {
-    uint32_t cnt;
-    double sum;
-};
-__device__ __forceinline__ TriSupport tri_score(const TriParams& p, uint64_t o0, uint64_t n, const double* X, bool mark) {
-    TriSupport s{0u, 0.0};
-    uint8_t* m = p.mask + o0;
-    for (uint64_t k = 0; k < n; ++k) {
-        const uint64_t o = o0 + k;
-        const double r = tri_residual(p.xy[2 * o], p.xy[2 * o + 1], p.poses[p.pose[o]].P, X);
-        const bool in = r <= p.max_residual;
-        if (in) {
-            s.cnt += 1;
-            s.sum += r;
-        }
-        if (mark) m[k] = in ? 1 : 0;
-    }
-    return s;
-}
-__device__ __forceinline__ bool tri_better(const TriSupport a, const TriSupport b) {
-    return a.cnt > b.cnt || (a.cnt == b.cnt && a.sum < b.sum);
-}
-
-// ---- LORANSAC<TriangulationEstimator x 2, InlierSupportMeasurer, CombinationSampler> -----------------
+// ---- the estimator and the LO-RANSAC are tri_core.h's ---------------------------------------------
 __global__ __launch_bounds__(kBlock) void tri_kernel(TriParams p) {
     const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
     if (g >= p.ntracks) return;
@@ -211,53 +72,13 @@ __global__ __launch_bounds__(kBlock) void tri_kernel(TriParams p) {
     TriSupport best{0u, DBL_MAX};
     uint64_t trial = 0;
     if (n >= 2) {
-        const uint64_t combos = n * (n - 1) / 2;
-        const uint64_t max_trials = p.max_trials < combos ? p.max_trials : combos;
         const uint64_t tab = n < p.dyn_n ? p.dyn_off[n] : kNoTable;
-        uint64_t dyn_max = max_trials;
-        uint64_t a = 0, b = 1;  // the next pair of the lexicographic combination order
-        bool abort = false;
-        for (trial = 0; trial < max_trials; ++trial) {
-            if (abort) {
-                trial += 1;
-                break;
-            }
-            const uint64_t i = a, j = b;
-            if (++b == n) {
-                ++a;
-                b = a + 1;
-                if (b == n) { a = 0; b = 1; }
-            }
-            double X[3];
-            if (!tri_estimate_two(p, o0 + i, o0 + j, X)) continue;
-            const TriSupport s = tri_score(p, o0, n, X, false);
-            if (tri_better(s, best)) {
-                best = s;
-                best_xyz[0] = X[0]; best_xyz[1] = X[1]; best_xyz[2] = X[2];
-                if (s.cnt > 2) {
-                    for (int lt = 0; lt < 10; ++lt) {
-                        const uint32_t prev = best.cnt;
-                        // the inlier set of the current best model, in the mask bytes
-                        const TriSupport cur = tri_score(p, o0, n, best_xyz, true);
-                        double L[3];
-                        if (tri_estimate_set(p, o0, n, cur.cnt, L)) {
-                            const TriSupport ls = tri_score(p, o0, n, L, false);
-                            if (tri_better(ls, best)) {
-                                best = ls;
-                                best_xyz[0] = L[0]; best_xyz[1] = L[1]; best_xyz[2] = L[2];
-                            }
-                        }
-                        if (best.cnt <= prev) break;
-                    }
-                }
-                dyn_max = tab == kNoTable ? kNoTable : p.dyn_tab[tab + best.cnt];
-            }
-            if (trial >= dyn_max && trial >= p.min_trials) abort = true;
-        }
+        trial = tri::tri_lo_ransac(p, o0, n, p.max_trials, p.min_trials, tab == kNoTable ? nullptr : p.dyn_tab + tab,
+                                   best_xyz, best);
     }
     const bool ok = best.cnt >= 2;
     if (ok) {
-        tri_score(p, o0, n, best_xyz, true);
+        tri::tri_score(p, o0, n, best_xyz, true);
     } else {
         for (uint64_t k = 0; k < n; ++k) mask[k] = 0;
     }
@@ -427,7 +248,7 @@ static int triangulate_impl(amc_ctx* ctx, const double* poses, size_t nposes, co
         TriParams p{};
         p.off = d_off;
         p.order = d_ord;
-        p.pose = d_opose;
+        p.pose_idx = d_opose;
         p.xy = d_xy;
         p.poses = d_pose;
         p.dyn_off = d_doff;

@@ -11,6 +11,7 @@
  *   BundleAdjustmentOptions{loss_function_type, loss_function_scale, refine_*, solver_options: CeresSolverOptions}
  *                                                                          amc_ba_opts + the constant masks
  *   bundle_adjustment(reconstruction, options)                             amc_bundle_adjust on the flattened model
+ *   BundleAdjuster(options, config).Solve(&reconstruction)                 amc_bundle_adjust_masked on the config's part
  */
 #ifndef AMC_BA_H_
 #define AMC_BA_H_
@@ -84,6 +85,14 @@ void amc_ba_opts_default(amc_ba_opts* o);
  * range, a value that is not finite, a point with fewer than two observations, invalid options), AMC_E_NOMEM,
  * AMC_E_HIP.  On an error the problem's arrays are unchanged. */
 int amc_bundle_adjust(amc_ctx* ctx, amc_ba_problem* problem, const amc_ba_opts* options, amc_ba_result* result);
+
+/* The same with constant points: point_const is num_points bytes, non-zero = the point is constant;
+ * NULL = no constant point, which is amc_bundle_adjust.  A constant point has no column: its xyz comes back bit for bit,
+ * its residuals still count in the cost and in the pose and camera blocks, it is left out of num_variable_parameters
+ * and it needs one observation instead of two.  A problem without any variable parameter ends with
+ * AMC_BA_NOTHING_TO_REFINE before the device is used (both costs 0). */
+int amc_bundle_adjust_masked(amc_ctx* ctx, amc_ba_problem* problem, const uint8_t* point_const,
+                             const amc_ba_opts* options, amc_ba_result* result);
 
 #ifdef __cplusplus
 }

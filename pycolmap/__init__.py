@@ -6,7 +6,8 @@ known-pose triangulation (`estimate_triangulation`, `PointData`, `EstimateTriang
 `rig_absolute_pose_estimation`) and of image undistortion (`undistort_images`, `UndistortCameraOptions`, `CopyType`, with
 the building blocks `undistort_camera` and `undistort_image`) and of bundle adjustment (`bundle_adjustment`,
 `BundleAdjustmentOptions`, `CeresSolverOptions`, `LossFunctionType`, with the minimal `Reconstruction` and its `Point3D`,
-`Track`, `TrackElement`, `Point2D`) and of incremental triangulation (`CorrespondenceGraph`, `Correspondence`,
+`Track`, `TrackElement`, `Point2D`; `BundleAdjustmentConfig` and `BundleAdjuster` with `solve` for a part of the
+model) and of incremental triangulation (`CorrespondenceGraph`, `Correspondence`,
 `IncrementalTriangulator` with `triangulate_image`, `IncrementalTriangulatorOptions`)
 resolves to pycolmap_amd's MI355X implementation.  Only what SURVEY.md section 8 and DESIGN.md sections 10 to 17 put in
 scope exists;
@@ -22,4 +23,4 @@ globals().update({n: getattr(_impl, n) for n in _PUBLIC})
 
 def __getattr__(name):
     raise AttributeError(f"pycolmap.{name} is outside pycolmap_amd's scope (SIFT feature extraction, exhaustive / sequential "
-                         f"matching + two-view verification, known-pose triangulation, absolute pose, image undistortion, bundle adjustment of a minimal Reconstruction behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}; also in scope: point filtering, and incremental triangulation of an image (CorrespondenceGraph, IncrementalTriangulator.triangulate_image)")
+                         f"matching + two-view verification, known-pose triangulation, absolute pose, image undistortion, bundle adjustment of a minimal Reconstruction behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}; also in scope: point filtering, and incremental triangulation of an image (CorrespondenceGraph, IncrementalTriangulator.triangulate_image), and the adjustment of a part of the model (BundleAdjustmentConfig, BundleAdjuster.solve)")

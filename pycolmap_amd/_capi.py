@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = [
     "amc_upload_matches",
     "amc_estimate_rig_absolute_poses", "amc_rigpose_result_free",
     "amc_undistort_opts_default", "amc_undistort_camera", "amc_undistort_points", "amc_undistort_images",
-    "amc_ba_opts_default", "amc_bundle_adjust",
+    "amc_ba_opts_default", "amc_bundle_adjust", "amc_bundle_adjust_masked",
     "amc_filter_opts_default", "amc_filter_points3d", "amc_filter_result_free",
     "amc_triobs_opts_default", "amc_triangulate_observations", "amc_triobs_result_free",
 ]
@@ -688,6 +688,10 @@ def load() -> C.CDLL:
         lib.amc_ba_opts_default.restype = None
         lib.amc_bundle_adjust.argtypes = [C.c_void_p, C.POINTER(BaProblem), C.POINTER(BaOpts), C.POINTER(BaResult)]
         lib.amc_bundle_adjust.restype = C.c_int
+    if hasattr(lib, "amc_bundle_adjust_masked"):
+        lib.amc_bundle_adjust_masked.argtypes = [C.c_void_p, C.POINTER(BaProblem), C.c_void_p, C.POINTER(BaOpts),
+                                                 C.POINTER(BaResult)]
+        lib.amc_bundle_adjust_masked.restype = C.c_int
     if hasattr(lib, "amc_filter_points3d"):  # (absent from a library built from an older revision)
         lib.amc_filter_opts_default.argtypes = [C.POINTER(FilterOpts)]
         lib.amc_filter_opts_default.restype = None
@@ -1121,12 +1125,13 @@ class Context:
         return out
 
     def bundle_adjust(self, camera_models, camera_params, camera_const, image_cameras, qvec, tvec, pose_const, xyz,
-                      obs_image, obs_point, obs_xy, options=None):
+                      obs_image, obs_point, obs_xy, options=None, point_const=None):
         """amc_bundle_adjust: Levenberg-Marquardt over every pose, point and camera at once.
         camera_models (C,), camera_params: C parameter vectors, camera_const (C, <= 12) non-zero = constant;
         image_cameras (I,) camera indices, qvec (I, 4) x y z w, tvec (I, 3), pose_const (I, 6) over the tangent
         (rotation 3, translation 3); xyz (P, 3); obs_image / obs_point (N,), obs_xy (N, 2) pixels.  options: a dict of
-        amc_ba_opts fields.  The inputs are not modified.  Returns a dict: camera_params (C, 12), qvec, tvec, xyz and
+        amc_ba_opts fields.  point_const (P,): non-zero = the point is constant (amc_bundle_adjust_masked, 15.12); None
+        = amc_bundle_adjust.  The inputs are not modified.  Returns a dict: camera_params (C, 12), qvec, tvec, xyz and
         the statistics of amc_ba_result (termination as a name)."""
         models, prm, cc, icam, q, t, pc, X, oi, op, xy = ba_inputs(camera_models, camera_params, camera_const,
                                                                    image_cameras, qvec, tvec, pose_const, xyz,
@@ -1136,7 +1141,13 @@ class Context:
         pb = BaProblem(models.size, ptr(models), ptr(prm), ptr(cc), icam.size, ptr(icam), ptr(q), ptr(t), ptr(pc),
                        X.shape[0], ptr(X), oi.size, ptr(oi), ptr(op), ptr(xy))
         res = BaResult()
-        _check(self._lib.amc_bundle_adjust(self._h, C.byref(pb), C.byref(o), C.byref(res)))
+        if point_const is None:
+            _check(self._lib.amc_bundle_adjust(self._h, C.byref(pb), C.byref(o), C.byref(res)))
+        else:
+            mask = np.ascontiguousarray(np.asarray(point_const).reshape(-1) != 0, dtype=np.uint8)
+            if mask.size != X.shape[0]:
+                raise ValueError(f"bundle adjustment: {X.shape[0]} points, {mask.size} point_const flags")
+            _check(self._lib.amc_bundle_adjust_masked(self._h, C.byref(pb), ptr(mask), C.byref(o), C.byref(res)))
         out = {k: getattr(res, k) for k, _ in BaResult._fields_}
         out["termination"] = BA_TERMINATIONS[res.termination]
         out.update(camera_params=prm, qvec=q, tvec=t, xyz=X)

@@ -55,6 +55,7 @@ struct Dev {
     // PCG and the step
     double *x, *r, *z, *p, *qv, *u, *campart2, *yp, *jy2_img;
     Scalars* s;
+    const uint8_t* pvar;  // 15.12: 1 = the point is variable (last, so that every other field and buffer stays where it was)
 };
 struct Params {
     double *q, *t, *cp, *X;
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(kBlock) void ba_eval_kernel(Dev d, Params P, int ja
         for (uint32_t k = 0; k < d.kc; ++k)
             d.Jc[(size_t)2 * d.kc * o + d.kc * a + k] =
                 d.cvar[kKC * c + k] ? Jc[kKC * a + k] * d.sc_c[6 * d.nimg + kKC * c + k] : 0.0;
-        for (int k = 0; k < 3; ++k) d.Jx[6 * o + 3 * a + k] = Jx[3 * a + k] * d.sc_p[3 * j + k];
+        for (int k = 0; k < 3; ++k) d.Jx[6 * o + 3 * a + k] = d.pvar[j] ? Jx[3 * a + k] * d.sc_p[3 * j + k] : 0.0;
     }
 }
 
@@ -115,6 +116,10 @@ __global__ __launch_bounds__(kBlock) void ba_point_kernel(Dev d, double radius) 
     V[0] = V[0] + ba::lm_diag(V[0], radius);
     V[3] = V[3] + ba::lm_diag(V[3], radius);
     V[5] = V[5] + ba::lm_diag(V[5], radius);
+    if (!d.pvar[j]) {  // 15.12: a constant point's block is the identity's (its J_x, hence V and g, are exact zeros)
+        V[0] = V[3] = V[5] = 1.0;
+        V[1] = V[2] = V[4] = 0.0;
+    }
     double Vi[6], vg[3];
     ba::sym3_inverse(V, Vi);
     ba::sym3_mul(Vi, g, vg);
@@ -513,7 +518,7 @@ __global__ __launch_bounds__(kWave) void ba_lm_reduce_kernel(Dev d, Params P, in
         o4 = wave_total(4 * d.nimg, [&](uint32_t k) { return P.q[k] * P.q[k]; }) +
              wave_total(3 * d.nimg, [&](uint32_t k) { return P.t[k] * P.t[k]; }) +
              wave_total(kKC * d.ncam, [&](uint32_t k) { return d.cvar[k] ? P.cp[k] * P.cp[k] : 0.0; }) +
-             wave_total(3 * d.npts, [&](uint32_t k) { return P.X[k] * P.X[k]; });
+             wave_total(3 * d.npts, [&](uint32_t k) { return d.pvar[k / 3] ? P.X[k] * P.X[k] : 0.0; });
     }
     if (threadIdx.x == 0) {
         d.s->out[0] = cost;
@@ -527,8 +532,8 @@ __global__ __launch_bounds__(kWave) void ba_lm_reduce_kernel(Dev d, Params P, in
 // ---- host side ------------------------------------------------------------------------------------------------------
 inline unsigned blocks_for(size_t n) { return (unsigned)std::max<size_t>((n + kBlock - 1) / kBlock, 1); }
 
-int run(amc_ctx* ctx, amc_ba_problem* pb, const amc_ba_opts* opts, amc_ba_result* result) {
-    const char* const fn = "amc_bundle_adjust";
+int run(const char* fn, amc_ctx* ctx, amc_ba_problem* pb, const uint8_t* point_const, const amc_ba_opts* opts,
+        amc_ba_result* result) {
     const char* const hipchk_who = fn;
     if (!ctx || !pb || !opts || !result) return api_fail(AMC_E_INVALID, "%s: NULL argument", fn);
     std::memset(result, 0, sizeof *result);
@@ -539,7 +544,7 @@ int run(amc_ctx* ctx, amc_ba_problem* pb, const amc_ba_opts* opts, amc_ba_result
     // 15.2: the checks, the variable columns, the two CSR orders, the cameras' image lists
     ba::Plan plan;
     try {
-        bad = ba::make_plan(*pb, &plan);
+        bad = ba::make_plan(*pb, point_const, &plan);
     } catch (const std::bad_alloc&) {
         return api_fail(AMC_E_NOMEM, "%s: out of host memory", fn);
     }
@@ -555,7 +560,7 @@ int run(amc_ctx* ctx, amc_ba_problem* pb, const amc_ba_opts* opts, amc_ba_result
     result->num_points = npts;
     result->num_observations = nobs;
     result->num_variable_parameters = plan.num_variable;
-    if (nobs == 0) {
+    if (nobs == 0 || plan.num_variable == 0) {  // (no device call: both costs are reported as 0)
         result->termination = AMC_BA_NOTHING_TO_REFINE;
         return AMC_OK;
     }
@@ -577,7 +582,7 @@ int run(amc_ctx* ctx, amc_ba_problem* pb, const amc_ba_opts* opts, amc_ba_result
     d.loss_scale = op.loss_function_scale;
     uint32_t *d_oimg, *d_opt, *d_ioff, *d_poff, *d_pobs, *d_icam, *d_coff, *d_cimg;
     int32_t* d_cmodel;
-    uint8_t *d_cvar, *d_ivar;
+    uint8_t *d_cvar, *d_ivar, *d_pvar;
     double* d_oxy;
     Params P[2];
     DevBuf<void> mem;
@@ -594,7 +599,7 @@ int run(amc_ctx* ctx, amc_ba_problem* pb, const amc_ba_opts* opts, amc_ba_result
         .part(&d.campart, camvar ? (size_t)kCamPart * nimg : 1)
         .part(&d.x, nred).part(&d.r, nred).part(&d.z, nred).part(&d.p, nred).part(&d.qv, nred)
         .part(&d.u, 3 * npts).part(&d.campart2, kKC * nimg).part(&d.yp, 3 * npts).part(&d.jy2_img, nimg)
-        .part(&d.s, 1);
+        .part(&d.s, 1).part(&d_pvar, npts);
     {
         const hipError_t e = parts.carve(mem);
         if (e == hipErrorOutOfMemory) return api_fail(AMC_E_NOMEM, "%s: out of device memory", fn);
@@ -611,6 +616,7 @@ int run(amc_ctx* ctx, amc_ba_problem* pb, const amc_ba_opts* opts, amc_ba_result
     d.cmodel = d_cmodel;
     d.cvar = d_cvar;
     d.ivar = d_ivar;
+    d.pvar = d_pvar;
     d.oxy = d_oxy;
     auto up = [&](void* dst, const void* src, size_t bytes) {
         return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
@@ -628,6 +634,7 @@ int run(amc_ctx* ctx, amc_ba_problem* pb, const amc_ba_opts* opts, amc_ba_result
     HIPCHK(up(d_cmodel, pb->camera_models, ncam * 4));
     HIPCHK(up(d_cvar, cvar.data(), kKC * ncam));
     HIPCHK(up(d_ivar, ivar.data(), 6 * nimg));
+    HIPCHK(up(d_pvar, plan.pvar.data(), npts));
     HIPCHK(up(d_oxy, oxy.data(), nobs * 16));
     HIPCHK(up(P[0].q, pb->qvec, nimg * 32));
     HIPCHK(up(P[0].t, pb->tvec, nimg * 24));
@@ -820,7 +827,12 @@ void amc_ba_opts_default(amc_ba_opts* o) {
 }
 
 int amc_bundle_adjust(amc_ctx* ctx, amc_ba_problem* problem, const amc_ba_opts* options, amc_ba_result* result) {
-    return run(ctx, problem, options, result);
+    return run("amc_bundle_adjust", ctx, problem, nullptr, options, result);
+}
+
+int amc_bundle_adjust_masked(amc_ctx* ctx, amc_ba_problem* problem, const uint8_t* point_const, const amc_ba_opts* options,
+                             amc_ba_result* result) {
+    return run("amc_bundle_adjust_masked", ctx, problem, point_const, options, result);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@ struct Plan {
     uint32_t kc = 0;             // the largest parameter count among the cameras
     bool camvar = false;         // is any camera parameter variable
     std::vector<uint8_t> cvar, ivar;            // 12 per camera, 6 per image: 1 = variable
+    std::vector<uint8_t> pvar;                  // 1 per point: 1 = variable (0: a constant point, 15.12)
     std::vector<uint32_t> ioff, poff, coff;     // CSR offsets by image, by point, by camera
     std::vector<uint32_t> oimg, opt;            // image and point of each observation, in image order
     std::vector<double> oxy;                    // its pixel
@@ -47,8 +48,9 @@ inline std::string check_options(const amc_ba_opts& o) {
 }
 
 // Checks the problem and fills the plan; returns what is wrong with the problem, or the empty string.  Nothing is read
-// through an index before that index has been checked.
-inline std::string make_plan(const amc_ba_problem& pb, Plan* plan) {
+// through an index before that index has been checked.  point_const: num_points bytes, non-zero = the point is constant
+// (15.12), or NULL for no constant point.
+inline std::string make_plan(const amc_ba_problem& pb, const uint8_t* point_const, Plan* plan) {
     constexpr int kP = cam::kMaxParams;
     const size_t ncam = pb.num_cameras, nimg = pb.num_images, npts = pb.num_points, nobs = pb.num_observations;
     if ((ncam && (!pb.camera_models || !pb.camera_params || !pb.camera_const)) ||
@@ -70,9 +72,12 @@ inline std::string make_plan(const amc_ba_problem& pb, Plan* plan) {
         ++pcount[pb.obs_point[o]];
         ++icount[pb.obs_image[o]];
     }
-    for (size_t j = 0; j < npts; ++j)
-        if (pcount[j] < 2)
-            return "point " + std::to_string(j) + " has " + std::to_string(pcount[j]) + " observations (at least two)";
+    for (size_t j = 0; j < npts; ++j) {
+        const bool constant = point_const && point_const[j];
+        if (constant ? pcount[j] < 1 : pcount[j] < 2)
+            return "point " + std::to_string(j) + " has " + std::to_string(pcount[j]) + " observations (at least " +
+                   (constant ? "one for a constant point)" : "two)");
+    }
     bool fin = all_finite(pb.qvec, 4 * nimg) && all_finite(pb.tvec, 3 * nimg) && all_finite(pb.xyz, 3 * npts) &&
                all_finite(pb.obs_xy, 2 * nobs);
     for (size_t c = 0; c < ncam && fin; ++c) fin = all_finite(pb.camera_params + kP * c, cam::num_params(pb.camera_models[c]));
@@ -83,7 +88,13 @@ inline std::string make_plan(const amc_ba_problem& pb, Plan* plan) {
     p.cvar.assign(kP * ncam, 0);
     p.ivar.assign(6 * nimg, 0);
     p.cparams.assign(kP * ncam, 0.0);
-    p.num_variable = 3 * npts;
+    p.pvar.assign(npts, 1);
+    for (size_t j = 0; j < npts; ++j) {
+        if (point_const && point_const[j])
+            p.pvar[j] = 0;
+        else
+            p.num_variable += 3;
+    }
     for (size_t c = 0; c < ncam; ++c) {
         const int np = cam::num_params(pb.camera_models[c]);
         p.kc = std::max<uint32_t>(p.kc, (uint32_t)np);
@@ -127,6 +138,7 @@ inline std::string make_plan(const amc_ba_problem& pb, Plan* plan) {
     for (size_t i = 0; i < nimg; ++i) p.cimg[cat[pb.image_cameras[i]]++] = (uint32_t)i;
     return std::string();
 }
+inline std::string make_plan(const amc_ba_problem& pb, Plan* plan) { return make_plan(pb, nullptr, plan); }
 
 }  // namespace ba
 }  // namespace amc

@@ -40,6 +40,7 @@
 #include "abspose_host.h"
 #include "rigpose_host.h"
 #include "undistort_host.h"
+#include "ba_config_host.h"
 #include "ba_host.h"
 #include "reconstruction.h"
 #include "triangulator_host.h"
@@ -1463,6 +1464,225 @@ PYBIND11_MODULE(_pycolmap, m) {
         },
         "reconstruction"_a, "options"_a = BundleAdjustmentOptions(),
         "Jointly refine every pose, point and camera of the reconstruction on the GPU, in place (DESIGN.md section 15).");
+
+    // ---- BundleAdjustmentConfig and BundleAdjuster (COLMAP 3.9.1's classes under the names later pycolmap releases
+    // bind; ba_config_host.h does the work): the adjustment of a part of the model. ----
+    py::class_<BundleAdjustmentConfig>(m, "BundleAdjustmentConfig")
+        .def(py::init<>())
+        .def("num_images", &BundleAdjustmentConfig::NumImages)
+        .def("num_points", &BundleAdjustmentConfig::NumPoints)
+        .def("num_constant_cam_intrinsics", &BundleAdjustmentConfig::NumConstantCamIntrinsics)
+        .def("num_constant_cam_poses", &BundleAdjustmentConfig::NumConstantCamPoses)
+        .def("num_constant_cam_positions", &BundleAdjustmentConfig::NumConstantCamPositions)
+        .def("num_variable_points", &BundleAdjustmentConfig::NumVariablePoints)
+        .def("num_constant_points", &BundleAdjustmentConfig::NumConstantPoints)
+        .def("num_residuals", [checked_model](const BundleAdjustmentConfig& c, const PyReconstruction& r) { return c.NumResiduals(checked_model(r)); },
+             "reconstruction"_a)
+        .def("add_image", &BundleAdjustmentConfig::AddImage, "image_id"_a)
+        .def("has_image", &BundleAdjustmentConfig::HasImage, "image_id"_a)
+        .def("remove_image", &BundleAdjustmentConfig::RemoveImage, "image_id"_a)
+        .def("set_constant_cam_intrinsics", &BundleAdjustmentConfig::SetConstantCamIntrinsics, "camera_id"_a)
+        .def("set_variable_cam_intrinsics", &BundleAdjustmentConfig::SetVariableCamIntrinsics, "camera_id"_a)
+        .def("is_constant_cam_intrinsics", &BundleAdjustmentConfig::IsConstantCamIntrinsics, "camera_id"_a)
+        .def("set_constant_cam_pose", &BundleAdjustmentConfig::SetConstantCamPose, "image_id"_a)
+        .def("set_variable_cam_pose", &BundleAdjustmentConfig::SetVariableCamPose, "image_id"_a)
+        .def("has_constant_cam_pose", &BundleAdjustmentConfig::HasConstantCamPose, "image_id"_a)
+        .def("set_constant_cam_positions", &BundleAdjustmentConfig::SetConstantCamPositions, "image_id"_a, "idxs"_a)
+        .def("remove_constant_cam_positions", &BundleAdjustmentConfig::RemoveConstantCamPositions, "image_id"_a)
+        .def("has_constant_cam_positions", &BundleAdjustmentConfig::HasConstantCamPositions, "image_id"_a)
+        .def("constant_cam_positions", [](const BundleAdjustmentConfig& c, uint32_t image_id) { return c.ConstantCamPositions(image_id); }, "image_id"_a)
+        .def("add_variable_point", &BundleAdjustmentConfig::AddVariablePoint, "point3D_id"_a)
+        .def("add_constant_point", &BundleAdjustmentConfig::AddConstantPoint, "point3D_id"_a)
+        .def("has_point", &BundleAdjustmentConfig::HasPoint, "point3D_id"_a)
+        .def("has_variable_point", &BundleAdjustmentConfig::HasVariablePoint, "point3D_id"_a)
+        .def("has_constant_point", &BundleAdjustmentConfig::HasConstantPoint, "point3D_id"_a)
+        .def("remove_variable_point", &BundleAdjustmentConfig::RemoveVariablePoint, "point3D_id"_a)
+        .def("remove_constant_point", &BundleAdjustmentConfig::RemoveConstantPoint, "point3D_id"_a)
+        .def_property_readonly("image_ids", [](const BundleAdjustmentConfig& c) { return c.Images(); })
+        .def_property_readonly("variable_point3D_ids", [](const BundleAdjustmentConfig& c) { return c.VariablePoints(); })
+        .def_property_readonly("constant_point3D_ids", [](const BundleAdjustmentConfig& c) { return c.ConstantPoints(); })
+        .def("__copy__", [](const BundleAdjustmentConfig& c) { return BundleAdjustmentConfig(c); })
+        .def("__deepcopy__", [](const BundleAdjustmentConfig& c, const py::dict&) { return BundleAdjustmentConfig(c); })
+        .def(py::pickle(
+            [](const BundleAdjustmentConfig& c) {
+                return py::make_tuple(c.Images(), c.ConstantIntrinsics(), c.ConstantCamPoses(), c.AllConstantCamPositions(), c.VariablePoints(),
+                                      c.ConstantPoints());
+            },
+            [](const py::tuple& t) {
+                if (t.size() != 6) throw py::value_error("BundleAdjustmentConfig: invalid pickled state");
+                BundleAdjustmentConfig c;
+                for (uint32_t id : t[0].cast<std::set<uint32_t>>()) c.AddImage(id);
+                for (uint32_t id : t[1].cast<std::set<uint32_t>>()) c.SetConstantCamIntrinsics(id);
+                for (uint32_t id : t[2].cast<std::set<uint32_t>>()) c.SetConstantCamPose(id);
+                for (const auto& kv : t[3].cast<std::map<uint32_t, std::vector<int>>>()) c.SetConstantCamPositions(kv.first, kv.second);
+                for (uint64_t id : t[4].cast<std::set<uint64_t>>()) c.AddVariablePoint(id);
+                for (uint64_t id : t[5].cast<std::set<uint64_t>>()) c.AddConstantPoint(id);
+                return c;
+            }))
+        .def("__repr__", [](const BundleAdjustmentConfig& c) {
+            return "BundleAdjustmentConfig(num_images=" + std::to_string(c.NumImages()) + ", num_constant_cam_intrinsics=" +
+                   std::to_string(c.NumConstantCamIntrinsics()) + ", num_constant_cam_poses=" + std::to_string(c.NumConstantCamPoses()) +
+                   ", num_constant_cam_positions=" + std::to_string(c.NumConstantCamPositions()) + ", num_variable_points=" +
+                   std::to_string(c.NumVariablePoints()) + ", num_constant_points=" + std::to_string(c.NumConstantPoints()) + ")";
+        });
+    struct PyBundleAdjuster {
+        BundleAdjustmentOptions options;
+        BundleAdjustmentConfig config;
+        py::dict summary;
+    };
+    auto adjuster_flat = [checked_model](const PyBundleAdjuster& a, const PyReconstruction& r, SparseModel* model) {
+        *model = checked_model(r);
+        const BundleAdjustmentOptions& o = a.options;
+        const BaRefineFlags flags{o.refine_focal_length, o.refine_principal_point, o.refine_extra_params, o.refine_extrinsics};
+        return FlattenForBundleAdjuster(*model, a.config, flags);
+    };
+    auto adjuster_dict = [](const FlatBaConfig& fc) {
+        auto arr = [](const auto& v, py::ssize_t cols) {
+            using T = typename std::decay<decltype(v)>::type::value_type;
+            py::array_t<T> a({static_cast<py::ssize_t>(v.size()) / cols, cols});
+            std::copy(v.begin(), v.end(), a.mutable_data());
+            return a;
+        };
+        const FlatBa& f = fc.flat;
+        py::dict d;
+        d["camera_models"] = arr(f.camera_models, 1);
+        d["camera_params"] = arr(f.camera_params, 12);
+        d["camera_const"] = arr(f.camera_const, 12);
+        d["image_cameras"] = arr(f.image_cameras, 1);
+        d["qvec"] = arr(f.qvec, 4);
+        d["tvec"] = arr(f.tvec, 3);
+        d["pose_const"] = arr(f.pose_const, 6);
+        d["xyz"] = arr(f.xyz, 3);
+        d["obs_image"] = arr(f.obs_image, 1);
+        d["obs_point"] = arr(f.obs_point, 1);
+        d["obs_xy"] = arr(f.obs_xy, 2);
+        d["point_const"] = arr(fc.point_const, 1);
+        d["camera_at"] = arr(fc.camera_at, 1);
+        d["image_at"] = arr(fc.image_at, 1);
+        d["point_at"] = arr(fc.point_at, 1);
+        d["num_skipped_points"] = fc.skipped_points;
+        return d;
+    };
+    // Solve: one amc_bundle_adjust_masked call on the config's part of the checked model.  Nothing of r
+    // changes unless the call succeeds.  Without a device the call raises pycolmap_amd._capi.AmcError.
+    // solver: None, or a callable that stands in for the library (a test hook: the CPU tests pass the reference): it takes
+    // the flat problem as a dict of arrays with the options and returns camera_params, qvec, tvec, xyz and the statistics.
+    auto adjuster_solve = [adjuster_flat, adjuster_dict, update_from_model](PyBundleAdjuster& a, PyReconstruction& r, const py::object& solver) -> bool {
+        const auto t0 = std::chrono::steady_clock::now();
+        SparseModel model;
+        FlatBaConfig fc = adjuster_flat(a, r, &model);
+        FlatBa& flat = fc.flat;
+        if (flat.obs_image.empty()) return false;  // COLMAP: "No residuals" — nothing to solve
+        const BundleAdjustmentOptions& o = a.options;
+        amc_ba_opts opts;
+        amc_ba_opts_default(&opts);
+        opts.loss_function_type = static_cast<int32_t>(o.loss_function_type);
+        opts.loss_function_scale = o.loss_function_scale;
+        opts.max_num_iterations = o.solver_options.max_num_iterations;
+        opts.max_linear_solver_iterations = o.solver_options.max_linear_solver_iterations;
+        opts.max_num_consecutive_invalid_steps = o.solver_options.max_num_consecutive_invalid_steps;
+        opts.function_tolerance = o.solver_options.function_tolerance;
+        opts.gradient_tolerance = o.solver_options.gradient_tolerance;
+        opts.parameter_tolerance = o.solver_options.parameter_tolerance;
+        static const char* const kTermination[] = {"FUNCTION_TOLERANCE", "PARAMETER_TOLERANCE", "GRADIENT_TOLERANCE", "MAX_ITERATIONS",
+                                                   "MIN_RADIUS", "INVALID_STEPS", "NOTHING_TO_REFINE"};
+        py::dict st;
+        st["call"] = "BundleAdjuster.solve";
+        st["num_images"] = flat.image_cameras.size();
+        st["num_points"] = fc.point_at.size();
+        st["num_observations"] = flat.obs_image.size();
+        st["num_filtered_observations"] = 0;
+        st["num_skipped_points"] = fc.skipped_points;
+        st["num_constant_points"] = fc.num_constant_points;
+        if (!solver.is_none()) {
+            py::dict d = adjuster_dict(fc);
+            py::dict od;
+            od["loss_function_type"] = opts.loss_function_type;
+            od["loss_function_scale"] = opts.loss_function_scale;
+            od["max_num_iterations"] = opts.max_num_iterations;
+            od["max_linear_solver_iterations"] = opts.max_linear_solver_iterations;
+            od["max_num_consecutive_invalid_steps"] = opts.max_num_consecutive_invalid_steps;
+            od["function_tolerance"] = opts.function_tolerance;
+            od["gradient_tolerance"] = opts.gradient_tolerance;
+            od["parameter_tolerance"] = opts.parameter_tolerance;
+            d["options"] = od;
+            const py::dict out = solver(d);
+            const auto cp = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(out["camera_params"]);
+            const auto q = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(out["qvec"]);
+            const auto t = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(out["tvec"]);
+            const auto X = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(out["xyz"]);
+            if (!cp || !q || !t || !X || static_cast<size_t>(cp.size()) != flat.camera_params.size() || static_cast<size_t>(q.size()) != flat.qvec.size() ||
+                static_cast<size_t>(t.size()) != flat.tvec.size() || static_cast<size_t>(X.size()) != flat.xyz.size())
+                throw py::value_error("BundleAdjuster.solve: the solver's result does not have the problem's shape");
+            std::copy(cp.data(), cp.data() + cp.size(), flat.camera_params.begin());
+            std::copy(q.data(), q.data() + q.size(), flat.qvec.begin());
+            std::copy(t.data(), t.data() + t.size(), flat.tvec.begin());
+            std::copy(X.data(), X.data() + X.size(), flat.xyz.begin());
+            for (const char* k : {"num_variable_parameters", "initial_cost", "final_cost", "num_successful_steps", "num_unsuccessful_steps",
+                                  "num_pcg_iterations", "termination"})
+                st[k] = out[k];
+            st["device_ms"] = 0.0;
+            st["kernel_ms"] = 0.0;
+        } else {
+            amc_ba_problem pb = flat.Problem();
+            amc_ba_result res{};
+            int rc = AMC_OK;
+            std::string err;
+            {
+                py::gil_scoped_release release;
+                EstimatorCtx& E = TheEstimatorCtx();
+                std::lock_guard<std::mutex> lock(E.mu);
+                amc_ctx* ctx = nullptr;
+                try {
+                    ctx = E.Get();
+                } catch (const std::runtime_error& e) {
+                    rc = AMC_E_HIP;
+                    err = e.what();
+                }
+                if (ctx) {
+                    rc = amc_bundle_adjust_masked(ctx, &pb, fc.point_const.data(), &opts, &res);
+                    if (rc != AMC_OK) err = std::string("amc_bundle_adjust_masked: ") + amc_last_error();
+                }
+            }
+            if (rc == AMC_E_INVALID) throw std::invalid_argument(err);
+            if (rc != AMC_OK) {
+                const py::object cls = py::module_::import("pycolmap_amd._capi").attr("AmcError");
+                const py::object exc = cls(rc, err);
+                PyErr_SetObject(cls.ptr(), exc.ptr());
+                throw py::error_already_set();
+            }
+            st["num_variable_parameters"] = res.num_variable_parameters;
+            st["initial_cost"] = res.initial_cost;
+            st["final_cost"] = res.final_cost;
+            st["num_successful_steps"] = res.num_successful_steps;
+            st["num_unsuccessful_steps"] = res.num_unsuccessful_steps;
+            st["num_pcg_iterations"] = res.num_pcg_iterations;
+            st["termination"] = kTermination[res.termination >= 0 && res.termination < 7 ? res.termination : 5];
+            st["device_ms"] = res.device_ms;
+            st["kernel_ms"] = res.kernel_ms;
+        }
+        WriteBackBundleAdjuster(fc, &model);
+        update_from_model(r, model);
+        st["host_ms"] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - st["device_ms"].cast<double>();
+        a.summary = st;
+        py::module_::import("pycolmap_amd._pycolmap").attr("_last_stats") = st;
+        return true;
+    };
+    py::class_<PyBundleAdjuster>(m, "BundleAdjuster")
+        .def(py::init([](const BundleAdjustmentOptions& options, const BundleAdjustmentConfig& config) {
+                 return PyBundleAdjuster{options, config, py::dict()};
+             }), "options"_a, "config"_a)
+        .def("solve", [adjuster_solve](PyBundleAdjuster& a, PyReconstruction& r) { return adjuster_solve(a, r, py::none()); }, "reconstruction"_a,
+             "Refine the config's part of the reconstruction on the GPU, in place (DESIGN.md 15.12).  False when the\n"
+             "config gives no residual.")
+        .def("_solve_with", adjuster_solve, "reconstruction"_a, "solver"_a, "solve with a callable in the library's place (test hook).")
+        .def("_problem", [adjuster_flat, adjuster_dict](const PyBundleAdjuster& a, const PyReconstruction& r) {
+                 SparseModel model;
+                 return adjuster_dict(adjuster_flat(a, r, &model));
+             }, "reconstruction"_a, "The flat problem solve hands to amc_bundle_adjust_masked (test hook).")
+        .def_property_readonly("options", [](const PyBundleAdjuster& a) { return a.options; })
+        .def_property_readonly("config", [](const PyBundleAdjuster& a) { return a.config; })
+        .def_property_readonly("summary", [](const PyBundleAdjuster& a) { return a.summary; });
 
     // ---- CorrespondenceGraph and IncrementalTriangulator (the reference's pycolmap/scene/correspondence_graph.h and
     // pycolmap/sfm/incremental_triangulator.h; correspondence_graph.h, triangulator_host.h) ----

@@ -11,6 +11,15 @@ least_squares on a reduced scene (--small-points), and a bit-for-bit check of th
 scene.  Prints one JSON line; --out writes it to a file as well.
 
     python tools/bundle_adjustment_bench.py [--reps 3] [--out profiles/bundle_adjustment/bundle_adjustment_bench.json]
+
+--local runs the local leg instead: the same kind of scene as a Reconstruction (--local-images,
+--local-points), a BundleAdjustmentConfig of --local-config neighbouring images in the middle of the path, and
+BundleAdjuster.solve on it: the points those images share with the rest of the model are constant.  Reports kernel, copy
+(device minus kernel) and host milliseconds of the best of --reps solves, the share of the host time that the set-up
+(model conversion, check and flattening, timed on its own through BundleAdjuster._problem) takes, and the single-threaded
+CPU reference (tests/ba_config_ref) on the same flat problem with a bit-for-bit check.
+
+    python tools/bundle_adjustment_bench.py --local [--out profiles/bundle_adjustment_config/local_bench.json]
 """
 from __future__ import annotations
 
@@ -65,6 +74,63 @@ def path_scene(nimg, npts, seed=0, noise=0.5):
             oi.astype(np.uint32), op.astype(np.uint32), xy)
 
 
+def local_leg(a):
+    """BundleAdjuster.solve on a few neighbouring images of a large model"""
+    import copy
+
+    import ba_cases
+    import ba_config_cases as cc
+    import ba_config_ref_lib as cref
+    import pycolmap_amd as pc
+    args = path_scene(a.local_images, a.local_points, seed=2)
+    sc = dict(models=[2], camera_params=args[1], image_cameras=args[3], qvec=args[4], tvec=args[5], xyz=args[7],
+              obs_image=args[8], obs_point=args[9], obs_xy=args[10])
+    t0 = time.perf_counter()
+    rec = ba_cases.reconstruction(sc)
+    build_ms = 1e3 * (time.perf_counter() - t0)
+    cfg = pc.BundleAdjustmentConfig()
+    first = a.local_images // 2 - a.local_config // 2
+    for i in range(first, first + a.local_config):
+        cfg.add_image(i + 1)
+    o = pc.BundleAdjustmentOptions()
+    o.solver_options.max_num_iterations = a.iterations
+    adj = pc.BundleAdjuster(o, cfg)
+    t0 = time.perf_counter()
+    d = adj._problem(rec)
+    setup_ms = 1e3 * (time.perf_counter() - t0)
+    pm = np.asarray(d["point_const"]).reshape(-1)
+    best = None
+    pc.BundleAdjuster(o, cfg).solve(copy.deepcopy(rec))  # warm-up
+    for _ in range(a.reps):
+        r = copy.deepcopy(rec)
+        t0 = time.perf_counter()
+        assert adj.solve(r)
+        st = dict(adj.summary)
+        st["wall_ms"] = 1e3 * (time.perf_counter() - t0)
+        if best is None or st["device_ms"] + st["host_ms"] < best[0]["device_ms"] + best[0]["host_ms"]:
+            best = (st, r)
+    st, solved = best
+    t0 = time.perf_counter()
+    want = cref.bundle_adjust(*cc.flat_args(d), options=dict(max_num_iterations=a.iterations), point_const=pm)
+    ref_ms = 1e3 * (time.perf_counter() - t0)
+    by_ref = copy.deepcopy(rec)
+    assert pc.BundleAdjuster(o, cfg)._solve_with(by_ref, lambda _d: want)
+    return {
+        "workload": {"model_images": a.local_images, "model_points": a.local_points, "model_observations": len(args[8]),
+                     "config_images": a.local_config, "problem_images": st["num_images"], "problem_points": st["num_points"],
+                     "constant_points": st["num_constant_points"], "problem_observations": st["num_observations"],
+                     "variable_parameters": st["num_variable_parameters"],
+                     "lm_iterations": st["num_successful_steps"] + st["num_unsuccessful_steps"]},
+        "initial_cost": st["initial_cost"], "final_cost": st["final_cost"], "termination": st["termination"],
+        "pcg_iterations": st["num_pcg_iterations"],
+        "kernel_ms": st["kernel_ms"], "copy_ms": st["device_ms"] - st["kernel_ms"], "host_ms": st["host_ms"],
+        "wall_ms": st["wall_ms"], "setup_ms": setup_ms, "setup_share_of_host": setup_ms / st["host_ms"] if st["host_ms"] else None,
+        "reconstruction_build_ms": build_ms,
+        "cpu_reference_ms": ref_ms, "cpu_reference_cost": want["final_cost"],
+        "gpu_equals_reference_bit_for_bit": cc.model_bits(solved) == cc.model_bits(by_ref),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=300)
@@ -74,7 +140,18 @@ def main():
     ap.add_argument("--small-points", type=int, default=400)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default="")
+    ap.add_argument("--local", action="store_true", help="the local leg: BundleAdjuster.solve on a few images of a large model")
+    ap.add_argument("--local-images", type=int, default=300)
+    ap.add_argument("--local-points", type=int, default=30000)
+    ap.add_argument("--local-config", type=int, default=5)
     a = ap.parse_args()
+    if a.local:
+        line = json.dumps(local_leg(a))
+        print(line)
+        if a.out:
+            Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(a.out).write_text(line + "\n")
+        return
 
     import ba_cases
     import ba_ref_lib as ref

@@ -4,10 +4,12 @@
 // "One way" = COLMAP's FindBestMatchesOneWayBruteForce: for every row of
 // image X, the best dot product against all rows of image Y (lowest index among ties) and the
 // second-largest value with multiplicity.  The host runs it twice per pair:
-//   MODE 0  X = image 1 (all rows)            , Y = image 2  -> row table
+//   MODE 0  X = image 1 (all rows)            , Y = image 2  -> accept bits, and the row table's 16-row X tiles that
+//           hold a set bit: every reader of the row table tests the row's bit first (resolve_index* side 0,
+//           select_candidates, finalize)
 //   MODE 1  X = image 2 (candidate rows only) , Y = image 1  -> column table, lazily: only the
-//           columns some accepted row points at (select_candidates_kernel); the cross check
-//           never looks at any other column, so results equal COLMAP's full transposed scan.
+//           columns some accepted row points at (select_candidates_kernel), every one of them stored; the cross
+//           check never looks at any other column, so results equal COLMAP's full transposed scan.
 // The kernel reports the best VALUE, the 32-row TILE of Y that holds it, and the largest value
 // OUTSIDE the best's unit, which is that tile (a lower bound of the second); resolve_index_kernel
 // (match_common.hip) turns the tile into the exact lowest index and completes the second value
@@ -51,11 +53,13 @@
 // fill a workgroup two at a time; and the reverse scan's candidate lists (known only on the
 // device: the packing kernels read cand_cnt) are packed just as tightly.
 //
-// Shape.  One workgroup per item (dynamic queue; items in Y order so co-resident workgroups stream
-// the same image out of L2; the next item's descriptor is fetched while the current one is
-// scanned): 512 threads, a segment (eight resident 16-row X tiles) per wave, 2 waves per SIMD.  MODE 0 compiles to
-// exactly 256 VGPRs, the most two waves per SIMD allow (MODE 1: 238), without scratch: anything added to the loop's
-// live state will spill - check -Rpass-analysis=kernel-resource-usage after every change.
+// Shape.  One workgroup per item (dynamic queue, one ticket per item, taken at the top of the item before; items in
+// Y order so co-resident workgroups stream the same image out of L2; the next item's descriptor is fetched while the
+// current one is scanned): 512 threads, a segment (eight resident 16-row X tiles) per wave, 2 waves per SIMD.  MODE 0
+// compiles to exactly 256 VGPRs, the most two waves per SIMD allow (MODE 1: 236), without scratch: anything added to
+// the loop's live state will spill - check -Rpass-analysis=kernel-resource-usage after every change
+// (profiles/boundary/kernel_resource_usage.txt).  Taking the ticket two items ahead and warming the next item's X
+// rows in L2 were both built and measured, and neither paid (profiles/boundary/README.md).
 // Y streams through LDS in 256-row chunks by direct-to-LDS DMA, three buffers, the pieces of chunk c+2
 // issued one per two steps of chunk c, one barrier per chunk; the prepared arena is pre-swizzled
 // (arena_swizzle, amc_internal.h) so the linear DMA image is bank-conflict-free for
@@ -539,24 +543,34 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
                     b = ow ? ob : b;
                 }
                 bool acc_bit = false;
-                if (lq == 0 && kl < cnt) {
+                const bool live = lq == 0 && kl < cnt;
+                Top2 o;
+                o.best_v = (uint32_t)(b + ex[xt]);
+                o.best_idx = o.best_v ? (uint32_t)t : 0xFFFFFFFFu;  // TILE of the best
+                o.second_v = (uint32_t)(s + ex[xt]);
+                o.pad = 0;
+                // a larger second only ever rejects: rows failing now can be forgotten
+                // (scan_accept.h: thresholds instead of acos; a superset of what the exact tests keep)
+                if (MODE == 0) acc_bit = live && scan_may_accept(sa, o.best_v, o.second_v);
+                const uint32_t bits = MODE == 0 ? (uint32_t)__ballot(acc_bit) : 0u;  // (lanes 0..15: the X tile's rows)
+                // MODE 0 stores what is read: every reader of the row table tests the row's accept bit first
+                // (resolve_index* side 0, select_candidates, finalize), so a row the scan rejects here is never looked
+                // at.  The unit is the X tile - 16 rows, 256 contiguous bytes - stored whole if any of its rows is
+                // accepted: on a sparse set (a few accepted rows per pair) next to nothing is written, 8 GB per
+                // headline step less, and on a dense one (a third of the rows accepted) the stores stay the full lines
+                // they were - 16-byte records scattered one in three cost the scan 0.8 % there.  MODE 1 stores every
+                // candidate row: finalize reads cols[j] without a mask.
+                if (live && (MODE == 1 || bits != 0)) {
                     Top2* out = reinterpret_cast<Top2*>(const_cast<char*>(dptr(dv, kDOut)));
                     int row = kl;  // MODE 0: `out` points at the segment's first row
                     if (MODE == 1) row = (int)reinterpret_cast<const uint32_t*>(dptr(dv, kDList))[kl];
-                    Top2 o;
-                    o.best_v = (uint32_t)(b + ex[xt]);
-                    o.best_idx = o.best_v ? (uint32_t)t : 0xFFFFFFFFu;  // TILE of the best
-                    o.second_v = (uint32_t)(s + ex[xt]);
-                    o.pad = 0;
                     out[row] = o;
-                    // a larger second only ever rejects: rows failing now can be forgotten
-                    // (scan_accept.h: thresholds instead of acos; a superset of what the exact tests keep)
-                    if (MODE == 0) acc_bit = scan_may_accept(sa, o.best_v, o.second_v);
                 }
-                if (MODE == 0) {  // accept bits of 32 rows = two X tiles (lanes 0..15 of each)
-                    const uint32_t bits = (uint32_t)__ballot(acc_bit);
+                if (MODE == 0) {  // accept bits of 32 rows = two X tiles
                     if (xt & 1) {
-                        if (lane == 0) accmask[(uint32_t)dword(dv, kDAccword) + (xt >> 1)] = bits_lo | (bits << 16);
+                        // a word without a bit stays as the batch's memset left it (enqueue_scan zeroes the mask)
+                        const uint32_t word = bits_lo | (bits << 16);
+                        if (lane == 0 && word != 0) accmask[(uint32_t)dword(dv, kDAccword) + (xt >> 1)] = word;
                     } else {
                         bits_lo = bits;
                     }

@@ -38,6 +38,8 @@ EXPORTED_SYMBOLS = [
     "amc_ba_opts_default", "amc_bundle_adjust", "amc_bundle_adjust_masked",
     "amc_filter_opts_default", "amc_filter_points3d", "amc_filter_result_free",
     "amc_triobs_opts_default", "amc_triangulate_observations", "amc_triobs_result_free",
+    "amc_complete_opts_default", "amc_complete_tracks", "amc_complete_result_free",
+    "amc_merge_opts_default", "amc_merge_tracks", "amc_merge_result_free",
 ]
 COMM_ID_BYTES = 128
 RANSAC_F, RANSAC_H, RANSAC_E = 0, 1, 2
@@ -415,6 +417,125 @@ def triobs_inputs(camera_models, camera_params, image_cameras, qvec, tvec, item_
     return models, prm, icam.astype(np.uint32), q, t, off.astype(np.uint64), ci.astype(np.uint32), xy, has, X, two
 
 
+class CompleteOpts(C.Structure):  # amc_complete_opts (include/amc_tracks.h)
+    _fields_ = [("complete_max_reproj_error", C.c_double), ("reserved", C.c_double)]
+
+
+class CompleteProblem(C.Structure):  # amc_complete_problem
+    _fields_ = [("num_cameras", C.c_size_t), ("camera_models", C.c_void_p), ("camera_params", C.c_void_p),
+                ("num_images", C.c_size_t), ("image_cameras", C.c_void_p), ("qvec", C.c_void_p), ("tvec", C.c_void_p),
+                ("num_items", C.c_size_t), ("item_xyz", C.c_void_p), ("item_offsets", C.c_void_p),
+                ("cand_image", C.c_void_p), ("cand_xy", C.c_void_p)]
+
+
+class CompleteResult(C.Structure):  # amc_complete_result
+    _fields_ = [("num_items", C.c_uint64), ("num_candidates", C.c_uint64), ("num_passed", C.c_uint64),
+                ("cand_sq_error", C.POINTER(C.c_double)), ("cand_pass", C.POINTER(C.c_uint8)),
+                ("num_batches", C.c_uint32), ("reserved", C.c_uint32), ("host_ms", C.c_double),
+                ("device_ms", C.c_double), ("kernel_ms", C.c_double), ("copy_ms", C.c_double),
+                ("alloc_ms", C.c_double)]
+
+
+def complete_inputs(camera_models, camera_params, image_cameras, qvec, tvec, item_xyz, item_offsets, cand_image, cand_xy):
+    """The flat problem of amc_complete_tracks as contiguous arrays (copies: the caller's arrays are not touched):
+    models (C,) int32, params (C, 12), image_cameras (I,) uint32, qvec (I, 4) x y z w, tvec (I, 3), item_xyz (T, 3),
+    item_offsets (T + 1,) uint64, cand_image (N,) uint32, cand_xy (N, 2)."""
+    who = "complete_tracks"
+    models = np.array(camera_models, dtype=np.int32).reshape(-1)
+    if len(camera_params) != models.size:
+        raise ValueError(f"{who}: {models.size} camera models, {len(camera_params)} parameter sets")
+    prm = np.zeros((models.size, 12), np.float64)
+    for i, p in enumerate(camera_params):
+        p = np.asarray(p, dtype=np.float64).reshape(-1)
+        if p.size > 12:
+            raise ValueError(f"{who}: camera {i} has {p.size} parameters (at most 12)")
+        prm[i, :p.size] = p
+    icam = np.array(image_cameras, dtype=np.int64).reshape(-1)
+    q = np.array(qvec, dtype=np.float64).reshape(-1, 4)
+    t = np.array(tvec, dtype=np.float64).reshape(-1, 3)
+    X = np.array(item_xyz, dtype=np.float64).reshape(-1, 3)
+    off = np.array(item_offsets, dtype=np.int64).reshape(-1)
+    ci = np.array(cand_image, dtype=np.int64).reshape(-1)
+    xy = np.array(cand_xy, dtype=np.float64).reshape(-1, 2)
+    if q.shape[0] != icam.size or t.shape[0] != icam.size or off.size != X.shape[0] + 1 or xy.shape[0] != ci.size:
+        raise ValueError(f"{who}: {icam.size} images by image_cameras, {q.shape[0]} rotations, {t.shape[0]} translations; "
+                         f"{X.shape[0]} items, {off.size} offsets; {ci.size} candidates by cand_image, {xy.shape[0]} pixels")
+    if off.min() < 0 or int(off[-1]) != ci.size:
+        raise ValueError(f"{who}: item_offsets ends at {int(off[-1])}, {ci.size} candidates")
+    for name, a in (("image_cameras", icam), ("cand_image", ci)):
+        if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+            raise ValueError(f"{who}: {name} has an index outside 0 .. 2^32 - 1")
+    return models, prm, icam.astype(np.uint32), q, t, X, off.astype(np.uint64), ci.astype(np.uint32), xy
+
+
+class MergeOpts(C.Structure):  # amc_merge_opts (include/amc_tracks.h)
+    _fields_ = [("merge_max_reproj_error", C.c_double), ("reserved", C.c_double)]
+
+
+class MergeProblem(C.Structure):  # amc_merge_problem
+    _fields_ = [("num_cameras", C.c_size_t), ("camera_models", C.c_void_p), ("camera_params", C.c_void_p),
+                ("num_images", C.c_size_t), ("image_cameras", C.c_void_p), ("qvec", C.c_void_p), ("tvec", C.c_void_p),
+                ("num_components", C.c_size_t), ("comp_point_offsets", C.c_void_p), ("comp_root_offsets", C.c_void_p),
+                ("roots", C.c_void_p), ("point_xyz", C.c_void_p), ("point_obs_offsets", C.c_void_p),
+                ("obs_image", C.c_void_p), ("obs_xy", C.c_void_p), ("obs_corr_offsets", C.c_void_p),
+                ("corr_obs", C.c_void_p)]
+
+
+class MergeResult(C.Structure):  # amc_merge_result
+    _fields_ = [("num_components", C.c_uint64), ("num_points", C.c_uint64), ("num_observations", C.c_uint64),
+                ("num_roots", C.c_uint64), ("num_merges", C.c_uint64), ("num_pairs_tried", C.c_uint64),
+                ("root_return", C.POINTER(C.c_uint32)), ("root_merge_offsets", C.POINTER(C.c_uint64)),
+                ("merge_current", C.POINTER(C.c_uint32)), ("merge_other", C.POINTER(C.c_uint32)),
+                ("merge_xyz", C.POINTER(C.c_double)), ("num_batches", C.c_uint32), ("reserved", C.c_uint32),
+                ("host_ms", C.c_double), ("device_ms", C.c_double), ("kernel_ms", C.c_double), ("copy_ms", C.c_double),
+                ("alloc_ms", C.c_double)]
+
+
+def merge_inputs(camera_models, camera_params, image_cameras, qvec, tvec, comp_point_offsets, comp_root_offsets, roots,
+                 point_xyz, point_obs_offsets, obs_image, obs_xy, obs_corr_offsets, corr_obs):
+    """The flat problem of amc_merge_tracks as contiguous arrays (copies: the caller's arrays are not touched): models
+    (C,) int32, params (C, 12), image_cameras (I,) uint32, qvec (I, 4) x y z w, tvec (I, 3), comp_point_offsets and
+    comp_root_offsets (K + 1,) uint64, roots (R,) uint32, point_xyz (P, 3), point_obs_offsets (P + 1,) uint64, obs_image
+    (N,) uint32, obs_xy (N, 2), obs_corr_offsets (N + 1,) uint64, corr_obs (M,) uint32."""
+    who = "merge_tracks"
+    models = np.array(camera_models, dtype=np.int32).reshape(-1)
+    if len(camera_params) != models.size:
+        raise ValueError(f"{who}: {models.size} camera models, {len(camera_params)} parameter sets")
+    prm = np.zeros((models.size, 12), np.float64)
+    for i, p in enumerate(camera_params):
+        p = np.asarray(p, dtype=np.float64).reshape(-1)
+        if p.size > 12:
+            raise ValueError(f"{who}: camera {i} has {p.size} parameters (at most 12)")
+        prm[i, :p.size] = p
+    icam = np.array(image_cameras, dtype=np.int64).reshape(-1)
+    q = np.array(qvec, dtype=np.float64).reshape(-1, 4)
+    t = np.array(tvec, dtype=np.float64).reshape(-1, 3)
+    cpo = np.array(comp_point_offsets, dtype=np.int64).reshape(-1)
+    cro = np.array(comp_root_offsets, dtype=np.int64).reshape(-1)
+    rt = np.array(roots, dtype=np.int64).reshape(-1)
+    X = np.array(point_xyz, dtype=np.float64).reshape(-1, 3)
+    poo = np.array(point_obs_offsets, dtype=np.int64).reshape(-1)
+    oi = np.array(obs_image, dtype=np.int64).reshape(-1)
+    xy = np.array(obs_xy, dtype=np.float64).reshape(-1, 2)
+    oco = np.array(obs_corr_offsets, dtype=np.int64).reshape(-1)
+    co = np.array(corr_obs, dtype=np.int64).reshape(-1)
+    if (q.shape[0] != icam.size or t.shape[0] != icam.size or cpo.size < 1 or cro.size != cpo.size or poo.size != X.shape[0] + 1
+            or xy.shape[0] != oi.size or oco.size != oi.size + 1):
+        raise ValueError(f"{who}: {icam.size} images by image_cameras, {q.shape[0]} rotations, {t.shape[0]} translations; "
+                         f"{cpo.size} and {cro.size} component offsets; {X.shape[0]} points, {poo.size} offsets; {oi.size} "
+                         f"observations by obs_image, {xy.shape[0]} pixels, {oco.size} offsets")
+    for name, off, n in (("comp_point_offsets", cpo, X.shape[0]), ("comp_root_offsets", cro, rt.size),
+                         ("point_obs_offsets", poo, oi.size), ("obs_corr_offsets", oco, co.size)):
+        if off.min() < 0 or int(off[-1]) != n:
+            raise ValueError(f"{who}: {name} ends at {int(off[-1])}, {n} elements")
+    for name, a in (("image_cameras", icam), ("roots", rt), ("obs_image", oi), ("corr_obs", co)):
+        if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+            raise ValueError(f"{who}: {name} has an index outside 0 .. 2^32 - 1")
+    u32, u64 = np.uint32, np.uint64
+    return (models, prm, icam.astype(u32), q, t, cpo.astype(u64), cro.astype(u64), rt.astype(u32), X, poo.astype(u64),
+            oi.astype(u32), xy, oco.astype(u64), co.astype(u32))
+
+
 class RigPoseResult(C.Structure):  # amc_rigpose_result (include/amc_rigpose.h)
     _fields_ = [("nqueries", C.c_size_t), ("ncorr", C.c_size_t), ("success", C.POINTER(C.c_uint8)),
                 ("qvec", C.POINTER(C.c_double)), ("tvec", C.POINTER(C.c_double)),
@@ -708,6 +829,21 @@ def load() -> C.CDLL:
         lib.amc_triangulate_observations.restype = C.c_int
         lib.amc_triobs_result_free.argtypes = [C.POINTER(TriobsResult)]
         lib.amc_triobs_result_free.restype = None
+    if hasattr(lib, "amc_complete_tracks"):  # (absent from a library built from an older revision)
+        lib.amc_complete_opts_default.argtypes = [C.POINTER(CompleteOpts)]
+        lib.amc_complete_opts_default.restype = None
+        lib.amc_complete_tracks.argtypes = [C.c_void_p, C.POINTER(CompleteProblem), C.POINTER(CompleteOpts),
+                                            C.POINTER(CompleteResult)]
+        lib.amc_complete_tracks.restype = C.c_int
+        lib.amc_complete_result_free.argtypes = [C.POINTER(CompleteResult)]
+        lib.amc_complete_result_free.restype = None
+    if hasattr(lib, "amc_merge_tracks"):  # (absent from a library built from an older revision)
+        lib.amc_merge_opts_default.argtypes = [C.POINTER(MergeOpts)]
+        lib.amc_merge_opts_default.restype = None
+        lib.amc_merge_tracks.argtypes = [C.c_void_p, C.POINTER(MergeProblem), C.POINTER(MergeOpts), C.POINTER(MergeResult)]
+        lib.amc_merge_tracks.restype = C.c_int
+        lib.amc_merge_result_free.argtypes = [C.POINTER(MergeResult)]
+        lib.amc_merge_result_free.restype = None
     if hasattr(lib, "amc_triangulate_tracks"):  # (absent from a library built from an older revision)
         lib.amc_tri_opts_default.argtypes = [C.POINTER(TriOpts)]
         lib.amc_tri_opts_default.restype = None
@@ -1212,6 +1348,66 @@ class Context:
                    "copy_ms": res.copy_ms, "alloc_ms": res.alloc_ms}
         finally:
             self._lib.amc_triobs_result_free(C.byref(res))
+        return out
+
+    def complete_tracks(self, camera_models, camera_params, image_cameras, qvec, tvec, item_xyz, item_offsets, cand_image,
+                        cand_xy, complete_max_reproj_error=4.0):
+        """amc_complete_tracks: the error test of COLMAP's CompleteTracks for every candidate observation of a batch of
+        points.  camera_models (C,), camera_params: C parameter vectors; image_cameras (I,),
+        qvec (I, 4) x y z w, tvec (I, 3); item_xyz (T, 3) the points; item_offsets (T + 1,) CSR over the candidates;
+        cand_image (N,), cand_xy (N, 2) pixels.  The threshold is in pixels.  The inputs are not modified.  Returns a
+        dict: cand_sq_error (N,), cand_pass (N,) bool, num_passed, num_batches, host_ms, device_ms, kernel_ms, copy_ms,
+        alloc_ms."""
+        models, prm, icam, q, t, X, off, ci, xy = complete_inputs(camera_models, camera_params, image_cameras, qvec, tvec,
+                                                                  item_xyz, item_offsets, cand_image, cand_xy)
+        o = CompleteOpts(float(complete_max_reproj_error), 0.0)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        pb = CompleteProblem(models.size, ptr(models), ptr(prm), icam.size, ptr(icam), ptr(q), ptr(t), off.size - 1,
+                             ptr(X), ptr(off), ptr(ci), ptr(xy))
+        res = CompleteResult()
+        _check(self._lib.amc_complete_tracks(self._h, C.byref(pb), C.byref(o), C.byref(res)))
+        try:
+            n = ci.size
+            a = lambda p, k: np.ctypeslib.as_array(p, (max(k, 1),))[:k].copy()  # noqa: E731
+            out = {"cand_sq_error": a(res.cand_sq_error, n), "cand_pass": a(res.cand_pass, n).astype(bool),
+                   "num_passed": int(res.num_passed), "num_batches": int(res.num_batches), "host_ms": res.host_ms,
+                   "device_ms": res.device_ms, "kernel_ms": res.kernel_ms, "copy_ms": res.copy_ms,
+                   "alloc_ms": res.alloc_ms}
+        finally:
+            self._lib.amc_complete_result_free(C.byref(res))
+        return out
+
+    def merge_tracks(self, camera_models, camera_params, image_cameras, qvec, tvec, comp_point_offsets, comp_root_offsets,
+                     roots, point_xyz, point_obs_offsets, obs_image, obs_xy, obs_corr_offsets, corr_obs,
+                     merge_max_reproj_error=4.0):
+        """amc_merge_tracks: COLMAP's MergeTracks for the roots of a batch of connected components of points (DESIGN.md
+        section 18).  The cameras and images as in complete_tracks; comp_point_offsets / comp_root_offsets (K + 1,) CSRs
+        over the points / the roots; roots (R,) point indices; point_xyz (P, 3); point_obs_offsets (P + 1,) CSR over
+        the observations in track order; obs_image (N,), obs_xy (N, 2) pixels; obs_corr_offsets (N + 1,) CSR over
+        corr_obs (M,), the corresponding observations that carry a point.  The threshold is in pixels.  The inputs are
+        not modified.  Returns a dict: root_return (R,), root_merge_offsets (R + 1,), merge_current and merge_other
+        (S,) component slots, merge_xyz (S, 3), num_merges, num_pairs_tried, num_batches, host_ms, device_ms, kernel_ms,
+        copy_ms, alloc_ms."""
+        a = merge_inputs(camera_models, camera_params, image_cameras, qvec, tvec, comp_point_offsets, comp_root_offsets,
+                         roots, point_xyz, point_obs_offsets, obs_image, obs_xy, obs_corr_offsets, corr_obs)
+        models, prm, icam, q, t, cpo, cro, rt, X, poo, oi, xy, oco, co = a
+        o = MergeOpts(float(merge_max_reproj_error), 0.0)
+        ptr = lambda v: v.ctypes.data_as(C.c_void_p)  # noqa: E731
+        pb = MergeProblem(models.size, ptr(models), ptr(prm), icam.size, ptr(icam), ptr(q), ptr(t), cpo.size - 1, ptr(cpo),
+                          ptr(cro), ptr(rt), ptr(X), ptr(poo), ptr(oi), ptr(xy), ptr(oco), ptr(co))
+        res = MergeResult()
+        _check(self._lib.amc_merge_tracks(self._h, C.byref(pb), C.byref(o), C.byref(res)))
+        try:
+            nr, nm = rt.size, int(res.num_merges)
+            arr = lambda p, k: np.ctypeslib.as_array(p, (max(k, 1),))[:k].copy()  # noqa: E731
+            out = {"root_return": arr(res.root_return, nr), "root_merge_offsets": arr(res.root_merge_offsets, nr + 1),
+                   "merge_current": arr(res.merge_current, nm), "merge_other": arr(res.merge_other, nm),
+                   "merge_xyz": arr(res.merge_xyz, 3 * nm).reshape(nm, 3), "num_merges": nm,
+                   "num_pairs_tried": int(res.num_pairs_tried), "num_batches": int(res.num_batches),
+                   "host_ms": res.host_ms, "device_ms": res.device_ms, "kernel_ms": res.kernel_ms,
+                   "copy_ms": res.copy_ms, "alloc_ms": res.alloc_ms}
+        finally:
+            self._lib.amc_merge_result_free(C.byref(res))
         return out
 
     def estimate_rig_absolute_poses(self, offsets, camera_offsets, camera_models, camera_params, cams_from_rig,

@@ -14,7 +14,8 @@ scope exists;
 anything else raises AttributeError naming this package, so that a script reaching for `import_images`, SfM or MVS
 fails at the attribute, not later.  Track completion and merging (`complete_tracks`,
 `complete_all_tracks`, `merge_tracks`, `merge_all_tracks`: module-level functions that take the `IncrementalTriangulator`
-first) resolve too."""
+first) resolve too, and so does `retriangulate(triangulator, options)` for under-reconstructed image
+pairs."""
 import pycolmap_amd as _impl
 from pycolmap_amd import *  # noqa: F401,F403
 from pycolmap_amd import __version__  # noqa: F401
@@ -25,4 +26,4 @@ globals().update({n: getattr(_impl, n) for n in _PUBLIC})
 
 def __getattr__(name):
     raise AttributeError(f"pycolmap.{name} is outside pycolmap_amd's scope (SIFT feature extraction, exhaustive / sequential "
-                         f"matching + two-view verification, known-pose triangulation, absolute pose, image undistortion, bundle adjustment of a minimal Reconstruction behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}; also in scope: point filtering, and incremental triangulation of an image (CorrespondenceGraph, IncrementalTriangulator.triangulate_image), and the adjustment of a part of the model (BundleAdjustmentConfig, BundleAdjuster.solve), and track completion and merging (complete_tracks, complete_all_tracks, merge_tracks, merge_all_tracks with the triangulator as first argument)")
+                         f"matching + two-view verification, known-pose triangulation, absolute pose, image undistortion, bundle adjustment of a minimal Reconstruction behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}; also in scope: point filtering, and incremental triangulation of an image (CorrespondenceGraph, IncrementalTriangulator.triangulate_image), and the adjustment of a part of the model (BundleAdjustmentConfig, BundleAdjuster.solve), and track completion and merging (complete_tracks, complete_all_tracks, merge_tracks, merge_all_tracks with the triangulator as first argument), and retriangulation of under-reconstructed image pairs (retriangulate with the triangulator as first argument)")

@@ -22,7 +22,7 @@ try:  # the compiled host layer; absent only before `python -m pycolmap_amd.buil
         TwoViewGeometryOptions, absolute_pose_estimation, essential_matrix_estimation, estimate_calibrated_two_view_geometry,
         estimate_triangulation, estimate_two_view_geometry, estimate_two_view_geometry_pose, fundamental_matrix_estimation, has_cuda,
         has_hip, homography_decomposition, homography_matrix_estimation, last_run_stats, logging, match_exhaustive, merge_all_tracks, merge_tracks, match_sequential,
-        match_spatial, match_vocabtree, pose_refinement, rig_absolute_pose_estimation, squared_sampson_error, verify_matches,
+        match_spatial, match_vocabtree, pose_refinement, retriangulate, rig_absolute_pose_estimation, squared_sampson_error, verify_matches,
     )
     from ._extraction import extract_features  # noqa: F401
     from ._undistortion import _undistort_plan, undistort_images  # noqa: F401

@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = [
     "amc_triobs_opts_default", "amc_triangulate_observations", "amc_triobs_result_free",
     "amc_complete_opts_default", "amc_complete_tracks", "amc_complete_result_free",
     "amc_merge_opts_default", "amc_merge_tracks", "amc_merge_result_free",
+    "amc_retri_opts_default", "amc_retriangulate_pairs", "amc_retri_result_free",
 ]
 COMM_ID_BYTES = 128
 RANSAC_F, RANSAC_H, RANSAC_E = 0, 1, 2
@@ -415,6 +416,85 @@ def triobs_inputs(camera_models, camera_params, image_cameras, qvec, tvec, item_
         if two.size != off.size - 1:
             raise ValueError(f"{who}: {off.size - 1} items, {two.size} two-view flags")
     return models, prm, icam.astype(np.uint32), q, t, off.astype(np.uint64), ci.astype(np.uint32), xy, has, X, two
+
+
+class RetriOpts(C.Structure):  # amc_retri_opts (include/amc_retri.h)
+    _fields_ = [("create_max_angle_error", C.c_double), ("re_max_angle_error", C.c_double), ("min_angle", C.c_double),
+                ("re_min_ratio", C.c_double)]
+
+
+class RetriProblem(C.Structure):  # amc_retri_problem
+    _fields_ = [("num_cameras", C.c_size_t), ("camera_models", C.c_void_p), ("camera_params", C.c_void_p),
+                ("num_images", C.c_size_t), ("image_cameras", C.c_void_p), ("qvec", C.c_void_p), ("tvec", C.c_void_p),
+                ("num_obs", C.c_size_t), ("obs_image", C.c_void_p), ("obs_xy", C.c_void_p), ("obs_point", C.c_void_p),
+                ("num_points", C.c_size_t), ("point_xyz", C.c_void_p),
+                ("num_pairs", C.c_size_t), ("pair_images", C.c_void_p), ("pair_offsets", C.c_void_p),
+                ("corr_obs", C.c_void_p), ("corr_two_view", C.c_void_p),
+                ("num_rounds", C.c_size_t), ("round_offsets", C.c_void_p)]
+
+
+class RetriResult(C.Structure):  # amc_retri_result
+    _fields_ = [("num_pairs", C.c_uint64), ("num_corrs", C.c_uint64), ("num_pairs_run", C.c_uint64),
+                ("num_continued", C.c_uint64), ("num_created", C.c_uint64), ("pair_ran", C.POINTER(C.c_uint8)),
+                ("pair_num_tri", C.POINTER(C.c_uint32)), ("corr_action", C.POINTER(C.c_uint8)),
+                ("created_offsets", C.POINTER(C.c_uint64)), ("created_xyz", C.POINTER(C.c_double)),
+                ("num_launches", C.c_uint32), ("reserved", C.c_uint32),
+                ("host_ms", C.c_double), ("device_ms", C.c_double), ("kernel_ms", C.c_double), ("copy_ms", C.c_double),
+                ("alloc_ms", C.c_double)]
+
+
+RETRI_NONE, RETRI_CONTINUE_1TO2, RETRI_CONTINUE_2TO1, RETRI_CREATED = 0, 1, 2, 3
+RETRI_MAX_CORRS = 1 << 24
+
+
+def retri_inputs(camera_models, camera_params, image_cameras, qvec, tvec, obs_image, obs_xy, obs_point, point_xyz,
+                 pair_images, pair_offsets, corr_obs, round_offsets, corr_two_view=None):
+    """The flat problem of amc_retriangulate_pairs as contiguous arrays (copies: the caller's arrays are not touched):
+    models (C,) int32, params (C, 12), image_cameras (I,) uint32, qvec (I, 4) x y z w, tvec (I, 3), obs_image (N,)
+    uint32, obs_xy (N, 2), obs_point (N,) int32, point_xyz (P, 3), pair_images (K, 2) uint32, pair_offsets (K + 1,)
+    uint64, corr_obs (M, 2) uint32, round_offsets (R + 1,) uint64, corr_two_view (M,) uint8 or None."""
+    who = "retriangulate_pairs"
+    models = np.array(camera_models, dtype=np.int32).reshape(-1)
+    if len(camera_params) != models.size:
+        raise ValueError(f"{who}: {models.size} camera models, {len(camera_params)} parameter sets")
+    prm = np.zeros((models.size, 12), np.float64)
+    for i, p in enumerate(camera_params):
+        p = np.asarray(p, dtype=np.float64).reshape(-1)
+        if p.size > 12:
+            raise ValueError(f"{who}: camera {i} has {p.size} parameters (at most 12)")
+        prm[i, :p.size] = p
+    icam = np.array(image_cameras, dtype=np.int64).reshape(-1)
+    q = np.array(qvec, dtype=np.float64).reshape(-1, 4)
+    t = np.array(tvec, dtype=np.float64).reshape(-1, 3)
+    oi = np.array(obs_image, dtype=np.int64).reshape(-1)
+    xy = np.array(obs_xy, dtype=np.float64).reshape(-1, 2)
+    op = np.array(obs_point, dtype=np.int64).reshape(-1)
+    X = np.array(point_xyz, dtype=np.float64).reshape(-1, 3)
+    pi = np.array(pair_images, dtype=np.int64).reshape(-1, 2)
+    poff = np.array(pair_offsets, dtype=np.int64).reshape(-1)
+    co = np.array(corr_obs, dtype=np.int64).reshape(-1, 2)
+    roff = np.array(round_offsets, dtype=np.int64).reshape(-1)
+    if q.shape[0] != icam.size or t.shape[0] != icam.size or not (xy.shape[0] == op.size == oi.size):
+        raise ValueError(f"{who}: {icam.size} images by image_cameras, {q.shape[0]} rotations, {t.shape[0]} translations; "
+                         f"{oi.size} observations by obs_image, {xy.shape[0]} pixels, {op.size} point indices")
+    if poff.size != pi.shape[0] + 1 or poff.min() < 0 or int(poff[-1]) != co.shape[0]:
+        raise ValueError(f"{who}: {pi.shape[0]} pairs, {poff.size} pair offsets ending at {int(poff[-1]) if poff.size else None}, "
+                         f"{co.shape[0]} correspondences")
+    if roff.size < 1 or roff.min() < 0:
+        raise ValueError(f"{who}: round_offsets needs at least one non-negative entry")
+    for name, a in (("image_cameras", icam), ("obs_image", oi), ("pair_images", pi), ("corr_obs", co)):
+        if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+            raise ValueError(f"{who}: {name} has an index outside 0 .. 2^32 - 1")
+    if op.size and (op.min() < -(1 << 31) or op.max() >= (1 << 31)):
+        raise ValueError(f"{who}: obs_point has an index outside the int32 range")
+    two = None
+    if corr_two_view is not None:
+        two = np.ascontiguousarray(np.asarray(corr_two_view).reshape(-1) != 0, dtype=np.uint8)
+        if two.size != co.shape[0]:
+            raise ValueError(f"{who}: {co.shape[0]} correspondences, {two.size} two-view flags")
+    return (models, prm, icam.astype(np.uint32), q, t, oi.astype(np.uint32), xy, op.astype(np.int32), X,
+            np.ascontiguousarray(pi.astype(np.uint32)), poff.astype(np.uint64), np.ascontiguousarray(co.astype(np.uint32)),
+            roff.astype(np.uint64), two)
 
 
 class CompleteOpts(C.Structure):  # amc_complete_opts (include/amc_tracks.h)
@@ -844,6 +924,13 @@ def load() -> C.CDLL:
         lib.amc_merge_tracks.restype = C.c_int
         lib.amc_merge_result_free.argtypes = [C.POINTER(MergeResult)]
         lib.amc_merge_result_free.restype = None
+    if hasattr(lib, "amc_retriangulate_pairs"):  # (absent from a library built from an older revision)
+        lib.amc_retri_opts_default.argtypes = [C.POINTER(RetriOpts)]
+        lib.amc_retri_opts_default.restype = None
+        lib.amc_retriangulate_pairs.argtypes = [C.c_void_p, C.POINTER(RetriProblem), C.POINTER(RetriOpts), C.POINTER(RetriResult)]
+        lib.amc_retriangulate_pairs.restype = C.c_int
+        lib.amc_retri_result_free.argtypes = [C.POINTER(RetriResult)]
+        lib.amc_retri_result_free.restype = None
     if hasattr(lib, "amc_triangulate_tracks"):  # (absent from a library built from an older revision)
         lib.amc_tri_opts_default.argtypes = [C.POINTER(TriOpts)]
         lib.amc_tri_opts_default.restype = None
@@ -1408,6 +1495,40 @@ class Context:
                    "copy_ms": res.copy_ms, "alloc_ms": res.alloc_ms}
         finally:
             self._lib.amc_merge_result_free(C.byref(res))
+        return out
+
+    def retriangulate_pairs(self, camera_models, camera_params, image_cameras, qvec, tvec, obs_image, obs_xy, obs_point,
+                            point_xyz, pair_images, pair_offsets, corr_obs, round_offsets, corr_two_view=None,
+                            create_max_angle_error=2.0, re_max_angle_error=5.0, min_angle=1.5, re_min_ratio=0.2):
+        """amc_retriangulate_pairs: COLMAP's Retriangulate for image pairs coloured into rounds.
+        The cameras and images as in triangulate_observations; obs_image (N,), obs_xy (N, 2) pixels, obs_point (N,) the
+        index of the point an observation carries or -1; point_xyz (P, 3); pair_images (K, 2); pair_offsets (K + 1,) CSR
+        over corr_obs (M, 2), the observation of the pair's first and of its second image; round_offsets (R + 1,) CSR
+        over the pairs, the pairs of a round sharing no image; corr_two_view (M,) or None.  The angles are in degrees.
+        The inputs are not modified.  Returns a dict: pair_ran (K,) bool, pair_num_tri (K,), corr_action (M,) uint8
+        (RETRI_*), created_offsets (K + 1,), created_xyz (S, 3), num_pairs_run, num_continued, num_created,
+        num_launches, host_ms, device_ms, kernel_ms, copy_ms, alloc_ms."""
+        a = retri_inputs(camera_models, camera_params, image_cameras, qvec, tvec, obs_image, obs_xy, obs_point, point_xyz,
+                         pair_images, pair_offsets, corr_obs, round_offsets, corr_two_view)
+        models, prm, icam, q, t, oi, xy, op, X, pi, poff, co, roff, two = a
+        o = RetriOpts(float(create_max_angle_error), float(re_max_angle_error), float(min_angle), float(re_min_ratio))
+        ptr = lambda v: v.ctypes.data_as(C.c_void_p)  # noqa: E731
+        pb = RetriProblem(models.size, ptr(models), ptr(prm), icam.size, ptr(icam), ptr(q), ptr(t), oi.size, ptr(oi),
+                          ptr(xy), ptr(op), X.shape[0], ptr(X), pi.shape[0], ptr(pi), ptr(poff), ptr(co),
+                          None if two is None else ptr(two), roff.size - 1, ptr(roff))
+        res = RetriResult()
+        _check(self._lib.amc_retriangulate_pairs(self._h, C.byref(pb), C.byref(o), C.byref(res)))
+        try:
+            npairs, nc, made = pi.shape[0], co.shape[0], int(res.num_created)
+            arr = lambda p, k: np.ctypeslib.as_array(p, (max(k, 1),))[:k].copy()  # noqa: E731
+            out = {"pair_ran": arr(res.pair_ran, npairs).astype(bool), "pair_num_tri": arr(res.pair_num_tri, npairs),
+                   "corr_action": arr(res.corr_action, nc), "created_offsets": arr(res.created_offsets, npairs + 1),
+                   "created_xyz": arr(res.created_xyz, 3 * made).reshape(made, 3), "num_pairs_run": int(res.num_pairs_run),
+                   "num_continued": int(res.num_continued), "num_created": made, "num_launches": int(res.num_launches),
+                   "host_ms": res.host_ms, "device_ms": res.device_ms, "kernel_ms": res.kernel_ms,
+                   "copy_ms": res.copy_ms, "alloc_ms": res.alloc_ms}
+        finally:
+            self._lib.amc_retri_result_free(C.byref(res))
         return out
 
     def estimate_rig_absolute_poses(self, offsets, camera_offsets, camera_models, camera_params, cams_from_rig,

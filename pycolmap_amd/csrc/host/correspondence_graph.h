@@ -4,6 +4,7 @@
 // std::invalid_argument in the THROW_CHECK format (COLMAP aborts).
 #pragma once
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <map>
@@ -96,6 +97,12 @@ class CorrespondenceGraph {
         return it == pairs_.end() ? 0 : it->second;
     }
     size_t NumPoints2D(uint32_t image_id) const { return At(image_id, __LINE__).corrs.size(); }
+    // every image pair the graph holds as (smaller id << 32 | larger id, correspondence count), ascending
+    std::vector<std::pair<uint64_t, size_t>> ImagePairs() const {
+        std::vector<std::pair<uint64_t, size_t>> out(pairs_.begin(), pairs_.end());
+        std::sort(out.begin(), out.end());
+        return out;
+    }
 
     const std::vector<Correspondence>& ExtractCorrespondences(uint32_t image_id, uint32_t point2D_idx) const {
         return Corrs(image_id, point2D_idx, __LINE__);

@@ -43,6 +43,7 @@
 #include "ba_config_host.h"
 #include "ba_host.h"
 #include "reconstruction.h"
+#include "retriangulate_host.h"
 #include "track_ops_host.h"
 #include "triangulator_host.h"
 
@@ -1763,6 +1764,7 @@ PYBIND11_MODULE(_pycolmap, m) {
     struct PyTriangulator {
         py::object graph, reconstruction;
         std::set<uint64_t> modified;
+        RetriTrials re_trials;  // retriangulate's per-pair trial counters
     };
     // the outcome of triangulate_image back into r: the created points as new objects first, then update_with_errors
     auto update_with_new_points = [update_with_errors](PyReconstruction& r, const SparseModel& m) {
@@ -1911,7 +1913,7 @@ PYBIND11_MODULE(_pycolmap, m) {
         .def(py::init([](const py::object& graph, const py::object& reconstruction) {
                  if (!py::isinstance<CorrespondenceGraph>(graph) || !py::isinstance<PyReconstruction>(reconstruction))
                      throw py::type_error("IncrementalTriangulator(correspondence_graph: CorrespondenceGraph, reconstruction: Reconstruction)");
-                 return PyTriangulator{graph, reconstruction, {}};
+                 return PyTriangulator{graph, reconstruction, {}, {}};
              }), "correspondence_graph"_a, "reconstruction"_a)
         .def("_triangulate_image_with", triangulate_image_with, "options"_a, "image_id"_a, "solver"_a,
              "triangulate_image with a callable in the library's place (test hook).")
@@ -1934,7 +1936,7 @@ PYBIND11_MODULE(_pycolmap, m) {
         .def("__copy__", [](const PyTriangulator& t) { return PyTriangulator(t); })
         .def("__deepcopy__", [](const PyTriangulator& t, const py::dict& memo) {
                  const py::object deepcopy = py::module_::import("copy").attr("deepcopy");
-                 return PyTriangulator{deepcopy(t.graph, memo), deepcopy(t.reconstruction, memo), t.modified};
+                 return PyTriangulator{deepcopy(t.graph, memo), deepcopy(t.reconstruction, memo), t.modified, t.re_trials};
              })
         .def("__repr__", [](const PyTriangulator& t) {
             const PyReconstruction& r = t.reconstruction.cast<const PyReconstruction&>();
@@ -2206,6 +2208,151 @@ PYBIND11_MODULE(_pycolmap, m) {
     m.def("merge_all_tracks", [merge_tracks_with](PyTriangulator& t, const TriangulatorOptions& o) {
               return merge_tracks_with(t, o, py::none(), py::none());
           }, "triangulator"_a, "options"_a, "Merge the tracks of all points3D of the reconstruction (DESIGN.md section 18).");
+
+    // ---- retriangulate (retriangulate_host.h) ----
+    // IncrementalTriangulator::Retriangulate as a module-level function with the triangulator first: tests pin that the
+    // class has no such method.  The host colours the statically eligible pairs into rounds, one
+    // amc_retriangulate_pairs call runs every round on the device, and the host replays the result in the sequential
+    // order.  Nothing of the reconstruction, of the modified set or of the trial counters changes unless everything
+    // succeeds.  Without a device the call raises pycolmap_amd._capi.AmcError.
+    // solver: None, or a callable that stands in for the library (a test hook): it takes the flat problem as a dict of
+    // arrays and returns a dict with pair_ran, corr_action, created_offsets and created_xyz.  max_correspondences: the
+    // bound above which the call is refused (the library's; tests pass a smaller one).
+    auto retriangulate_with = [checked_model, update_with_new_points](PyTriangulator& t, const TriangulatorOptions& o, const py::object& solver,
+                                                                      uint64_t max_correspondences) -> size_t {
+        const auto t0 = std::chrono::steady_clock::now();
+        const std::string bad = o.Check();
+        if (!bad.empty()) throw py::value_error(CheckMessage(__FILE__, __LINE__, bad));
+        PyReconstruction& r = t.reconstruction.cast<PyReconstruction&>();
+        const CorrespondenceGraph& graph = t.graph.cast<const CorrespondenceGraph&>();
+        SparseModel model = checked_model(r);
+        ModelIndex ix(model, o);
+        const FlatRetri flat = PlanRetriangulation(graph, model, ix, o, t.re_trials, max_correspondences);
+        std::set<uint64_t> modified = t.modified;
+        RetriTrials trials = t.re_trials;
+        RetriApplied applied;
+        uint64_t calls = 0;
+        double device_ms = 0, kernel_ms = 0, copy_ms = 0;
+        if (flat.NumPairs() == 0) {
+            applied = ApplyRetriResult(flat, nullptr, nullptr, nullptr, nullptr, &model, &ix, &modified, &trials);
+        } else if (!solver.is_none()) {
+            auto arr = [](const auto& v, py::ssize_t cols) {
+                using T = typename std::decay<decltype(v)>::type::value_type;
+                py::array_t<T> a({static_cast<py::ssize_t>(v.size()) / cols, cols});
+                std::copy(v.begin(), v.end(), a.mutable_data());
+                return a;
+            };
+            py::dict d;
+            d["camera_models"] = arr(flat.camera_models, 1);
+            d["camera_params"] = arr(flat.camera_params, 12);
+            d["image_cameras"] = arr(flat.image_cameras, 1);
+            d["qvec"] = arr(flat.qvec, 4);
+            d["tvec"] = arr(flat.tvec, 3);
+            d["obs_image"] = arr(flat.obs_image, 1);
+            d["obs_xy"] = arr(flat.obs_xy, 2);
+            d["obs_point"] = arr(flat.obs_point, 1);
+            d["point_xyz"] = arr(flat.point_xyz, 3);
+            d["pair_images"] = arr(flat.pair_images, 2);
+            d["pair_offsets"] = arr(flat.pair_offsets, 1);
+            d["corr_obs"] = arr(flat.corr_obs, 2);
+            d["corr_two_view"] = arr(flat.corr_two_view, 1);
+            d["round_offsets"] = arr(flat.round_offsets, 1);
+            d["create_max_angle_error"] = o.create_max_angle_error;
+            d["re_max_angle_error"] = o.re_max_angle_error;
+            d["min_angle"] = o.min_angle;
+            d["re_min_ratio"] = o.re_min_ratio;
+            const py::dict out = solver(d);
+            const auto ran = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>::ensure(out["pair_ran"]);
+            const auto act = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>::ensure(out["corr_action"]);
+            const auto coff = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>::ensure(out["created_offsets"]);
+            const auto cxyz = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(out["created_xyz"]);
+            if (!ran || !act || !coff || !cxyz || static_cast<size_t>(ran.size()) != flat.NumPairs() || static_cast<size_t>(act.size()) != flat.NumCorrs() ||
+                static_cast<size_t>(coff.size()) != flat.NumPairs() + 1 || static_cast<uint64_t>(cxyz.size()) != 3 * coff.data()[flat.NumPairs()])
+                throw py::value_error("retriangulate: the solver's result does not have the problem's shape");
+            applied = ApplyRetriResult(flat, ran.data(), act.data(), coff.data(), cxyz.data(), &model, &ix, &modified, &trials);
+        } else {
+            amc_retri_opts opts;
+            amc_retri_opts_default(&opts);
+            opts.create_max_angle_error = o.create_max_angle_error;
+            opts.re_max_angle_error = o.re_max_angle_error;
+            opts.min_angle = o.min_angle;
+            opts.re_min_ratio = o.re_min_ratio;
+            const amc_retri_problem pb = flat.Problem();
+            amc_retri_result res{};
+            int rc = AMC_OK;
+            std::string err;
+            {
+                py::gil_scoped_release release;
+                EstimatorCtx& E = TheEstimatorCtx();
+                std::lock_guard<std::mutex> lock(E.mu);
+                amc_ctx* ctx = nullptr;
+                try {
+                    ctx = E.Get();
+                } catch (const std::runtime_error& e) {
+                    rc = AMC_E_HIP;
+                    err = e.what();
+                }
+                if (ctx) {
+                    rc = amc_retriangulate_pairs(ctx, &pb, &opts, &res);
+                    if (rc != AMC_OK) err = std::string("amc_retriangulate_pairs: ") + amc_last_error();
+                }
+            }
+            if (rc == AMC_E_INVALID) throw std::invalid_argument(err);
+            if (rc != AMC_OK) {
+                const py::object cls = py::module_::import("pycolmap_amd._capi").attr("AmcError");
+                const py::object exc = cls(rc, err);
+                PyErr_SetObject(cls.ptr(), exc.ptr());
+                throw py::error_already_set();
+            }
+            calls = 1;
+            device_ms = res.device_ms;
+            kernel_ms = res.kernel_ms;
+            copy_ms = res.copy_ms;
+            try {
+                applied = ApplyRetriResult(flat, res.pair_ran, res.corr_action, res.created_offsets, res.created_xyz, &model, &ix, &modified, &trials);
+            } catch (...) {
+                amc_retri_result_free(&res);
+                throw;
+            }
+            amc_retri_result_free(&res);
+        }
+        if (applied.num_tris != 0) update_with_new_points(r, model);
+        t.modified.swap(modified);
+        t.re_trials.swap(trials);
+        py::dict st;
+        st["call"] = "retriangulate";
+        st["num_pairs"] = flat.NumPairs();
+        st["num_pairs_run"] = applied.num_pairs_run;
+        st["num_rounds"] = flat.NumRounds();
+        st["num_correspondences"] = flat.NumCorrs();
+        st["num_continued_observations"] = applied.num_continued;
+        st["num_created_points"] = applied.num_created;
+        st["num_device_calls"] = calls;
+        st["device_ms"] = device_ms;
+        st["kernel_ms"] = kernel_ms;
+        st["copy_ms"] = copy_ms;
+        st["host_ms"] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - device_ms;
+        py::module_::import("pycolmap_amd._pycolmap").attr("_last_stats") = st;
+        return applied.num_tris;
+    };
+    m.def("_retriangulate_with", retriangulate_with, "triangulator"_a, "options"_a, "solver"_a,
+          "max_correspondences"_a = static_cast<uint64_t>(AMC_RETRI_MAX_CORRS),
+          "retriangulate with a callable in the library's place, or None for the library (test hook).");
+    m.def("retriangulate", [retriangulate_with](PyTriangulator& t, const TriangulatorOptions& o) {
+              return retriangulate_with(t, o, py::none(), AMC_RETRI_MAX_CORRS);
+          }, "triangulator"_a, "options"_a,
+          "Retriangulate the under-reconstructed image pairs: for every pair of the correspondence graph whose share of\n"
+          "correspondences with a common point3D is below re_min_ratio and that has trials left, continue tracks within\n"
+          "re_max_angle_error and create two-view points, on the GPU (DESIGN.md section 19).  Returns the number of\n"
+          "triangulated observations.");
+    m.def("_retriangulate_trials", [](const PyTriangulator& t) {
+              py::dict d;
+              for (const auto& kv : t.re_trials)
+                  d[py::make_tuple(static_cast<uint32_t>(kv.first >> 32), static_cast<uint32_t>(kv.first))] = kv.second;
+              return d;
+          }, "triangulator"_a, "The trial counters of retriangulate, {(image_id1, image_id2): trials} (test hook, a copy).");
+    m.def("_retriangulate_rounds", [](const std::vector<std::pair<uint32_t, uint32_t>>& pairs) { return ColourRetriRounds(pairs); },
+          "pairs"_a, "The round of every image pair under retriangulate's greedy colouring, pairs in the given order (test hook).");
 
     // ---- estimate_triangulation (/root/reference/pycolmap/estimators/triangulation.h; tri_host.h) ----------------------
     py::class_<TriPointData>(m, "PointData")

@@ -21,7 +21,7 @@ namespace amc {
 // (best=0, second=0 floors, strict '>'), so padded rows/columns can never
 // become a best or raise a second: no bounds checks inside the kernels.
 constexpr int kDim = AMC_DESC_DIM;   // 128 bytes per descriptor
-constexpr int kRowPad = 256;         // = MFMA kernel's column chunk; multiple of every tile
+constexpr int kRowPad = 256;         // a multiple of the MFMA kernel's column chunk (128) and of every tile
 constexpr int kAcosLutSize = 262145; // d in [0, 512*512]
 
 // The prepared arena stores the eight 16-byte slots of a row XOR-swizzled: slot q of row r lies at q ^ arena_swizzle(r).
@@ -375,7 +375,7 @@ hipError_t launch_match_guided_grid(const ImageDev* imgs, const GridDev* grids, 
 // packed kSegsPerItem to an item.  One 64-byte descriptor per segment holds every pointer a wave needs, so a
 // workgroup that pops an item is one round trip from its data whatever pairs its segments belong to.
 constexpr int kSegRows = 128;
-constexpr int kSegsPerItem = 8;
+constexpr int kSegsPerItem = 4;  // = waves of a scan workgroup; two workgroups share a CU (match_mfma.hip, "Shape")
 struct alignas(64) SegDesc {
     const uint8_t* xprep;   // mode 0: the segment's first prepared row; mode 1: the image's row 0
     const int32_t* xrs;     // rs128, likewise
@@ -404,7 +404,7 @@ __device__ __forceinline__ bool one_way_accepts(const Top2 t, const float* __res
 }
 
 // Packs the segments of the pairs listed in `order` (sorted by the streamed image; grp_start cuts it where that
-// image changes) into items: segs[0 .. 8 * *nitems_dev).  seg_base (one per order entry), grp_segs and
+// image changes) into items: segs[0 .. kSegsPerItem * *nitems_dev).  seg_base (one per order entry), grp_segs and
 // grp_item_base (one per group) are scratch.  All on stream s; mode 1 reads cand_cnt on the device.
 hipError_t launch_build_segments(int mode, const ImageDev* imgs, const PairDev* pairs, const uint32_t* order,
                            const uint32_t* grp_start, uint32_t ngroups, const uint32_t* cand_cnt,

@@ -200,7 +200,7 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
         size_t bytes = 0;
         int set = -1;  // the batch set whose bev[set][4] marks the copy done; -1: nothing pending
     } pending;
-    constexpr uint32_t kCopyParts = 8;
+    constexpr uint32_t kCopyParts = 64 / kSegsPerItem;  // 64 waves copy, whatever a scan workgroup holds
     auto sync_batch_streams = [&](const char* what) { return hc(hipStreamSynchronize(st), what); };
     const bool hook_split = batch_hook && hook_split_mode != 0;
     const size_t hook_split_min_pairs = hook_split_mode == 2 ? 2 : 4096;

@@ -42,27 +42,33 @@
 // t = 0..7 is Y row 32 (m >> 2) + 4 t + (m & 3).  Lane quarter q's 32 outputs of a block are then the contiguous
 // rows 32 q .. 32 q + 31 - one unit, exactly the 32-row tile 4 block + q that resolve_index recomputes - and the C
 // operand of a tile is four consecutive ints.  A block is scanned in four STEPS of two MFMA tiles each (32 rows'
-// worth of fragments); the scan of an image's last chunk ends at the last block that holds rows.
+// worth of fragments); the scan of an image ends with the last block that holds rows.
 //
 // Work items.  Every pair's X side is cut into
-// SEGMENTS of 128 rows; the segments of all pairs that stream the same Y image are packed, eight to
+// SEGMENTS of 128 rows; the segments of all pairs that stream the same Y image are packed, four to
 // an ITEM, by three small kernels (seg_count / seg_scan / seg_fill below) into 64-byte descriptors
 // that carry every pointer a wave needs.  A workgroup pops an item, streams that Y image once
 // through LDS, and its waves scan their own segments - which may belong to DIFFERENT pairs (they
-// only share the Y stream).  So a 4,500-row image costs 36 segment-times, not 5 x 8; 512-row pairs
-// fill a workgroup two at a time; and the reverse scan's candidate lists (known only on the
+// only share the Y stream).  So a 4,500-row image costs 36 segment-times, not 5 x 8; a 512-row pair
+// fills a workgroup; and the reverse scan's candidate lists (known only on the
 // device: the packing kernels read cand_cnt) are packed just as tightly.
 //
 // Shape.  One workgroup per item (dynamic queue, one ticket per item, taken at the top of the item before; items in
 // Y order so co-resident workgroups stream the same image out of L2; the next item's descriptor is fetched while the
-// current one is scanned): 512 threads, a segment (eight resident 16-row X tiles) per wave, 2 waves per SIMD.  MODE 0
-// compiles to exactly 256 VGPRs, the most two waves per SIMD allow (MODE 1: 236), without scratch: anything added to
-// the loop's live state will spill - check -Rpass-analysis=kernel-resource-usage after every change
-// (profiles/boundary/kernel_resource_usage.txt).  Taking the ticket two items ahead and warming the next item's X
-// rows in L2 were both built and measured, and neither paid (profiles/boundary/README.md).
-// Y streams through LDS in 256-row chunks by direct-to-LDS DMA, three buffers, the pieces of chunk c+2
-// issued one per two steps of chunk c, one barrier per chunk; the prepared arena is pre-swizzled
-// (arena_swizzle, amc_internal.h) so the linear DMA image is bank-conflict-free for
+// current one is scanned): 256 threads, a segment (eight resident 16-row X tiles) per wave, one wave per SIMD - and
+// TWO such workgroups on every CU, each popping its own items, so that every SIMD still holds two waves.  They are
+// independent: at an item boundary all four waves of a workgroup leave the loop together (they wait for the next
+// item's chunks and X rows, decode, and meet at two barriers: 6.7 % of an item's clocks, profiles/boundary/), and
+// the partner workgroup's wave then has the SIMD to itself instead of the matrix pipe of the whole CU standing idle.
+// A chunk crossing's barrier joins four waves on four SIMDs.  Both workgroups must fit: at most 256 registers per lane
+// (amdgpu_waves_per_eu pins it; MODE 0 compiles to 254 VGPRs, MODE 1 to 236, without scratch: anything added to
+// the loop's live state will spill - check -Rpass-analysis=kernel-resource-usage after every change,
+// profiles/items4/kernel_resource_usage.txt) and at most 80 KB of LDS (66 KB); launch_match_mfma asks the runtime.
+// Taking the ticket two items ahead and warming the next item's X rows in L2 were both built and measured, and
+// neither paid (profiles/boundary/README.md).
+// Y streams through LDS in 128-row chunks (one block) by direct-to-LDS DMA, a ring of four buffers, a wave's four
+// 1-KiB pieces of chunk c+3 issued one per step of chunk c, one barrier per chunk behind a counted wait; the prepared
+// arena is pre-swizzled (arena_swizzle, amc_internal.h) so the linear DMA image is bank-conflict-free for
 // ds_read_b128.  Each wave software-pipelines: the 4 MFMAs of (step, X tile) u+1 are interleaved with the
 // VALU of u, two accumulator sets.
 #include <cstdlib>
@@ -76,29 +82,32 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) const void gvoid_t;
 typedef __attribute__((address_space(3))) void lvoid_t;
 
-constexpr int kBN = 256;                // Y rows per LDS chunk (= kRowPad); 512 measured 2 % slower
+constexpr int kBN = 128;                // Y rows per LDS chunk: one block
 constexpr int kYS = kBN / 32;           // 32-row steps per chunk
 constexpr int kUR = 128;                // Y rows per block; arena_swizzle (amc_internal.h) is made for this width
 constexpr int kSPB = kUR / 32;          // steps per block
-constexpr int kUPC = kBN / kUR;         // blocks per chunk
-constexpr int kChunkBytes = kBN * kDim; // 32 KiB
+constexpr int kChunkBytes = kBN * kDim; // 16 KiB
 constexpr int kW = kSegsPerItem;        // waves per workgroup: a segment each
+constexpr int kWGPerCU = 2;             // workgroups that share a CU, one wave of each on every SIMD
 constexpr int kXT = kSegRows / 16;      // resident 16-row X tiles per wave
 constexpr int kKeyShift = 7, kKeyCarried = 127;
 
-// single LDS object (a second __shared__ object de-pipelines the DMA waits).  THREE chunk buffers: while chunk c is
-// scanned, chunk c+1 has landed (or is landing) and chunk c+2 is being fetched into the buffer chunk c-1 left -
-// so its DMA pieces need not wait for a barrier and are issued a few steps apart instead of all at the chunk
-// boundary, where they stalled the wave's MFMA stream (2.7 % of the scan).
-constexpr int kNB = 3;
+// single LDS object (a second __shared__ object de-pipelines the DMA waits).  A ring of FOUR chunk buffers: while
+// chunk c is scanned, chunks c+1 and c+2 have landed (or are landing) and chunk c+3 is being fetched into the buffer
+// chunk c-1 left - so its DMA pieces need not wait for a barrier and are issued one per step instead of all at the
+// chunk boundary, where they stalled the wave's MFMA stream (2.7 % of the scan).  Three chunks ahead of 128 rows each
+// is the prefetch distance in rows that two chunks of 256 were.
+constexpr int kNB = 4;
 constexpr int kOffRs = 0;                        // kNB x rs128 chunks (kBN ints each)
 constexpr int kOffQ = kOffRs + kNB * kBN * 4;    // queue slot
 constexpr int kOffB = kOffQ + 16;                // kNB x descriptor chunks
 constexpr int kLdsBytes = kOffB + kNB * kChunkBytes;
-static_assert(kBN == kRowPad, "a chunk is the row padding unit");
-static_assert(kUR == 128 && kSPB == 4, "a lane quarter's rows of a block are one 32-row tile; the loop body is one block");
+static_assert(kRowPad % kBN == 0, "a chunk divides the row padding: every chunk that holds a row lies inside the padded image");
+static_assert(kUR == 128 && kSPB == 4 && kBN == kUR, "a lane quarter's rows of a block are one 32-row tile; the loop body is one block, which is one chunk");
 static_assert(kRowPad % kSegRows == 0 && kSegRows % 32 == 0, "segments tile the padded rows");
-static_assert(kLdsBytes <= 160 * 1024, "LDS of one CU");
+static_assert((kNB & (kNB - 1)) == 0, "the ring position is taken modulo kNB with a mask");
+static_assert(kWGPerCU * (kLdsBytes + 16) <= 160 * 1024, "LDS of one CU holds two workgroups (and their copy-part slots)");
+static_assert(kW == 4, "one wave of a workgroup per SIMD");
 static_assert(sizeof(SegDesc) == 64, "a descriptor is 16 dwords: one per lane of a quarter wave");
 
 // dword positions of the SegDesc fields (a wave holds its descriptor in ONE register: lane l < 16 has dword l)
@@ -145,8 +154,8 @@ __device__ uint32_t g_scan_stamps[2 * kStampMaxWG * kSegsPerItem * 8];
 // covers the buffer with its grid and takes every CU while PCIe moves 400 MB (10 ms, and the scan behind it waits:
 // kernel trace of the dense set, 19 ms of 292 per call); a small copy kernel on a second stream shares a hardware queue
 // with the scan's stream more often than not.  So the copy rides in the scan's own launch: the first `parts`
-// workgroups to arrive take one part each - 512 lanes with four 16-byte loads in flight per lane saturate PCIe from
-// a handful of workgroups - and then scan like the others; the scan loses parts x 10 ms of one workgroup's time.
+// workgroups to arrive take one part each - 256 lanes with four 16-byte loads in flight per lane, sixteen such
+// workgroups saturate PCIe - and then scan like the others; the scan loses parts x 10 ms of one workgroup's time.
 // Compiled as ONE general function of (tid, nthreads).  `used` keeps the compiler from specialising it for its
 // single caller's thread count (which also moves that kernel's register allocation); the assumption states the
 // ranges it may rely on.
@@ -163,14 +172,15 @@ __device__ __noinline__ __attribute__((used)) void copy_part(const uint4* __rest
     for (; i < e; i += st) dst[i] = src[i];
 }
 
+// Two waves per SIMD, pinned: a 256-thread bound alone lets the compiler plan for one wave per SIMD and 512 registers,
+// and then only one workgroup fits a CU (launch_match_mfma checks the occupancy it gets).
 template <int MODE>
-__global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __restrict__ segs,
-                                                             const uint32_t* __restrict__ nitems_p,
-                                                             uint32_t* __restrict__ queue_head,
-                                                             uint32_t* __restrict__ accmask,
-                                                             const ScanAccept* __restrict__ accept,
-                                                             CopyJob job, uint32_t* __restrict__ copy_head) {
-    static_assert((kChunkBytes / 1024) % kW == 0 && kYS % (kChunkBytes / 1024 / kW) == 0, "a chunk splits into 1 KiB DMA pieces per wave, dealt evenly over its steps");
+__global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kWGPerCU, kWGPerCU)))
+void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restrict__ nitems_p,
+                       uint32_t* __restrict__ queue_head, uint32_t* __restrict__ accmask,
+                       const ScanAccept* __restrict__ accept, CopyJob job, uint32_t* __restrict__ copy_head) {
+    static_assert(kChunkBytes / 1024 == kW * kYS, "a chunk splits into 1 KiB DMA pieces, one per wave and step");
+    static_assert(kBN * 4 == 512, "a chunk's rs128 block is half a wave's DMA");
     __shared__ __attribute__((aligned(16))) char smem[kLdsBytes];
 
     const int tid = threadIdx.x;
@@ -214,7 +224,7 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
                                          (lvoid_t*)(smem + kOffB + buf * kChunkBytes + piece * 1024), 16, 0, 0);
     };
     auto stage_rs = [&](const char* yrs, int c, int buf) __attribute__((always_inline)) {
-        if (wid == 0)  // rs128 of this chunk's rows: 1 KiB
+        if (wid == 0 && lane < kBN / 4)  // rs128 of this chunk's rows: 512 B, the lower half of the wave
             __builtin_amdgcn_global_load_lds((gvoid_t*)(yrs + (size_t)c * kBN * 4 + lane * 16),
                                              (lvoid_t*)(smem + kOffRs + buf * kBN * 4), 16, 0, 0);
     };
@@ -222,6 +232,16 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
 #pragma unroll
         for (int ps = 0; ps < kPW; ++ps) stage_piece(yprep, c, buf, ps);
         stage_rs(yrs, c, buf);
+    };
+    // an item starts with the chunks 0 .. kNB - 2 of its Y image in flight, as many as hold rows (dv: its descriptor)
+    auto stage_head = [&](int dv) __attribute__((always_inline)) {
+        const char* yprep = dptr(dv, kDYprep);
+        const char* yrs = dptr(dv, kDYrs);
+        const int yrows = dword(dv, kDYrows);
+        stage(yprep, yrs, 0, 0);
+#pragma unroll
+        for (int c = 1; c < kNB - 1; ++c)
+            if (yrows > c * kBN) stage(yprep, yrs, c, c);
     };
 
     // A-operand fragments + C blocks of step `ys` of the chunk in LDS buffer `buf`, as six 16-byte reads: parts 0, 1 =
@@ -294,25 +314,21 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
     uint32_t q = *s_q;
     int dv = load_desc(q);
     if (q < nitems) {
-        stage(dptr(dv, kDYprep), dptr(dv, kDYrs), 0, 0);
-        if (dword(dv, kDYrows) > kBN) stage(dptr(dv, kDYprep), dptr(dv, kDYrs), 1, 1);
+        stage_head(dv);
         if (dword(dv, kDCnt) > 0) load_x(dv);
     }
     __syncthreads();  // everyone has read the slot before it is rewritten
 
     while (q < nitems) {
-        // chunks 0 and 1 of this item's Y image are on their way and the X fragments are being loaded (issued by
+        // chunks 0 .. 2 of this item's Y image are on their way and the X fragments are being loaded (issued by
         // the previous iteration or the prologue)
         const char* yprep = dptr(dv, kDYprep);  // the same in every descriptor of the item
         const char* yrs = dptr(dv, kDYrs);
-        const int yrows_item = dword(dv, kDYrows);
-        const int nchunks = (yrows_item + kBN - 1) / kBN;
-        // Steps of the LAST chunk that hold rows, rounded up to a block: what follows them in the chunk is the
-        // image's zero padding (rows_pad is a multiple of 256) - a zero row can never become a best nor raise a second,
-        // so its blocks need not be scanned (an image of 4,000 rows paid for 4,096; n ~ U[2000, 6000]: 2.4 % of
-        // the scan; ending at a 128-row block leaves 64 padded rows per image on average where a chunk leaves 128).  An image whose rows fill its last chunk scans
-        // all kYS steps.
-        const int last_steps = (((yrows_item - (nchunks - 1) * kBN) + 31) / 32 + kSPB - 1) & ~(kSPB - 1);
+        // Only the chunks that hold rows: what follows them is the image's zero padding (rows_pad is a multiple of
+        // 256) - a zero row can never become a best nor raise a second, so a chunk of nothing else is neither
+        // fetched nor scanned (an image of 4,000 rows paid for 4,096; n ~ U[2000, 6000]: 2.4 % of the scan; ending
+        // at a 128-row chunk leaves 64 padded rows per image on average).
+        const int nchunks = (dword(dv, kDYrows) + kBN - 1) / kBN;
         const bool active = dword(dv, kDCnt) > 0;  // wave-uniform
         if (tid == 0) *s_q = atomicAdd(queue_head, 1u);  // the next item, behind the loads already in flight
 
@@ -434,26 +450,38 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
         // have run to their end since: well over the 7 wait states a 4-pass MFMA's result needs before a VALU read
         // (two further MFMAs would do; the rule the 8-pass instruction needed, 11 states, held with two as well).
         // one step = 32 rows' worth of Y held in `yc`; prefetches the next step into `yn`
-        // cb / nb: LDS buffers of chunk c and c + 1 (c % 3, (c + 1) % 3)
-        auto step = [&](YFrag& yc, YFrag& yn, int c, int cb, int nb, int ys, int sp) __attribute__((always_inline)) {
-            const bool lastt = sp == kSPB - 1 && ys == kYS - 1;  // (a chunk ends with a block)
+        // cb / nb: LDS buffers of chunk c and c + 1 (c % kNB, (c + 1) % kNB); ys = the step of the chunk, 0 .. kYS - 1
+        auto step = [&](YFrag& yc, YFrag& yn, int c, int cb, int nb, int ys) __attribute__((always_inline)) {
+            const int sp = ys;  // a chunk is one block
+            const bool lastt = ys == kYS - 1;
             const bool cross = lastt && (c + 1 < nchunks);
-            const bool fetch = c + 2 < nchunks;  // chunk c + 2 goes to the buffer chunk c - 1 left: (c + 2) % 3
+            // chunk c + 3 goes to the buffer chunk c - 1 left, (c + 3) % kNB: this wave's kPW pieces of it, one
+            // 1 KiB piece per step, never bunched
+            const bool fetch = c + kNB - 1 < nchunks;
+            static_assert(kPW == kYS, "one DMA piece per wave and step");
             if (fetch) {
-                const int fb = cb == 0 ? 2 : cb - 1;
-                constexpr int kEvery = kYS / kPW;  // a piece every other step
-                static_assert(kEvery == 2, "a DMA piece behind every other step");
-                if (sp % kEvery == 0) stage_piece(yprep, c + 2, fb, ys / kEvery);
-                if (ys == 0) stage_rs(yrs, c + 2, fb);
+                const int fb = (cb + kNB - 1) & (kNB - 1);
+                stage_piece(yprep, c + kNB - 1, fb, ys);
+                if (ys == 0) stage_rs(yrs, c + kNB - 1, fb);
             }
             if (cross) {
 #ifdef AMC_SCAN_STAMPS
                 const uint32_t st_t = AMC_STAMP();
 #endif
-                // chunk c + 1 must have landed: everything but this chunk's own kPW (+ 1) pieces of chunk c + 2
-                if (!fetch) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                else if (wid == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPW + 1) : "memory");
-                else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPW) : "memory");
+                // Chunk c + 1 must have landed.  Loads return in the order they were issued, and behind this wave's
+                // pieces of chunk c + 1 it has issued its kPW pieces (wave 0: + 1 rs128 block) of every later chunk
+                // that exists, c + 2 and c + 3: so many may stay in flight and no more.  (At the first crossing chunks
+                // 1 and 2 have landed with the item's X rows; fewer pieces are in flight than the count allows.)
+                static_assert(kNB == 4, "the counted waits below are written out for three chunks ahead");
+                if (fetch) {
+                    if (wid == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * kPW + 2) : "memory");
+                    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * kPW) : "memory");
+                } else if (c + 2 < nchunks) {
+                    if (wid == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPW + 1) : "memory");
+                    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPW) : "memory");
+                } else {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // nothing further to fetch
+                }
                 // a bare barrier: __syncthreads() is a fence and would drain the pieces just issued (vmcnt(0)).
                 // Nothing is stored to LDS here by a wave itself; the DMA'd bytes are ordered by the waits above.
                 asm volatile("s_barrier" ::: "memory");
@@ -465,7 +493,7 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
                 // very last step: re-read itself (result unused) to stay branch-free
                 const int nbuf = cross ? nb : cb;
                 const int nys = lastt ? (cross ? 0 : ys) : ys + 1;
-                const int gb = c * kUPC + ys / kSPB;
+                const int gb = c;  // the block = the chunk
 #pragma unroll
                 for (int xt = 0; xt < kXT; ++xt) {
                     if (xt + 1 < kXT)
@@ -479,20 +507,16 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
                 }
             }
         };
-        for (int c = 0, cb = 0; c < nchunks; ++c) {
-            const int nb = cb == 2 ? 0 : cb + 1;
-            const int yend = (c == nchunks - 1) ? last_steps : kYS;
 #pragma unroll 1
-            for (int ys = 0; ys < yend; ys += kSPB) {  // one block
-                step(y0, y1, c, cb, nb, ys, 0);
-                step(y1, y0, c, cb, nb, ys + 1, 1);
-                step(y0, y1, c, cb, nb, ys + 2, 2);
-                step(y1, y0, c, cb, nb, ys + 3, 3);
-            }
-            cb = nb;
+        for (int c = 0; c < nchunks; ++c) {  // one chunk = one block
+            const int cb = c & (kNB - 1), nb = (c + 1) & (kNB - 1);
+            step(y0, y1, c, cb, nb, 0);
+            step(y1, y0, c, cb, nb, 1);
+            step(y0, y1, c, cb, nb, 2);
+            step(y1, y0, c, cb, nb, 3);
         }
         if (active) {
-            const int lastb = (nchunks - 1) * kUPC + last_steps / kSPB - 1;
+            const int lastb = nchunks - 1;
             insert(kXT - 1, 126 - (lastb & 63));  // the last unit's maximum is still pending
             flush(lastb >> 6);
 #pragma unroll
@@ -519,8 +543,7 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
             ex[xt] = xterm[xt];
         }
         if (qn < nitems) {
-            stage(dptr(dvn, kDYprep), dptr(dvn, kDYrs), 0, 0);
-            if (dword(dvn, kDYrows) > kBN) stage(dptr(dvn, kDYprep), dptr(dvn, kDYrs), 1, 1);
+            stage_head(dvn);
             if (dword(dvn, kDCnt) > 0) load_x(dvn);
         }
         if (active) {
@@ -594,7 +617,7 @@ __global__ __launch_bounds__(64 * kW) void match_mfma_kernel(const SegDesc* __re
 // `order` lists the launch's pairs sorted by the streamed image; `grp_start` (host-built, ngroups + 1
 // entries) cuts it where that image changes.  A pair contributes ceil(rows / 128) segments - rows = image 1's
 // rows (mode 0) or the pair's candidate count (mode 1, known only here) - none if the streamed image is empty.
-// Items never mix streamed images: every group is padded to a multiple of 8 segments with null descriptors
+// Items never mix streamed images: every group is padded to a multiple of 4 segments with null descriptors
 // (cnt = 0, but a valid Y stream, so any wave can read it from its own descriptor).
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t pair_segments(int mode, const ImageDev* imgs, const PairDev& p, uint32_t pi,
@@ -643,7 +666,7 @@ __global__ __launch_bounds__(256) void seg_count_kernel(int mode, const ImageDev
     if (tid == 0) grp_segs[g] = running;
 }
 
-// one block: grp_item_base = exclusive scan of ceil(grp_segs / 8); the launch's item count
+// one block: grp_item_base = exclusive scan of ceil(grp_segs / 4); the launch's item count
 __global__ __launch_bounds__(1024) void seg_scan_kernel(const uint32_t* __restrict__ grp_segs, uint32_t ngroups,
                                                         uint32_t* __restrict__ grp_item_base,
                                                         uint32_t* __restrict__ nitems_out) {
@@ -768,14 +791,26 @@ hipError_t launch_match_mfma(int mode, const SegDesc* segs, const uint32_t* nite
     int dev = 0, cus = 256;
     if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
     if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-    // 1 WG per CU.  AMC_SCAN_GRID (A/B hook, read once): fewer workgroups - the CUs left over stay free for whatever
-    // else is in flight (round 6's question: does a power-bound scan lose less than its share of CUs?  DESIGN.md section 6)
+    // Two workgroups per CU, and the kernels must really fit that way (registers, LDS): asked of the runtime once.
+    // One per CU would run on half the machine's register file without anyone noticing - it is an error instead.
+    static const hipError_t occupancy = [] {
+        int n0 = 0, n1 = 0;
+        hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n0, match_mfma_kernel<0>, 64 * kW, 0);
+        if (oe == hipSuccess) oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, match_mfma_kernel<1>, 64 * kW, 0);
+        if (oe != hipSuccess) return oe;
+        return n0 >= kWGPerCU && n1 >= kWGPerCU ? hipSuccess : hipErrorLaunchOutOfResources;
+    }();
+    if (occupancy != hipSuccess) return occupancy;
+    int wgs = kWGPerCU * cus;
+    // AMC_SCAN_GRID (A/B hook, read once) caps the number of WORKGROUPS (two of them fill a CU): fewer than 2 per CU -
+    // the CUs left over stay free for whatever else is in flight (round 6's question: does a power-bound scan lose
+    // less than its share of CUs?  DESIGN.md section 6)
     static const int grid_cap = [] {
         const char* e = std::getenv("AMC_SCAN_GRID");
         return e ? std::atoi(e) : 0;
     }();
-    if (grid_cap > 0 && grid_cap < cus) cus = grid_cap;
-    const uint32_t grid = max_items < (uint32_t)cus ? max_items : (uint32_t)cus;
+    if (grid_cap > 0 && grid_cap < wgs) wgs = grid_cap;
+    const uint32_t grid = max_items < (uint32_t)wgs ? max_items : (uint32_t)wgs;
     if (job.parts > grid) job.parts = grid;  // every part needs a workgroup
     if ((e = memset_async(queue_head, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
     if (mode == 0)

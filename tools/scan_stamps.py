@@ -4,10 +4,12 @@
 crossings (a / c) and at the item boundary (b / c).  The stamps are described in match_mfma.hip (AMC_SCAN_STAMPS).
 Needs a GPU; not in the test suite.
 
-    bash tools/scan_stamps_build.sh && python tools/scan_stamps.py --images 8 --rows 4096 --grid 14
+    bash tools/scan_stamps_build.sh && python tools/scan_stamps.py --images 8 --rows 4096 --grid 28
 
---grid caps the scan's workgroups (AMC_SCAN_GRID): 8 images are 112 items, fewer than a workgroup per CU takes, and an
-item boundary only exists where a workgroup scans more than one item."""
+--grid caps the scan's workgroups (AMC_SCAN_GRID; two of them share a CU): 8 images are 224 items of four segments,
+fewer than the workgroups of a full grid (two per CU) take, and an item boundary only exists where a workgroup scans
+more than one item.  A workgroup's clocks run while its CU partner scans too: compare clocks per item with TWICE the
+clocks of an item of the same four segments scanned alone."""
 import argparse
 import ctypes
 import json
@@ -19,7 +21,7 @@ import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 LIB = os.path.join(ROOT, "pycolmap_amd", "csrc", "_obj", "libamc_stamps.so")
-MAX_WG, WAVES = 1024, 8
+MAX_WG, WAVES = 1024, 4  # kStampMaxWG, kSegsPerItem (match_mfma.hip, amc_internal.h)
 
 
 def main():

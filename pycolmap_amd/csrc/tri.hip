@@ -122,6 +122,9 @@ static int triangulate_impl(amc_ctx* ctx, const double* poses, size_t nposes, co
                             size_t ntracks, const uint32_t* obs_pose, const double* obs_xy, const amc_tri_opts* opts,
                             amc_tri_result* result) {
     const char* const hipchk_who = "amc_triangulate_tracks";
+    // (the test hooks are read before anything can fail, once per call: smaller batch bounds, the same results)
+    const uint64_t max_batch_tracks = (uint64_t)env_int("AMC_TRI_BATCH_TRACKS", (long long)kMaxBatchTracks, 1, (long long)kMaxBatchTracks);
+    const uint64_t max_batch_obs = (uint64_t)env_int("AMC_TRI_BATCH_OBS", (long long)kMaxBatchObs, 1, (long long)kMaxBatchObs);
     if (!ctx || !opts || !result || !track_offsets || (nposes && !poses))
         return api_fail(AMC_E_INVALID, "amc_triangulate_tracks: NULL argument");
     std::memset(result, 0, sizeof *result);
@@ -186,8 +189,8 @@ static int triangulate_impl(amc_ctx* ctx, const double* poses, size_t nposes, co
     if (dyn_tab.empty()) dyn_tab.push_back(0);
 
     // batches: contiguous track ranges of at most kMaxBatchTracks tracks and kMaxBatchObs observations (a longer track
-    // is a batch of its own)
-    const Batches batches = split_batches(track_offsets, ntracks, kMaxBatchTracks, kMaxBatchObs);
+    // is a batch of its own); AMC_TRI_BATCH_TRACKS and AMC_TRI_BATCH_OBS lower the bounds
+    const Batches batches = split_batches(track_offsets, ntracks, max_batch_tracks, max_batch_obs);
     const std::vector<size_t>& bstart = batches.start;
     const size_t nbatch = batches.count();
     const uint64_t max_bt = batches.most_items, max_bo = std::max<uint64_t>(batches.most_elems, 1);

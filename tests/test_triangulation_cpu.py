@@ -188,9 +188,27 @@ def test_reference_trial_caps():
 
 
 # ---- an independent restatement: numpy / LAPACK ------------------------------------------------------------------------
-def _np_triangulate_track(P, C, xy, min_tri_angle, max_error, conf=0.9999, mult=3.0, min_trials=1000, max_trials=100000):
+def _np_num_trials(ratio, conf, mult):
+    """ComputeNumTrials with kMinNumSamples = 2; 1 << 64 for "no limit" """
+    nom = 1 - conf
+    if nom <= 0:
+        return 1 << 64
+    denom = 1 - ratio ** 2
+    if denom <= 0:
+        return 1
+    if denom == 1.0:
+        return 1 << 64
+    return int(math.ceil(math.log(nom) / math.log(denom) * mult))
+
+
+def _np_triangulate_track(P, C, xy, min_tri_angle, max_error, conf=0.9999, mult=3.0, min_trials=1000, max_trials=100000,
+                          min_ratio=0.01):
+    """(xyz or None, mask, num_trials, clear): clear is False when one of this function's own residuals came within
+    1e-6 relative of max_error^2, or one of its angles within 1e-9 rad of a positive min_tri_angle (the margins of
+    tests/test_filter_cpu.py): a comparison there decides by rounding."""
     n = len(xy)
     maxres = max_error * max_error
+    clear = [True]
 
     def angle(c1, c2, X):
         b2, r1, r2 = np.sum((c1 - c2) ** 2), np.sum((X - c1) ** 2), np.sum((X - c2) ** 2)
@@ -199,7 +217,10 @@ def _np_triangulate_track(P, C, xy, min_tri_angle, max_error, conf=0.9999, mult=
             return 0.0
         with np.errstate(invalid="ignore"):
             a = abs(np.arccos((r1 + r2 - b2) / den))
-        return min(a, np.pi - a) if not np.isnan(a) else np.nan
+        a = min(a, np.pi - a) if not np.isnan(a) else np.nan
+        if min_tri_angle > 0 and abs(a - min_tri_angle) <= 1e-9:
+            clear[0] = False
+        return a
 
     def residuals(X):
         a = np.c_[xy, np.ones(n)]
@@ -207,7 +228,10 @@ def _np_triangulate_track(P, C, xy, min_tri_angle, max_error, conf=0.9999, mult=
         q = P[:, :, :3] @ X + P[:, :, 3]
         q /= np.linalg.norm(q, axis=1, keepdims=True)
         with np.errstate(invalid="ignore"):
-            return np.arccos(np.sum(a * q, axis=1)) ** 2
+            r = np.arccos(np.sum(a * q, axis=1)) ** 2
+            if np.any(np.abs(r - maxres) <= 1e-6 * maxres):
+                clear[0] = False
+        return r
 
     def estimate(idx):
         if len(idx) == 2:
@@ -243,17 +267,11 @@ def _np_triangulate_track(P, C, xy, min_tri_angle, max_error, conf=0.9999, mult=
         return s[0] > b[0] or (s[0] == b[0] and s[1] < b[1])
 
     def num_trials(k):
-        nom = 1 - conf
-        if nom <= 0:
-            return 1 << 64
-        denom = 1 - (k / n) ** 2
-        if denom <= 0:
-            return 1
-        if denom == 1.0:
-            return 1 << 64
-        return int(math.ceil(math.log(nom) / math.log(denom) * mult))
+        return _np_num_trials(k / n, conf, mult)
 
-    cap = min(max_trials, num_trials_cfg(conf, mult, max_trials), n * (n - 1) // 2)
+    if n < 2:
+        return None, np.zeros(n, bool), 0, True
+    cap = min(max_trials, _np_num_trials(int(min_ratio * 100000) / 100000, conf, mult), n * (n - 1) // 2)
     best, best_X = (0, np.finfo(float).max), None
     dyn = cap
     pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
@@ -283,16 +301,12 @@ def _np_triangulate_track(P, C, xy, min_tri_angle, max_error, conf=0.9999, mult=
                 abort = True
         trial += 1
     if best[0] < 2:
-        return None, np.zeros(n, bool)
-    return best_X, residuals(best_X) <= maxres
+        return None, np.zeros(n, bool), trial, clear[0]
+    return best_X, residuals(best_X) <= maxres, trial, clear[0]
 
 
-def num_trials_cfg(conf, mult, max_trials, min_inlier_ratio=0.01):
-    r = int(min_inlier_ratio * 100000) / 100000
-    return int(math.ceil(math.log(1 - conf) / math.log(1 - r * r) * mult))
-
-
-def _np_batch(sc, min_tri_angle=0.0, max_error=tri_cases.TIGHT):
+def _np_batch(sc, min_tri_angle=0.0, max_error=tri_cases.TIGHT, confidence=0.9999, dyn_num_trials_multiplier=3.0,
+              min_num_trials=1000, max_num_trials=100000, min_inlier_ratio=0.01):
     Pall = sc["poses"]
     Call = -np.einsum("cji,cj->ci", Pall[:, :, :3], Pall[:, :, 3])
     off = sc["offsets"].astype(np.int64)
@@ -300,7 +314,8 @@ def _np_batch(sc, min_tri_angle=0.0, max_error=tri_cases.TIGHT):
     for t in range(len(off) - 1):
         sl = slice(off[t], off[t + 1])
         idx = sc["obs_pose"][sl]
-        out.append(_np_triangulate_track(Pall[idx], Call[idx], sc["obs_xy"][sl], min_tri_angle, max_error))
+        out.append(_np_triangulate_track(Pall[idx], Call[idx], sc["obs_xy"][sl], min_tri_angle, max_error, confidence,
+                                         dyn_num_trials_multiplier, min_num_trials, max_num_trials, min_inlier_ratio))
     return out
 
 
@@ -309,22 +324,28 @@ def test_reference_agrees_with_numpy_restatement():
     sc = tri_cases.scene(401, 150, outlier_frac=0.0, mean_len=5.0, max_len=8)
     xyz, ok, mask, st = ref.triangulate(sc["poses"], sc["offsets"], sc["obs_pose"], sc["obs_xy"], max_error=tri_cases.TIGHT)
     off = sc["offsets"].astype(np.int64)
-    for t, (X, m) in enumerate(_np_batch(sc)):
-        assert (X is not None) == ok[t]
+    for t, (X, m, trials, _) in enumerate(_np_batch(sc)):
+        assert (X is not None) == ok[t] and trials == st["num_trials"][t]
         assert np.array_equal(m, mask[off[t]:off[t + 1]])
         if X is not None:
             assert np.allclose(X, xyz[t], rtol=1e-6, atol=1e-9)
-    # a seeded random set with outliers and an angle limit: report the agreement, expect nearly all
+    # a seeded random set with outliers and an angle limit: identical on every track that the restatement's own numbers
+    # show to be clear of a threshold, and those are at least 95 % of the tracks
     sc = tri_cases.scene(402, 300, outlier_frac=0.2, mean_len=6.0, max_len=12)
     xyz, ok, mask, st = ref.triangulate(sc["poses"], sc["offsets"], sc["obs_pose"], sc["obs_xy"], max_error=tri_cases.TIGHT,
                                         min_tri_angle=0.05)
     off = sc["offsets"].astype(np.int64)
-    agree = 0
-    for t, (X, m) in enumerate(_np_batch(sc, min_tri_angle=0.05)):
-        agree += int((X is not None) == ok[t] and np.array_equal(m, mask[off[t]:off[t + 1]]))
-    rate = agree / (len(off) - 1)
-    print(f"reference vs numpy restatement: {agree} of {len(off) - 1} tracks identical ({rate:.3f})")
-    assert rate > 0.95
+    unclear = 0
+    for t, (X, m, trials, clear) in enumerate(_np_batch(sc, min_tri_angle=0.05)):
+        if not clear:
+            unclear += 1
+            continue
+        assert (X is not None) == ok[t] and trials == st["num_trials"][t], t
+        assert np.array_equal(m, mask[off[t]:off[t + 1]]), t
+        if X is not None:
+            assert np.allclose(X, xyz[t], rtol=1e-6, atol=1e-9), t
+    print(f"reference vs numpy restatement: {unclear} of {len(off) - 1} tracks within a margin of a threshold")
+    assert unclear <= 0.05 * (len(off) - 1)
 
 
 # ---- the frozen fixture and the recording ------------------------------------------------------------------------------
@@ -355,3 +376,181 @@ def test_reference_against_pycolmap_recording():
         assert (ok == rok).mean() > 0.95, name
         both = ok & rok
         assert np.allclose(fx[f"{name}/xyz"][both], rc[f"{name}/xyz"][both], rtol=1e-6, atol=1e-8), name
+
+
+# ---- the edge cases (tri_cases.EDGE_CASES) -------------------------------------------------------------
+EDGES = tri_cases.EDGE_CASES
+
+
+def _maker():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("mk_tri", ROOT / "tests" / "golden" / "make_tri_ref_golden.py")
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    return mk
+
+
+@pytest.fixture(scope="module")
+def traced_edges():
+    """the reference with its trace on every edge case, once: name -> (xyz, success, mask, stats, trace)"""
+    return {name: ref.triangulate_trace(sc["poses"], sc["offsets"], sc["obs_pose"], sc["obs_xy"], **opts)
+            for name, (sc, opts) in EDGES.items()}
+
+
+def test_edge_fixture_lists_the_edge_cases():
+    golden = _maker().load_edges()
+    assert sorted(golden) == sorted(EDGES)
+    assert (GOLDEN / "tri_ref_edges_v1.npz").stat().st_size < 10_000
+    assert len(tri_cases.cases()) == 12
+
+
+@pytest.mark.parametrize("name", sorted(EDGES))
+def test_reference_equals_its_edge_fixture_bit_for_bit(name, traced_edges):
+    sc, opts = EDGES[name]
+    plain = ref.triangulate(sc["poses"], sc["offsets"], sc["obs_pose"], sc["obs_xy"], **opts)
+    assert tri_cases.digest(plain) == _maker().load_edges()[name]
+    assert tri_cases.digest(traced_edges[name][:4]) == tri_cases.digest(plain)  # the trace records, it does not compute
+
+
+def _lens(name):
+    return np.diff(EDGES[name][0]["offsets"].astype(np.int64)).tolist()
+
+
+def test_edge_case_list_covers_what_it_names(traced_edges):
+    """by the reference's own results and trace and the cases' own shapes, so that the list cannot decay"""
+    T = traced_edges
+    ok = lambda n: T[n][1].tolist()  # noqa: E731
+    mask = lambda n: T[n][2].astype(int).tolist()  # noqa: E731
+    ntr = lambda n: T[n][3]["num_trials"].tolist()  # noqa: E731
+    tr = lambda n, k: T[n][4][k].tolist()  # noqa: E731
+    # lanes and blocks
+    for n in (1, 63, 64, 65, 255, 256, 257, 513):
+        assert _lens(f"tracks_{n}") == [3] * n and ntr(f"tracks_{n}") == [3] * n
+        assert sum(ok(f"tracks_{n}")) > 0.9 * n
+    # bins and order: ascending lengths, which the sort reverses; above 64 three lengths share a bin
+    lens = _lens("len_bins")
+    assert lens == sorted(lens) and lens == [n for n in (0, 1, 2, 3, 63, 64, 65, 66, 130) for _ in (0, 1)]
+    assert _lens("len_bins_descending") == lens[::-1]
+    a, d = T["len_bins"], T["len_bins_descending"]
+    assert np.array_equal(a[0].view(np.uint64), d[0][::-1].view(np.uint64)) and a[1].tolist() == d[1][::-1].tolist()
+    assert not np.array_equal(a[0][-1].view(np.uint64), a[0][-2].view(np.uint64))  # (the two of a length are not twins)
+    assert tr("len_bins", "dyn_row") == [0] * 8 + [1] * 10 and ntr("len_bins")[:8] == [0, 0, 0, 0, 1, 1, 3, 3]
+    assert tr("len_bins", "abort_trial")[8:] == [1000] * 10 and ntr("len_bins")[8:] == [1002] * 10
+    assert _lens("mixed_wave") == [2 + i % 39 for i in range(70)]
+    # no work
+    sc = EDGES["all_empty"][0]
+    assert len(sc["poses"]) == 0 and len(sc["obs_xy"]) == 0 and _lens("all_empty") == [0] * 5
+    assert _lens("all_single") == [1] * 5 and _lens("empty_around") == [0, 3, 0]
+    for n in ("all_empty", "all_single"):
+        assert not any(ok(n)) and ntr(n) == [0] * 5 and not any(mask(n))
+    assert ok("empty_around") == [False, True, False] and ntr("empty_around") == [0, 3, 0]
+    # sharing
+    sc = EDGES["two_poses"][0]
+    assert set(sc["obs_pose"].tolist()) == {0, 1} and _lens("two_poses") == [3] * 8 and all(ok("two_poses"))
+    sc = EDGES["observation_twice_thrice"][0]
+    assert _lens("observation_twice_thrice") == [4, 5] and all(ok("observation_twice_thrice"))
+    for first, count in ((1, 2), (5, 3)):
+        same = slice(first, first + count)
+        assert len(set(sc["obs_pose"][same].tolist())) == 1 and len({tuple(p) for p in sc["obs_xy"][same].tolist()}) == 1
+    for n in ("one_pose_angle_0", "one_pose_angle_true_min"):
+        assert all(len(set(EDGES[n][0]["obs_pose"][3 * t:3 * t + 3].tolist())) == 1 for t in range(4))
+        assert all(a == 0.0 or math.isnan(a) for a in tr(n, "angle"))  # coincident centres: the angle is 0
+    assert EDGES["one_pose_angle_0"][1]["min_tri_angle"] == 0.0 and any(ok("one_pose_angle_0"))
+    assert sum(tr("one_pose_angle_0", "angle_rejects")) == 0
+    assert EDGES["one_pose_angle_true_min"][1]["min_tri_angle"] == 5e-324 > 0.0
+    assert not any(ok("one_pose_angle_true_min")) and sum(tr("one_pose_angle_true_min", "angle_rejects")) > 0
+    # the RANSAC's limits on 45 pairs: (a table row applies, the trial at which abort was set, num_trials)
+    limits10 = {"min42": (1, 42, 44), "min43": (1, 43, 45), "min44": (1, 44, 45), "min45": (0, -1, 45),
+                "min46": (0, -1, 45), "min0_max0": (0, -1, 0), "min1_max1": (0, -1, 1), "min42_max42": (0, -1, 42),
+                "min41_max42": (1, 41, 42), "confidence0": (0, -1, 0), "confidence1": (1, -1, 45),
+                "ratio0.9": (1, None, 2), "ratio1.0": (1, -1, 1), "multiplier0": (0, -1, 0)}
+    assert sorted(limits10) == sorted(tri_cases.LIMITS_10)
+    for k, (row, abort, trials) in limits10.items():
+        n = f"limit10_{k}"
+        assert _lens(n) == [10] * 4 and tr(n, "dyn_row") == [row] * 4 and ntr(n) == [trials] * 4, n
+        assert abort is None or tr(n, "abort_trial") == [abort] * 4, n
+        assert ok(n) == [trials > 0] * 4 and (trials > 0 or not any(mask(n))), n
+        assert trials == 0 or T[n][3]["num_inliers"].tolist() == [10] * 4, n
+    # ... and on 1 and 3 pairs: the table present for one length and absent for the other in one call (min1)
+    limits23 = {"min0": ([1] * 6, [-1] * 3 + [1] * 3, [1, 1, 1, 3, 3, 3]),
+                "min1": ([0] * 3 + [1] * 3, [-1] * 3 + [1] * 3, [1, 1, 1, 3, 3, 3]),
+                "min2": ([0] * 3 + [1] * 3, [-1] * 3 + [2] * 3, [1, 1, 1, 3, 3, 3]),
+                "min3": ([0] * 6, [-1] * 6, [1, 1, 1, 3, 3, 3]), "min4": ([0] * 6, [-1] * 6, [1, 1, 1, 3, 3, 3]),
+                "min0_max0": ([0] * 6, [-1] * 6, [0] * 6), "min1_max1": ([0] * 6, [-1] * 6, [1] * 6),
+                "min2_max2": ([0] * 6, [-1] * 6, [1, 1, 1, 2, 2, 2]), "confidence0": ([0] * 6, [-1] * 6, [0] * 6),
+                "confidence1": ([1] * 6, [-1] * 6, [1, 1, 1, 3, 3, 3]),
+                "ratio0.9": ([1] * 6, [-1] * 3 + [1] * 3, [1, 1, 1, 2, 2, 2]), "ratio1.0": ([1] * 6, [-1] * 6, [1] * 6),
+                "multiplier0": ([0] * 6, [-1] * 6, [0] * 6)}
+    assert sorted(limits23) == sorted(tri_cases.LIMITS_SHORT)
+    for k, (row, abort, trials) in limits23.items():
+        n = f"limit23_{k}"
+        assert _lens(n) == [2, 2, 2, 3, 3, 3], n
+        assert tr(n, "dyn_row") == row and tr(n, "abort_trial") == abort and ntr(n) == trials, n
+        assert ok(n) == [t > 0 for t in trials], n
+    # support
+    assert ok("two_inliers") == [True] and mask("two_inliers") == [1, 1, 0] and tr("two_inliers", "lo_rounds") == [0]
+    assert tr("local_grows", "lo_max_growing")[0] >= 2 and tr("local_grows", "lo_max_iters")[0] >= 3
+    n = "local_grows_early_stop"
+    assert EDGES[n][0] is EDGES["local_grows"][0] and tr(n, "lo_max_growing")[0] >= 2 and tr(n, "dyn_row") == [1]
+    assert 0 <= tr(n, "abort_trial")[0] and ntr(n)[0] == tr(n, "abort_trial")[0] + 2 < 66 == ntr("local_grows")[0]
+    t = T["local_not_better"][4]
+    assert t["lo_iters"][0] - t["lo_refused"][0] - t["lo_replaced"][0] >= 1
+    assert tr("local_refused", "lo_refused")[0] >= 1 and ok("local_refused") == [True]
+    # thresholds: the mask flips on the one planted observation, between two neighbouring doubles
+    (sc_a, o_a), (sc_w, o_w) = EDGES["residual_above_max_error"], EDGES["residual_within_max_error"]
+    m, r = o_a["max_error"], tr("residual_above_max_error", "residuals")[2]
+    assert sc_a is sc_w and o_w["max_error"] == np.nextafter(m, np.inf) and {**o_a, "max_error": 0} == {**o_w, "max_error": 0}
+    assert m * m < r <= o_w["max_error"] * o_w["max_error"]
+    assert mask("residual_above_max_error") == [1, 1, 0] and mask("residual_within_max_error") == [1, 1, 1]
+    (sc_a, o_a), (sc_b, o_b) = EDGES["angle_at_min_tri_angle"], EDGES["angle_below_min_tri_angle"]
+    a = tr("angle_at_min_tri_angle", "angle")[0]
+    assert sc_a is sc_b and _lens("angle_at_min_tri_angle") == [2]
+    assert o_a["min_tri_angle"] == a and o_b["min_tri_angle"] == np.nextafter(a, np.inf)
+    assert tr("angle_below_min_tri_angle", "angle") == [a]
+    assert ok("angle_at_min_tri_angle") == [True] and tr("angle_at_min_tri_angle", "angle_rejects") == [0]
+    assert ok("angle_below_min_tri_angle") == [False] and tr("angle_below_min_tri_angle", "angle_rejects") == [1]
+    # depth
+    assert tr("behind_one_camera", "depth_rejects") == [2] and ok("behind_one_camera") == [True]
+    assert mask("behind_one_camera") == [1, 0, 1]
+    assert tr("behind_all_cameras", "depth_rejects") == [3] and ok("behind_all_cameras") == [False]
+    # non-finite and extreme: the NaN flag where a NaN is expected, and only there
+    sc = EDGES["negative_zero"][0]
+    P, xy = sc["poses"].reshape(2, -1), sc["obs_xy"].reshape(2, -1)
+    for v in (P, xy):
+        assert np.array_equal(v[0], v[1]) and (v[0] == 0.0).any()
+        assert not np.signbit(v[0][v[0] == 0.0]).any() and np.signbit(v[1][v[1] == 0.0]).all()
+    assert all(ok("negative_zero")) and np.array_equal(T["negative_zero"][0][0], T["negative_zero"][0][1])
+    assert tr("negative_zero", "nan") == [0, 0]
+    sc = EDGES["pixel_1e200"][0]
+    big = np.flatnonzero(np.abs(sc["obs_xy"]).max(axis=1) == 1e200).tolist()
+    with np.errstate(over="ignore"):
+        assert big == [1, 6] and np.isinf(np.float64(1e200) * np.float64(1e200))
+    # (x x overflows: the samples of that observation give no finite point and fail the depth test; its residual is
+    # acos(0)^2, finite)
+    assert tr("pixel_1e200", "depth_rejects") == [3, 3] and tr("pixel_1e200", "nan") == [0, 0]
+    assert [mask("pixel_1e200")[k] for k in big] == [0, 0] and sum(mask("pixel_1e200")) == 6 and all(ok("pixel_1e200"))
+    sc = EDGES["zero_pose"][0]
+    assert not sc["poses"][3].any() and sc["obs_pose"].tolist() == [0, 1, 2, 3]
+    assert tr("zero_pose", "nan") == [1] and mask("zero_pose") == [1, 1, 1, 0] and math.isnan(tr("zero_pose", "residuals")[3])
+    t = EDGES["subnormal_translation"][0]["poses"][0, :, 3]
+    assert (t != 0).all() and (np.abs(t) < np.finfo(np.float64).tiny).all()
+    assert tr("subnormal_translation", "nan") == [0] and mask("subnormal_translation") == [1, 1, 1, 1]
+
+
+RESTATED = sorted(n for n in EDGES if n.startswith("limit")) + ["two_inliers", "local_grows", "local_grows_early_stop",
+                                                                       "local_not_better"]
+
+
+@pytest.mark.parametrize("name", RESTATED)
+def test_numpy_restatement_agrees_on_the_limit_and_support_edges(name, traced_edges):
+    """success, mask and num_trials identical, xyz to 1e-6 relative.  (local_refused and the four threshold cases sit on
+    a threshold to the last bit by construction: there only the reference's own arithmetic decides.)"""
+    sc, opts = EDGES[name]
+    xyz, ok, mask, st, _ = traced_edges[name]
+    off = sc["offsets"].astype(np.int64)
+    for t, (X, m, trials, clear) in enumerate(_np_batch(sc, **opts)):
+        assert clear, (name, t)
+        assert (X is not None) == ok[t] and trials == st["num_trials"][t], (name, t)
+        assert np.array_equal(m, mask[off[t]:off[t + 1]]), (name, t)
+        if X is not None:
+            assert np.allclose(X, xyz[t], rtol=1e-6, atol=0), (name, t)

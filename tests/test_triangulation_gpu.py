@@ -1,6 +1,7 @@
 """Track triangulation on the GPU (libamc.so's amc_triangulate_tracks, pycolmap_amd.estimate_triangulation) against
 its CPU reference (tests/tri_ref/tri_ref.cc): xyz bits, masks, trial and inlier counts and success identical over
-clean, noisy and outlier tracks, short and long tracks, every option, degenerate input, batches in any order."""
+clean, noisy and outlier tracks, short and long tracks, every option, degenerate input, batches in any order; and the
+same over tri_cases.EDGE_CASES, also against their frozen digests, as one shuffled call, and in split calls."""
 import numpy as np
 import pytest
 
@@ -124,3 +125,89 @@ def test_pycolmap_estimate_triangulation_matches_reference():
             assert np.array_equal(np.asarray(r["xyz"]).view(np.uint64), want[0][t].view(np.uint64))
             assert np.array_equal(r["inliers"], want[2][off[t]:off[t + 1]])
         assert nones >= 1
+
+
+# ---- the edge cases (tri_cases.EDGE_CASES) -------------------------------------------------------------
+EDGES = tri_cases.EDGE_CASES
+_REFS = {}
+
+
+def reference(name):
+    """the live reference on a case of EDGES or CASES, computed once and shared"""
+    if name not in _REFS:
+        sc, opts = EDGES[name] if name in EDGES else CASES[name]
+        _REFS[name] = ref.triangulate(sc["poses"], sc["offsets"], sc["obs_pose"], sc["obs_xy"], **opts)
+    return _REFS[name]
+
+
+@pytest.fixture(scope="module")
+def golden_edges():
+    import importlib.util
+    from pathlib import Path
+    spec = importlib.util.spec_from_file_location("mk_tri", Path(__file__).resolve().parent / "golden" / "make_tri_ref_golden.py")
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    return mk.load_edges()
+
+
+@pytest.mark.parametrize("name", sorted(EDGES))
+def test_edge_case_bit_exact_to_reference_and_fixture(amc_ctx, name, golden_edges):
+    sc, opts = EDGES[name]
+    got = run_gpu(amc_ctx, sc, **opts)
+    assert_same(got, reference(name), name)
+    assert tri_cases.digest(got) == golden_edges[name], name
+    assert got[3]["num_batches"] == 1
+
+
+def _option_groups():
+    groups = {}
+    for name in sorted(EDGES):
+        groups.setdefault(tuple(sorted(EDGES[name][1].items())), []).append(name)
+    return [names for names in groups.values() if len(names) > 1]
+
+
+def test_edge_cases_in_one_call_in_any_order(amc_ctx):
+    """the edge cases that share options as one call, tracks shuffled: every track as in its own case's call"""
+    groups = _option_groups()
+    assert len(groups) >= 8 and max(len(g) for g in groups) >= 20
+    for gi, names in enumerate(groups):
+        both = tri_cases.concat(*[EDGES[n][0] for n in names])
+        want = [reference(n) for n in names]
+        T = len(both["offsets"]) - 1
+        perm = np.random.default_rng(1000 + gi).permutation(T)
+        off = both["offsets"].astype(np.int64)
+        idx = np.concatenate([np.arange(off[t], off[t + 1]) for t in perm] + [np.zeros(0, np.int64)])
+        xyz, ok, mask, st = run_gpu(amc_ctx, tri_cases.reorder(both, perm), **EDGES[names[0]][1])
+        wst = {k: np.concatenate([w[3][k] for w in want])[perm] for k in ("num_inliers", "num_trials")}
+        assert_same((xyz, ok, mask, st), (np.concatenate([w[0] for w in want])[perm], np.concatenate([w[1] for w in want])[perm],
+                                          np.concatenate([w[2] for w in want])[idx], wst), f"{names[0]} .. {names[-1]}")
+
+
+def _num_batches(offsets, max_tracks, max_obs):
+    """split_batches' rule: greedily, at most max_tracks tracks and max_obs observations; a longer track alone"""
+    off, T, i, count = [int(o) for o in offsets], len(offsets) - 1, 0, 0
+    while i < T:
+        j = i + 1
+        while j < T and j - i < max_tracks and off[j + 1] - off[i] <= max_obs:
+            j += 1
+        i, count = j, count + 1
+    return count
+
+
+@pytest.mark.parametrize("hook,bound", [("AMC_TRI_BATCH_TRACKS", 1), ("AMC_TRI_BATCH_TRACKS", 64), ("AMC_TRI_BATCH_TRACKS", 65),
+                                        ("AMC_TRI_BATCH_OBS", 1), ("AMC_TRI_BATCH_OBS", 129)])
+@pytest.mark.parametrize("name", ["len_bins", "mixed_wave", "outliers30"])
+def test_split_calls_equal_the_reference(amc_ctx, monkeypatch, name, hook, bound):
+    """a call split into device batches that reuse one set of buffers (the hooks are read per call)"""
+    sc, opts = EDGES[name] if name in EDGES else CASES[name]
+    monkeypatch.setenv(hook, str(bound))
+    got = run_gpu(amc_ctx, sc, **opts)
+    assert_same(got, reference(name), f"{name} {hook}={bound}")
+    lens = np.diff(sc["offsets"].astype(np.int64))
+    want = _num_batches(sc["offsets"], bound if hook.endswith("TRACKS") else 1 << 20, bound if hook.endswith("OBS") else 1 << 23)
+    assert got[3]["num_batches"] == want
+    assert (want > 1) == (hook.endswith("OBS") or len(lens) > bound)
+    if (hook, bound) == ("AMC_TRI_BATCH_TRACKS", 1):
+        assert want == len(lens)
+    if (hook, bound) == ("AMC_TRI_BATCH_OBS", 1):  # every track of two or more observations is a batch of its own
+        assert int((lens >= 2).sum()) <= want <= int((lens >= 1).sum()) + 1

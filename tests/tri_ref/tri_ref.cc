@@ -160,8 +160,40 @@ Vec3 SmallestDehom(double a[4][4]) {
     return Vec3{{v[0][m] / v[3][m], v[1][m] / v[3][m], v[2][m] / v[3][m]}};
 }
 
+// What tri_ref_triangulate_trace reports of one track's RANSAC (the tests prove with it that an edge case is of the
+// kind its name says).  Filling it changes no arithmetic.
+struct Trace {
+    int64_t dyn_row = 0;         // 1: min(max_num_trials', n(n-1)/2) > min_num_trials, the RANSAC can stop early (11.3)
+    int64_t abort_trial = -1;    // the trial at which abort was set, or -1
+    int64_t depth_rejects = 0;   // two-view samples refused by a depth
+    int64_t angle_rejects = 0;   // two-view samples refused by the angle
+    int64_t lo_rounds = 0;       // local optimisations entered
+    int64_t lo_max_iters = 0;    // most iterations of one of them
+    int64_t lo_max_growing = 0;  // most iterations of one of them after which the inlier count had grown
+    int64_t lo_iters = 0;        // iterations of all of them
+    int64_t lo_replaced = 0;     // local models that replaced the best
+    int64_t lo_refused = 0;      // local estimates without a model
+    int64_t nan = 0;             // 1: a residual or an angle was NaN
+    double angle = std::numeric_limits<double>::quiet_NaN();  // the angle that admitted the final model; without a
+                                                              // model, the last angle that refused one
+    double last_angle = std::numeric_limits<double>::quiet_NaN();
+    int why = 0;                 // the last Estimate: 0 a model, 1 refused by a depth, 2 by the angle
+};
+constexpr int kTraceInts = 11;
+
 struct Estimator {
     double min_tri_angle;
+    Trace* tr = nullptr;
+    bool Admit(double angle) const {
+        if (tr) {
+            tr->last_angle = angle;
+            if (angle != angle) tr->nan = 1;
+        }
+        return angle >= min_tri_angle;
+    }
+    void Why(int w) const {
+        if (tr) tr->why = w;
+    }
     // TriangulationEstimator::Estimate: empty or one model
     std::vector<Vec3> Estimate(const std::vector<Obs>& obs) const {
         if (obs.size() == 2) {
@@ -180,10 +212,12 @@ struct Estimator {
                     ata[r][c] = s;
                 }
             const Vec3 X = SmallestDehom(ata);
-            if (Depth(*obs[0].pose, X) >= DBL_EPSILON && Depth(*obs[1].pose, X) >= DBL_EPSILON &&
-                TriAngle(obs[0].pose->C, obs[1].pose->C, X) >= min_tri_angle)
-                return {X};
-            return {};
+            Why(1);
+            if (!(Depth(*obs[0].pose, X) >= DBL_EPSILON && Depth(*obs[1].pose, X) >= DBL_EPSILON)) return {};
+            Why(2);
+            if (!Admit(TriAngle(obs[0].pose->C, obs[1].pose->C, X))) return {};
+            Why(0);
+            return {X};
         }
         double A[4][4] = {};
         for (const Obs& o : obs) {
@@ -200,16 +234,24 @@ struct Estimator {
                 for (int c = 0; c < 4; ++c) A[r][c] = A[r][c] + (T[0][r] * T[0][c] + T[1][r] * T[1][c] + T[2][r] * T[2][c]);
         }
         const Vec3 X = SmallestDehom(A);
+        Why(1);
         for (const Obs& o : obs)
             if (!(Depth(*o.pose, X) >= DBL_EPSILON)) return {};
+        Why(2);
         for (size_t i = 0; i < obs.size(); ++i)
             for (size_t j = 0; j < i; ++j)
-                if (TriAngle(obs[i].pose->C, obs[j].pose->C, X) >= min_tri_angle) return {X};
+                if (Admit(TriAngle(obs[i].pose->C, obs[j].pose->C, X))) {
+                    Why(0);
+                    return {X};
+                }
         return {};
     }
     void Residuals(const std::vector<Obs>& obs, const Vec3& X, std::vector<double>* res) const {
         res->resize(obs.size());
-        for (size_t i = 0; i < obs.size(); ++i) (*res)[i] = Residual(obs[i], X);
+        for (size_t i = 0; i < obs.size(); ++i) {
+            (*res)[i] = Residual(obs[i], X);
+            if (tr && (*res)[i] != (*res)[i]) tr->nan = 1;
+        }
     }
 };
 
@@ -257,8 +299,10 @@ struct Report {
 };
 
 // LORANSAC<TriangulationEstimator, TriangulationEstimator, InlierSupportMeasurer, CombinationSampler>::Estimate
-Report LoRansac(const Options& o, const std::vector<Obs>& obs) {
-    const Estimator est{o.min_tri_angle};
+// (tr, final_res: the trace, filled when given)
+Report LoRansac(const Options& o, const std::vector<Obs>& obs, Trace* tr = nullptr,
+                std::vector<double>* final_res = nullptr) {
+    const Estimator est{o.min_tri_angle, tr};
     Report report;
     const size_t n = obs.size();
     report.mask.assign(n, 0);
@@ -269,10 +313,11 @@ Report LoRansac(const Options& o, const std::vector<Obs>& obs) {
                                                              kNumSamples, o.confidence, o.multiplier));
     const size_t max_num_trials = std::min<size_t>(max_cfg, n * (n - 1) / 2);  // CombinationSampler::MaxNumSamples
     size_t dyn_max_num_trials = max_num_trials;
+    if (tr) tr->dyn_row = max_num_trials > static_cast<size_t>(o.min_num_trials) ? 1 : 0;
     const double max_residual = o.max_error * o.max_error;
     Support best_support;
     Vec3 best_model{{0, 0, 0}};
-    bool abort = false;
+    bool abort = false, have_model = false;
     std::vector<double> res, best_local_res;
     std::vector<Obs> sample(2), inl;
     std::vector<size_t> comb(n);  // CombinationSampler: the first two entries are the sample, next_combination order
@@ -294,28 +339,49 @@ Report LoRansac(const Options& o, const std::vector<Obs>& obs) {
             comb[0] = 0;
             comb[1] = 1;
         }
-        for (const Vec3& m : est.Estimate(sample)) {
+        const std::vector<Vec3> models = est.Estimate(sample);
+        if (tr && models.empty()) (tr->why == 1 ? tr->depth_rejects : tr->angle_rejects) += 1;
+        for (const Vec3& m : models) {
             est.Residuals(obs, m, &res);
             const Support support = Evaluate(res, max_residual);
             if (Better(support, best_support)) {
                 best_support = support;
                 best_model = m;
+                if (tr) {
+                    tr->angle = tr->last_angle;
+                    have_model = true;
+                }
                 if (support.num_inliers > 2) {
+                    if (tr) tr->lo_rounds += 1;
+                    int64_t iters = 0, growing = 0;
                     for (size_t lt = 0; lt < 10; ++lt) {
+                        iters += 1;
                         inl.clear();
                         for (size_t i = 0; i < n; ++i)
                             if (res[i] <= max_residual) inl.push_back(obs[i]);
                         const size_t prev = best_support.num_inliers;
-                        for (const Vec3& lm : est.Estimate(inl)) {
+                        const std::vector<Vec3> local_models = est.Estimate(inl);
+                        if (tr && local_models.empty()) tr->lo_refused += 1;
+                        for (const Vec3& lm : local_models) {
                             est.Residuals(obs, lm, &res);
                             const Support ls = Evaluate(res, max_residual);
                             if (Better(ls, best_support)) {
                                 best_support = ls;
                                 best_model = lm;
                                 std::swap(res, best_local_res);
+                                if (tr) {
+                                    tr->lo_replaced += 1;
+                                    tr->angle = tr->last_angle;
+                                }
                             }
                         }
+                        if (tr) {
+                            tr->lo_iters += 1;
+                            tr->lo_max_iters = std::max(tr->lo_max_iters, iters);
+                        }
                         if (best_support.num_inliers <= prev) break;
+                        growing += 1;
+                        if (tr) tr->lo_max_growing = std::max(tr->lo_max_growing, growing);
                         std::swap(res, best_local_res);
                     }
                 }
@@ -323,17 +389,63 @@ Report LoRansac(const Options& o, const std::vector<Obs>& obs) {
             }
             if (report.num_trials >= dyn_max_num_trials && report.num_trials >= static_cast<size_t>(o.min_num_trials)) {
                 abort = true;
+                if (tr) tr->abort_trial = static_cast<int64_t>(report.num_trials);
                 break;
             }
         }
     }
     report.support = best_support;
-    if (best_support.num_inliers < 2) return report;
+    if (best_support.num_inliers < 2) {
+        if (tr && !have_model) tr->angle = tr->last_angle;
+        return report;
+    }
     report.success = true;
     report.model = best_model;
     est.Residuals(obs, best_model, &res);
+    if (final_res) *final_res = res;
     for (size_t i = 0; i < n; ++i) report.mask[i] = res[i] <= max_residual;
     return report;
+}
+
+int Run(const double* poses, size_t nposes, const uint64_t* offsets, size_t ntracks, const uint32_t* obs_pose,
+        const double* obs_xy, const Options& o, double* xyz, uint8_t* success, uint32_t* num_inliers,
+        uint64_t* num_trials, uint8_t* mask, int64_t* trace, double* trace_angle, double* trace_residuals) {
+    if (offsets[0] != 0) return -1;
+    std::vector<Pose> ps(nposes);
+    for (size_t i = 0; i < nposes; ++i) {
+        Pose& p = ps[i];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) p.P[r][c] = poses[12 * i + 4 * r + c];
+        // 11.1: C = -R^T t
+        for (int c = 0; c < 3; ++c) p.C[c] = -(p.P[0][c] * p.P[0][3] + p.P[1][c] * p.P[1][3] + p.P[2][c] * p.P[2][3]);
+    }
+    std::vector<Obs> obs;
+    std::vector<double> final_res;
+    for (size_t t = 0; t < ntracks; ++t) {
+        if (offsets[t + 1] < offsets[t]) return -1;
+        obs.clear();
+        for (uint64_t k = offsets[t]; k < offsets[t + 1]; ++k) {
+            if (obs_pose[k] >= nposes) return -1;
+            obs.push_back(Obs{obs_xy[2 * k], obs_xy[2 * k + 1], &ps[obs_pose[k]]});
+        }
+        Trace tr;
+        final_res.assign(obs.size(), std::numeric_limits<double>::quiet_NaN());
+        const Report r = trace ? LoRansac(o, obs, &tr, &final_res) : LoRansac(o, obs);
+        for (int c = 0; c < 3; ++c) xyz[3 * t + c] = r.success ? r.model.v[c] : 0.0;
+        success[t] = r.success ? 1 : 0;
+        num_inliers[t] = static_cast<uint32_t>(r.support.num_inliers);
+        num_trials[t] = r.num_trials;
+        for (size_t k = 0; k < obs.size(); ++k) mask[offsets[t] + k] = r.mask[k];
+        if (trace) {
+            const int64_t v[kTraceInts] = {tr.dyn_row,        tr.abort_trial, tr.depth_rejects, tr.angle_rejects,
+                                           tr.lo_rounds,      tr.lo_max_iters, tr.lo_max_growing, tr.lo_iters,
+                                           tr.lo_replaced,    tr.lo_refused,  tr.nan};
+            for (int c = 0; c < kTraceInts; ++c) trace[kTraceInts * t + c] = v[c];
+            trace_angle[t] = tr.angle;
+            for (size_t k = 0; k < obs.size(); ++k) trace_residuals[offsets[t] + k] = final_res[k];
+        }
+    }
+    return 0;
 }
 
 }  // namespace
@@ -353,32 +465,23 @@ int tri_ref_triangulate(const double* poses, size_t nposes, const uint64_t* offs
                         double min_inlier_ratio, double confidence, double multiplier, int64_t min_num_trials,
                         int64_t max_num_trials, double* xyz, uint8_t* success, uint32_t* num_inliers,
                         uint64_t* num_trials, uint8_t* mask) {
-    if (offsets[0] != 0) return -1;
-    std::vector<Pose> ps(nposes);
-    for (size_t i = 0; i < nposes; ++i) {
-        Pose& p = ps[i];
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 4; ++c) p.P[r][c] = poses[12 * i + 4 * r + c];
-        // 11.1: C = -R^T t
-        for (int c = 0; c < 3; ++c) p.C[c] = -(p.P[0][c] * p.P[0][3] + p.P[1][c] * p.P[1][3] + p.P[2][c] * p.P[2][3]);
-    }
     const Options o{min_tri_angle, max_error, min_inlier_ratio, confidence, multiplier, min_num_trials, max_num_trials};
-    std::vector<Obs> obs;
-    for (size_t t = 0; t < ntracks; ++t) {
-        if (offsets[t + 1] < offsets[t]) return -1;
-        obs.clear();
-        for (uint64_t k = offsets[t]; k < offsets[t + 1]; ++k) {
-            if (obs_pose[k] >= nposes) return -1;
-            obs.push_back(Obs{obs_xy[2 * k], obs_xy[2 * k + 1], &ps[obs_pose[k]]});
-        }
-        const Report r = LoRansac(o, obs);
-        for (int c = 0; c < 3; ++c) xyz[3 * t + c] = r.success ? r.model.v[c] : 0.0;
-        success[t] = r.success ? 1 : 0;
-        num_inliers[t] = static_cast<uint32_t>(r.support.num_inliers);
-        num_trials[t] = r.num_trials;
-        for (size_t k = 0; k < obs.size(); ++k) mask[offsets[t] + k] = r.mask[k];
-    }
-    return 0;
+    return Run(poses, nposes, offsets, ntracks, obs_pose, obs_xy, o, xyz, success, num_inliers, num_trials, mask,
+               nullptr, nullptr, nullptr);
+}
+
+// The same, and what each track's RANSAC went through: trace, ntracks x 11 (struct Trace's integers in its order);
+// trace_angle, one per track (Trace::angle); trace_residuals, one per observation: the final model's residuals (NaN in
+// a track without one).
+int tri_ref_triangulate_trace(const double* poses, size_t nposes, const uint64_t* offsets, size_t ntracks,
+                              const uint32_t* obs_pose, const double* obs_xy, double min_tri_angle, double max_error,
+                              double min_inlier_ratio, double confidence, double multiplier, int64_t min_num_trials,
+                              int64_t max_num_trials, double* xyz, uint8_t* success, uint32_t* num_inliers,
+                              uint64_t* num_trials, uint8_t* mask, int64_t* trace, double* trace_angle,
+                              double* trace_residuals) {
+    const Options o{min_tri_angle, max_error, min_inlier_ratio, confidence, multiplier, min_num_trials, max_num_trials};
+    return Run(poses, nposes, offsets, ntracks, obs_pose, obs_xy, o, xyz, success, num_inliers, num_trials, mask, trace,
+               trace_angle, trace_residuals);
 }
 
 }  // extern "C"

@@ -36,13 +36,32 @@ def load() -> C.CDLL:
     lib.tri_ref_triangulate.restype = C.c_int
     lib.tri_ref_triangulate.argtypes = ([C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p] +
                                         [C.c_double] * 5 + [C.c_int64] * 2 + [C.c_void_p] * 5)
+    lib.tri_ref_triangulate_trace.restype = C.c_int
+    lib.tri_ref_triangulate_trace.argtypes = lib.tri_ref_triangulate.argtypes + [C.c_void_p] * 3
     _lib = lib
     return lib
+
+
+# tri_ref_triangulate_trace's integers per track, in struct Trace's order (tests/tri_ref/tri_ref.cc)
+TRACE_FIELDS = ("dyn_row", "abort_trial", "depth_rejects", "angle_rejects", "lo_rounds", "lo_max_iters", "lo_max_growing",
+                "lo_iters", "lo_replaced", "lo_refused", "nan")
 
 
 def triangulate(poses, track_offsets, obs_pose, obs_xy, **opts):
     """The reference on a batch, in Context.triangulate_tracks' form: (xyz (T, 3), success (T,) bool,
     inlier_mask (M,) bool, {"num_inliers", "num_trials"})."""
+    return _run(False, poses, track_offsets, obs_pose, obs_xy, opts)
+
+
+def triangulate_trace(poses, track_offsets, obs_pose, obs_xy, **opts):
+    """triangulate(), and a fifth element: what each track's RANSAC went through, a dict of (T,) int64 arrays named by
+    TRACE_FIELDS (abort_trial is -1 where abort was never set), "angle" (T,) - the triangulation angle that admitted the
+    final model, or without a model the last one that refused one - and "residuals" (M,), the final model's (NaN in a
+    track without a model)."""
+    return _run(True, poses, track_offsets, obs_pose, obs_xy, opts)
+
+
+def _run(trace, poses, track_offsets, obs_pose, obs_xy, opts):
     o = dict(DEFAULTS)
     for k, v in opts.items():
         if k not in o:
@@ -59,13 +78,25 @@ def triangulate(poses, track_offsets, obs_pose, obs_xy, **opts):
     ntr = np.zeros(nt, np.uint64)
     mask = np.zeros(max(m, 1), np.uint8)
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    rc = load().tri_ref_triangulate(ptr(P), P.shape[0], ptr(off), nt, ptr(op), ptr(xy), float(o["min_tri_angle"]),
-                                    float(o["max_error"]), float(o["min_inlier_ratio"]), float(o["confidence"]),
-                                    float(o["dyn_num_trials_multiplier"]), int(o["min_num_trials"]),
-                                    int(o["max_num_trials"]), ptr(xyz), ptr(ok), ptr(ninl), ptr(ntr), ptr(mask))
+    args = [ptr(P), P.shape[0], ptr(off), nt, ptr(op), ptr(xy), float(o["min_tri_angle"]), float(o["max_error"]),
+            float(o["min_inlier_ratio"]), float(o["confidence"]), float(o["dyn_num_trials_multiplier"]),
+            int(o["min_num_trials"]), int(o["max_num_trials"]), ptr(xyz), ptr(ok), ptr(ninl), ptr(ntr), ptr(mask)]
+    if trace:
+        ti = np.zeros((max(nt, 1), len(TRACE_FIELDS)), np.int64)
+        ta = np.zeros(max(nt, 1), np.float64)
+        tres = np.zeros(max(m, 1), np.float64)
+        rc = load().tri_ref_triangulate_trace(*args, ptr(ti), ptr(ta), ptr(tres))
+    else:
+        rc = load().tri_ref_triangulate(*args)
     if rc != 0:
         raise ValueError("tri_ref_triangulate: invalid input")
-    return xyz, ok.astype(bool), mask[:m].astype(bool), {"num_inliers": ninl, "num_trials": ntr}
+    out = (xyz, ok.astype(bool), mask[:m].astype(bool), {"num_inliers": ninl, "num_trials": ntr})
+    if trace:
+        tr = {k: ti[:nt, i].copy() for i, k in enumerate(TRACE_FIELDS)}
+        tr["angle"] = ta[:nt]
+        tr["residuals"] = tres[:m]
+        out += (tr,)
+    return out
 
 
 def acos(x: float) -> float:

@@ -316,9 +316,9 @@ int amc_undistort_camera(const amc_undistort_opts* opts, const amc_undistort_cam
         const double max_scale_y = std::max(cy / (cy - top_max), (uh - 0.5 - cy) / (bottom_min - cy));
         double scale_x = 1.0 / (min_scale_x * o.blank_pixels + max_scale_x * (1.0 - o.blank_pixels));
         double scale_y = 1.0 / (min_scale_y * o.blank_pixels + max_scale_y * (1.0 - o.blank_pixels));
-        scale_x = std::min(std::max(scale_x, o.min_scale), o.max_scale);  // (a NaN scale becomes min_scale)
+        scale_x = std::min(std::max(scale_x, o.min_scale), o.max_scale);  // (a NaN scale stays NaN: no comparison holds)
         scale_y = std::min(std::max(scale_y, o.min_scale), o.max_scale);
-        const double nw = std::max(1.0, scale_x * uw), nh = std::max(1.0, scale_y * uh);
+        const double nw = std::max(1.0, scale_x * uw), nh = std::max(1.0, scale_y * uh);  // (... and gives one sample)
         if (!(nw <= (double)kMaxSide) || !(nh <= (double)kMaxSide))
             return api_fail(AMC_E_INVALID, "amc_undistort_camera: the undistorted size %g x %g is out of range", nw, nh);
         const double new_w = (double)(uint64_t)nw, new_h = (double)(uint64_t)nh;

@@ -16,6 +16,7 @@ from pycolmap_amd import _capi
 
 ROOT = Path(__file__).resolve().parent.parent
 GOLDEN = ROOT / "tests" / "golden" / "undistort_ref_v1.npz"
+EDGES_GOLDEN = ROOT / "tests" / "golden" / "undistort_ref_edges_v1.npz"
 RECORDED = ROOT / "tests" / "golden" / "undistort_pycolmap_v1.npz"
 OPTION_FIELDS = dict(blank_pixels=0.0, min_scale=0.2, max_scale=2.0, max_image_size=-1, roi_min_x=0.0, roi_min_y=0.0,
                      roi_max_x=1.0, roi_max_y=1.0)
@@ -287,26 +288,28 @@ def np_rescaled(model, params, sx, sy):
     return p
 
 
-@pytest.mark.parametrize("case", cases.warp_cases(), ids=lambda c: c[0])
+@pytest.mark.parametrize("case", cases.warp_cases() + cases.edge_cases(), ids=lambda c: c[0])
 def test_reference_warp_against_numpy_restatement(case):
     """Conditions, not measurements: where both call a pixel inside, the reference's byte is the numpy value rounded
     (|byte - value| <= 0.5 + 1e-6: the project's atan is within one ulp of numpy's, which moves a coordinate by parts in
-    1e-13 and a value by less than 1e-9); inside / outside may differ only within 1e-9 of a bound."""
-    name, img, cam, opts = case
+    1e-13 and a value by less than 1e-9); inside / outside may differ only within 1e-9 of a bound.  A case carries
+    either undistort_camera's options or (the edge list) the target camera itself."""
+    name, img, cam, target = case
     model, sw, sh, params = cam
-    und = ref.undistort_camera(cam, **opts)
+    und = ref.undistort_camera(cam, **target) if isinstance(target, dict) else target
     dw, dh = und[1], und[2]
     out, vals, coords = ref.warp(img, cam, und, details=True)
     src = np.ascontiguousarray(img)
     if dw * dh < sw * sh:  # the pre-pass (checked on its own below): resized pixels, Camera::Rescale(dw, dh)
         src = ref.resize(src, dw, dh)
         params = np_rescaled(model, params, dw / sw, dh / sh)
-    want, inside, margin = np_warp(src, model, params, und[3], dw, dh)
+    with np.errstate(all="ignore"):  # the (h) cases overflow on purpose
+        want, inside, margin = np_warp(src, model, params, und[3], dw, dh)
     ref_inside = vals[..., 0] >= 0
     differ = ref_inside != inside
     assert np.all(margin[differ] <= 1e-9), (name, int(differ.sum()))
     both = ref_inside & inside
-    assert both.any() or name == "SIMPLE_RADIAL-2x2-3ch"
+    assert both.any() or name == "SIMPLE_RADIAL-2x2-3ch" or "black" in name
     o3 = out.reshape(dh, dw, -1).astype(np.float64)
     assert np.all(np.abs(o3[both] - want[both]) <= 0.5 + 1e-6), name
     assert np.all(np.abs(vals[both] - want[both]) <= 1e-6), name
@@ -326,8 +329,13 @@ def np_axis_matrix(n_in, n_out):
     return m / m.sum(axis=1, keepdims=True)
 
 
+def window_shapes():
+    """The (source, target) shapes of the edge list's windows as (array shape, dw, dh)."""
+    return [((sh, sw) + ((3,) if ch == 3 else ()), dw, dh) for (sw, sh), (dw, dh), ch in cases.WINDOWS]
+
+
 @pytest.mark.parametrize("shape, dw, dh", [((45, 67, 3), 30, 45), ((45, 67), 67, 20), ((45, 67), 66, 42), ((9, 5, 3), 2, 9),
-                                           ((7, 40), 13, 7)])
+                                           ((7, 40), 13, 7)] + window_shapes())
 def test_reference_resize_against_numpy_restatement(shape, dw, dh):
     img = cases.make_image(shape[0], shape[1], 1 if len(shape) == 2 else 3, 500 + dw)
     a = img.reshape(shape[0], shape[1], -1).astype(np.float64)
@@ -351,6 +359,267 @@ def test_identity_warp_blanks_the_top_row_and_the_last_column():
         out = ref.warp(img, cam, (1, cases.W, cases.H, cam[3]))
         assert np.array_equal(out[1:, :-1], img[1:, :-1])
         assert np.all(out[0] == 0) and np.all(out[:, -1] == 0)
+
+
+# ---- the edge list ------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def edge_reference():
+    """{name: (image, source camera, target camera, reference image, values before rounding, source coordinates)},
+    computed once and left unchanged."""
+    out = {}
+    for name, img, cam, dst in cases.edge_cases():
+        warped, vals, coords = ref.warp(img, cam, dst, details=True)
+        for a in (warped, vals, coords):
+            a.setflags(write=False)
+        out[name] = (img, cam, dst, warped, vals, coords)
+    return out
+
+
+def axis_window_lengths(n_in, n_out):
+    """14.4's window of every output sample, zero weights included: min(int(c + width + 0.5), n) - max(0, int(c - width + 0.5))."""
+    scale = n_out / n_in
+    width = 1 / scale if scale < 1 else 1.0
+    centers = [u / scale + 0.5 / scale for u in range(n_out)]
+    return np.array([min(int(c + width + 0.5), n_in) - max(0, int(c - width + 0.5)) for c in centers])
+
+
+# the longest window per (in, out) pair, counted by hand from 14.4: about 2 in / out samples for a reduction (1000 -> 3:
+# centres 166.67, 500, 833.33 and width 333.33, the middle window is int(833.83) - int(167.17) = 833 - 167), three for
+# an enlargement at most (width 1 around a centre: int(c + 1.5) - int(c - 0.5), here 2 as no centre of 7 -> 100 has a
+# fraction of exactly one half); 64 -> 63 has width 64 / 63 and int(c + 1.516) - int(c - 0.516) = 2 for its centres
+# u + 0.5 + (u + 0.5) / 63; 67 -> 22 would reach 7 only at u = 21, where the image's end clips it
+LONGEST_WINDOW = {(1000, 3): 666, (300, 7): 86, (300, 2): 225, (257, 1): 257, (64, 1): 64, (64, 16): 8, (64, 32): 4,
+                  (64, 63): 2, (67, 22): 6, (45, 15): 6, (7, 100): 2}
+
+
+def test_edge_case_list_reaches_what_it_names(edge_reference):
+    """From the shapes and the reference's details alone: the list holds the edges 14.6 names."""
+    names = [c[0] for c in cases.edge_cases()]
+    assert len(set(names)) == len(names) == len(edge_reference) and 100 <= len(names) <= 160
+    shape = {n: (r[1][1], r[1][2], r[2][1], r[2][2]) for n, r in edge_reference.items()}  # sw, sh, dw, dh
+    inside = {n: r[4][..., 0] >= 0 for n, r in edge_reference.items()}
+    prepass = {n: s[2] * s[3] < s[0] * s[1] for n, s in shape.items()}
+    for n, (sw, sh, dw, dh) in shape.items():
+        assert max(sw * sh, dw * dh) <= 12000, n  # a few thousand pixels each
+        img, warped = edge_reference[n][0], edge_reference[n][3]
+        assert img.shape[:2] == (sh, sw) and warped.shape[:2] == (dh, dw) and warped.shape[2:] == img.shape[2:], n
+        if "black" in n:  # a side of 1 in the image the warp reads: nothing can be inside
+            assert not inside[n].any() and not warped.any() and prepass[n] and min(dw, dh) == 1, n
+        else:
+            assert inside[n].any(), n
+
+    def tail_is_inside_with_data(n):
+        dw, dh = shape[n][2:]
+        k = (dw * dh) % 4 or 4  # the last group: the partial one, or a full one
+        flat_inside = inside[n].reshape(-1)
+        flat = edge_reference[n][3].reshape(dw * dh, -1)
+        assert flat_inside[-k:].all() and flat[-k:].any(axis=1).all(), n
+
+    # a. every tail length for both channel counts, without and with the pre-pass, data in the tail pixels
+    for ch in (1, 3):
+        for pre in ("", "-prepass"):
+            tails = set()
+            for dw, dh in cases.GROUP_TAILS:
+                n = f"a-tail-{dw}x{dh}-{ch}ch{pre}"
+                assert prepass[n] == bool(pre) and edge_reference[n][0].reshape(shape[n][1], shape[n][0], -1).shape[2] == ch
+                tail_is_inside_with_data(n)
+                tails.add((dw * dh) % 4)
+            assert tails == {0, 1, 2, 3}
+    assert min(s[2] * s[3] for s in shape.values()) == 1 and sorted({s[2] for n, s in shape.items() if n[0] == "b"}) == [1, 2, 3, 5]
+    # b. one group of four pixels spans 4, 2, 2 and 1 to 2 rows
+    assert [-(-4 // dw) for (dw, dh), _ in cases.NARROW] == [4, 2, 2, 1]
+    for n in names:
+        if n.startswith("b-narrow"):
+            assert not prepass[n] and inside[n].all(), n
+    # c. the warp's pixel counts: 63 | 64 | 65 and 255 | 256 | 257 groups, each also with a one-pixel tail
+    c_counts = {}
+    for n in names:
+        if n.startswith("c-"):
+            c_counts.setdefault(shape[n][2] * shape[n][3], []).append(n)
+            ch = edge_reference[n][0].reshape(shape[n][1], shape[n][0], -1).shape[2]
+            assert ch == (3 if shape[n][2] * shape[n][3] % 4 == 1 else 1), n
+            if "black" not in n:
+                assert not prepass[n]
+                tail_is_inside_with_data(n)
+    assert sorted(c_counts) == [252, 253, 256, 257, 260, 1020, 1021, 1024, 1025, 1028]
+    assert sorted({-(-k // 4) for k in c_counts}) == [63, 64, 65, 255, 256, 257]
+    assert all(any("black" not in n for n in v) for v in c_counts.values())  # every count also with pixels in it
+    # d. the resize kernels' sample counts
+    first = sorted(shape[n][2] * shape[n][1] for n in names if n.startswith("d-first"))
+    second = sorted(shape[n][2] * shape[n][3] for n in names if n.startswith("d-second"))
+    assert first == [255, 256, 257] and second == [255, 256, 257]
+    assert all(prepass[n] for n in names if n.startswith("d-"))
+    assert sum("black" not in n for n in names if n.startswith("d-")) == 5  # 257 = 1 x 257 only: that one is black
+    # e. every window pair on x and on y, the longest window restated from 14.4 and within the device's table bound
+    on_x = {(shape[n][0], shape[n][2]) for n in names if n.startswith("e-")}
+    on_y = {(shape[n][1], shape[n][3]) for n in names if n.startswith("e-")}
+    assert all(prepass[n] for n in names if n.startswith("e-"))
+    assert set(cases.WINDOW_PAIRS) == set(LONGEST_WINDOW)
+    for n_in, n_out in cases.WINDOW_PAIRS:
+        assert (n_in, n_out) in on_x and (n_in, n_out) in on_y, (n_in, n_out)
+        lengths = axis_window_lengths(n_in, n_out)
+        m = np_axis_matrix(n_in, n_out)
+        assert lengths.max() == LONGEST_WINDOW[(n_in, n_out)] and lengths.min() >= 1, (n_in, n_out, lengths.max())
+        assert np.all((m > 0).sum(axis=1) <= lengths) and np.all((m > 0).sum(axis=1) >= 1)  # no empty window (14.4's fallback)
+        assert lengths.max() <= 2 * (n_in // n_out + 1) + 3  # undistort.hip sizes a batch's weight table by this
+    sw, sh, dw, dh = shape["e-window-7x300-to-100x2-1ch"]
+    assert dw > sw and dw * dh < sw * sh  # an axis enlarged inside a resized image
+    # f. the eleven models through a pre-pass that enlarges x and reduces y; 11 % .. 100 % inside
+    f_names = [n for n in names if n.startswith("f-")]
+    assert {n.split("-")[2] for n in f_names} == set(cases.CAMERAS)
+    for n in f_names:
+        assert shape[n] == (cases.W, cases.H, 100, 9) and prepass[n] and 0.11 <= inside[n].mean() <= 1.0, (n, inside[n].mean())
+    # g. the half-pixel shifts decide many bytes by round half up
+    a = edge_reference["g-halfx-1ch"][0].astype(int)
+    assert ((a[1:, :-1] + a[1:, 1:]) % 2 == 1).mean() > 0.3
+    a = edge_reference["g-halfy-3ch"][0].astype(int)
+    assert ((a[:-1, :-1] + a[1:, :-1]) % 2 == 1).mean() > 0.3
+    a = edge_reference["g-halfxy-1ch"][0].astype(int)
+    quarters = (a[:-1, :-1] + a[:-1, 1:] + a[1:, :-1] + a[1:, 1:]) % 4
+    assert (quarters == 2).mean() > 0.15 and ((quarters == 1) | (quarters == 3)).mean() > 0.3  # .5 up, .25 and .75 not
+    for n in names:
+        if n.startswith("g-"):  # every coordinate is a multiple of 1 / 8
+            co = edge_reference[n][5]
+            assert np.array_equal(co * 8, np.round(co * 8)), n
+    # h. the split of the huge coordinates
+    h_names = [n for n in names if n.startswith("h-")]
+    assert len(h_names) == 11 * len(cases.HUGE_FOCALS) * len(cases.HUGE_TARGETS)
+    for n in h_names:
+        model, focal = n.split("-")[2], float("-".join(n.split("-")[3:5]))
+        co = edge_reference[n][5]
+        assert prepass[n] == (shape[n][2:] == (21, 15)) and inside[n][7, 10], n  # u = v = 0 on pixel (10, 7)
+        if model in ("RADIAL", "OPENCV", "FULL_OPENCV"):
+            assert np.isnan(co).any(), n
+        if model in ("SIMPLE_PINHOLE", "PINHOLE") or (model == "SIMPLE_RADIAL" and focal == 1e-150):
+            assert not np.isnan(co).any() and (np.isinf(co).any() or np.abs(co).max() > 1e100), n
+        if model in cases.POLYNOMIAL:
+            assert inside[n].sum() == 1, n
+        elif model in ("FOV", "THIN_PRISM_FISHEYE") and focal == 1e-150:
+            # r is finite here: atan(r) / r leaves a point about pi / 2 (FOV: pi / (2 omega)) from the axis, which is
+            # finite, ordinary and far outside the 67 x 45 source; only the pixel on the principal point is inside
+            assert np.isfinite(co).all() and inside[n].sum() == 1 and np.abs(co).max() < 1e3, n
+        else:  # r overflows to infinity, or u * theta_d / r - u absorbs into -u: every pixel lands on the principal point
+            assert np.isfinite(co).all() and inside[n].all(), n
+    # i. u = v = 0 exactly on a pixel centre: the source coordinate is the (rescaled) principal point, bit for bit
+    for model in ("OPENCV_FISHEYE", "SIMPLE_RADIAL_FISHEYE", "RADIAL_FISHEYE", "THIN_PRISM_FISHEYE"):
+        (n,) = [k for k in names if k.startswith(f"i-centre-{model}-")]
+        _, _, cx, cy = cases.focal_and_principal_point(edge_reference[n][1])
+        assert np.array_equal(edge_reference[n][5][7, 10], [cx * (21 / cases.W), cy * (15 / cases.H)]) and inside[n][7, 10], n
+    for n in names:
+        if n.startswith("i-fov-omega"):
+            assert edge_reference[n][1][3][4] ** 2 < 1e-4
+    dst = edge_reference["i-fov-small-radius-1ch"][2][3]
+    y, x = np.mgrid[0:50, 0:70]
+    r2 = ((x + 0.5 - dst[2]) / dst[0]) ** 2 + ((y + 0.5 - dst[3]) / dst[1]) ** 2
+    assert 4 <= (r2 < 1e-4).sum() < r2.size / 4  # both of FOV's radius branches in one image
+    # j. saturation: the inside bytes are exactly 255 and 0
+    for value in (255, 0):
+        for size in ("130x90", "30x20"):
+            n = f"j-all-{value}-{size}-3ch"
+            assert inside[n].all() and np.all(edge_reference[n][3] == value) and prepass[n] == (size == "30x20"), n
+    board = edge_reference["j-checkerboard-64-to-63-1ch"][0]
+    assert set(np.unique(board)) == {0, 255} and np.all(board[:, 1:] != board[:, :-1]) and np.all(board[1:] != board[:-1])
+    # k. the layouts
+    assert edge_reference["k-rows-subsampled-3ch"][0].strides[0] == 2 * cases.W * 3
+    assert edge_reference["k-trailing-1-axis"][0].shape == (cases.H, cases.W, 1)
+    assert edge_reference["k-fortran-order-3ch"][0].flags.f_contiguous and not edge_reference["k-fortran-order-3ch"][0].flags.c_contiguous
+    assert edge_reference["k-negative-row-stride-1ch"][0].strides[0] < 0
+
+
+def test_known_answers_on_the_reference(edge_reference):
+    """The (g) cases against integer arithmetic (cases.known_answers): round half up at exact ties, the strict bounds,
+    a negative focal length, and the pre-pass seen through an identity warp."""
+    answers = cases.known_answers()
+    assert sorted(answers) == sorted(n for n in edge_reference if n.startswith("g-")) and len(answers) == 8
+    for name, (want, pinned) in answers.items():
+        got = edge_reference[name][3]
+        assert pinned.all(), name  # (the pre-pass seeds leave no byte to an FP tie)
+        assert np.array_equal(got, want), (name, int((got != want).sum()))
+        assert np.all(got[:, -1] == 0) and (np.all(got[-1] == 0) if "halfy" in name or "halfxy" in name else np.all(got[0] == 0))
+
+
+def test_int_resize_is_the_numpy_restatement():
+    """The integer statement of 14.4 for a reduction by 4 against the dense float64 matrix: the same windows, weights
+    equal to within rounding."""
+    for n_in, n_out in ((64, 16), (48, 12)):
+        m = np_axis_matrix(n_in, n_out)
+        for u, (left, w, d) in enumerate(cases.int_axis_weights(n_in, n_out)):
+            row = np.zeros(n_in)
+            row[left:left + len(w)] = np.array(w) / d
+            assert np.allclose(m[u], row, rtol=0, atol=1e-15), (n_in, u)
+
+
+def test_saturated_images_stay_saturated_through_the_resize():
+    """Normalised weights may sum to just above 1: 255 times that sum must clamp to 255, not wrap."""
+    above = 0
+    for n_in, n_out in cases.WINDOW_PAIRS + [(67, 30), (45, 20)]:
+        m = np_axis_matrix(n_in, n_out)
+        above += int(np.any(np.array([sum(row[row > 0]) for row in m]) > 1.0))
+    assert above > 0  # (sequential sums of the normalised weights, as the reference accumulates them)
+    for shape, dw, dh in window_shapes() + [((45, 67, 3), 30, 20)]:
+        for value in (255, 0):
+            assert np.all(ref.resize(np.full(shape, value, np.uint8), dw, dh) == value), (shape, dw, dh)
+
+
+def test_edge_reference_against_frozen_fixture(edge_reference):
+    fx = np.load(EDGES_GOLDEN)
+    assert sorted({k.split("/")[0] for k in fx.files}) == sorted(edge_reference)
+    full = 0
+    for name, (img, cam, dst, warped, vals, coords) in edge_reference.items():
+        assert bytes(fx[f"{name}/input_digest"]).decode() == cases.digest(img), name
+        assert bytes(fx[f"{name}/digest"]).decode() == cases.digest(warped), name
+        assert int(fx[f"{name}/inside"]) == int((vals[..., 0] >= 0).sum()), name
+        if f"{name}/image" in fx.files:
+            assert np.array_equal(fx[f"{name}/image"], warped), name
+            full += 1
+    assert full == 6
+
+
+# ---- undistort_camera at its edges (14.2) --------------------------------------------------------------------------------------
+CAMERA_EDGES = [
+    ("roi-1x1", {}, dict(roi_min_x=0.5, roi_max_x=0.505, roi_min_y=0.5, roi_max_y=0.51)),  # round(33.5) = round(33.8) = 34
+    ("roi-min-near-1", {}, dict(roi_min_x=0.999, roi_min_y=0.999)),                        # round(66.9) = 67 -> W - 1
+    ("one-scale-blank-0", {}, dict(blank_pixels=0.0, min_scale=0.7, max_scale=0.7)),
+    ("one-scale-blank-half", {}, dict(blank_pixels=0.5, min_scale=0.7, max_scale=0.7)),
+    ("one-scale-blank-1", {}, dict(blank_pixels=1.0, min_scale=0.7, max_scale=0.7)),
+    ("max_image_size-1", {}, dict(max_image_size=1)),
+    ("max_image_size-1-flat", dict(height=20), dict(max_image_size=1)),
+]
+
+
+@pytest.mark.parametrize("model", list(cases.CAMERAS))
+@pytest.mark.parametrize("label, size, opts", CAMERA_EDGES, ids=[c[0] for c in CAMERA_EDGES])
+def test_undistort_camera_edges_equal_the_reference(model, label, size, opts):
+    cam = cases.camera(model, height=size.get("height", cases.H))
+    und = _capi.undistort_camera(cam, **opts)
+    assert same_camera(und, ref.undistort_camera(cam, **opts)), (und, ref.undistort_camera(cam, **opts))
+    if label == "roi-1x1":       # a one-pixel window times a scale of at most max_scale = 2
+        assert 1 <= und[1] <= 2 and 1 <= und[2] <= 2
+    elif label == "roi-min-near-1":
+        # x0 = W - 1, y0 = H - 1: a one-pixel window again, the principal point moved by (W - 1, H - 1)
+        assert 1 <= und[1] <= 2 and 1 <= und[2] <= 2 and und[3][2] < 0 and und[3][3] < 0
+    elif label.startswith("one-scale") and model not in ("PINHOLE", "SIMPLE_PINHOLE"):
+        assert (und[1], und[2]) == (int(0.7 * cases.W), int(0.7 * cases.H))  # whatever blank_pixels weighs
+    elif label == "max_image_size-1":      # s = 1 / W'': round(s W'') = 1 and round(s H'') = round(H'' / W'') = 1
+        assert (und[1], und[2]) == (1, 1) and und[3][1] > 0
+    elif label == "max_image_size-1-flat":
+        # 14.2 step 5: round(s H'') = 0 for H'' < W'' / 2; the size is clamped to 1, the factor 0 / H'' is not
+        assert (und[1], und[2]) == (1, 1) and und[3][1] == 0.0 and und[3][3] == 0.0 and und[3][0] > 0
+
+
+def test_undistort_camera_with_a_nan_scale():
+    """SIMPLE_RADIAL without distortion and cx = 0.5: the left border lifts to x = cx, so cx / (cx - left) = inf on both
+    the min and the max side; max_scale_x = inf.  blank_pixels = 1 weighs it with 0: inf * 0 = NaN.  14.2 step 4: a NaN
+    passes min(max(scale, min_scale), max_scale) unchanged (every comparison with it is false) and max(1.0, NaN * W) is
+    1.0: the axis gets one sample.  blank_pixels < 1 gives 1 / inf = 0, clamped to min_scale."""
+    cam = ("SIMPLE_RADIAL", cases.W, cases.H, [58.0, 0.5, 22.5, 0.0])
+    for blank, width in ((1.0, 1), (0.5, int(0.2 * cases.W)), (0.0, int(0.2 * cases.W))):
+        und = _capi.undistort_camera(cam, blank_pixels=blank)
+        assert same_camera(und, ref.undistort_camera(cam, blank_pixels=blank)) and und[1] == width, (blank, und)
+        assert und[3][2] == 0.5 * width / cases.W
+    cam = ("SIMPLE_RADIAL", cases.W, cases.H, [58.0, 33.5, 0.5, 0.0])  # the same on y
+    und = _capi.undistort_camera(cam, blank_pixels=1.0, min_scale=0.5)
+    assert same_camera(und, ref.undistort_camera(cam, blank_pixels=1.0, min_scale=0.5)) and und[2] == 1
 
 
 def test_own_atan_within_one_ulp_of_numpy():

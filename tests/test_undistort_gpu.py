@@ -1,7 +1,9 @@
 """GPU checks of undistortion: Context.undistort_images against the CPU reference
-(tests/undistort_ref) and the frozen fixture, batch independence, the pybind building blocks, undistort_images end to
-end on a tiny workspace, and the error paths.  Every comparison is exact: uint8 arrays equal, camera parameters equal
-bit for bit."""
+(tests/undistort_ref) and the frozen fixtures on the warp cases and on the edge list (group tails, wave and block
+boundaries, long windows, exact ties, coordinates that are not finite), the edge list's known answers in integer
+arithmetic, batch independence and the batch count at its bound, the pybind building blocks, undistort_images end to
+end on a tiny workspace and through several device calls, and the error paths.  Every comparison is exact: uint8
+arrays equal, camera parameters equal bit for bit."""
 import json
 import os
 import subprocess
@@ -20,6 +22,7 @@ from pycolmap_amd import _capi
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 GOLDEN = ROOT / "tests" / "golden" / "undistort_ref_v1.npz"
+EDGES_GOLDEN = ROOT / "tests" / "golden" / "undistort_ref_edges_v1.npz"
 
 
 def bits(a):
@@ -121,6 +124,152 @@ def test_pybind_building_blocks_equal_the_capi(amc_ctx, reference):
         pycolmap_amd.undistort_image({}, np.zeros((2, 2), np.uint8), pycolmap_amd.Camera("PINHOLE", 67, 45, [60, 60, 33, 22]))
     with pytest.raises(ValueError, match="uint8"):
         pycolmap_amd.undistort_image({}, np.zeros((45, 67), np.float32), pycolmap_amd.Camera("PINHOLE", 67, 45, [60, 60, 33, 22]))
+
+
+# ---- the edge list (DESIGN.md 14.6): targets given directly ---------------------------------------------------------------------
+EDGE_NAMES = [c[0] for c in cases.edge_cases()]
+
+
+@pytest.fixture(scope="module")
+def edge_reference():
+    """[(name, image, source camera, target camera, reference image)], computed once and left unchanged."""
+    out = []
+    for name, img, cam, dst in cases.edge_cases():
+        want = ref.warp(img, cam, dst)
+        want.setflags(write=False)
+        out.append((name, img, cam, dst, want))
+    return out
+
+
+@pytest.fixture(scope="module")
+def edge_fixture_digests():
+    fx = np.load(EDGES_GOLDEN)
+    return {name: bytes(fx[f"{name}/digest"]).decode() for name in EDGE_NAMES}
+
+
+def takes_the_prepass(cam, dst):
+    return dst[1] * dst[2] < cam[1] * cam[2]  # 14.4
+
+
+@pytest.mark.parametrize("index", range(len(EDGE_NAMES)), ids=EDGE_NAMES)
+def test_edge_case_equals_reference_and_fixture(amc_ctx, edge_reference, edge_fixture_digests, index):
+    name, img, cam, dst, want = edge_reference[index]
+    outs, st = amc_ctx.undistort_images([img], [cam], [dst])
+    assert outs[0].shape == (dst[2], dst[1]) + img.shape[2:] and outs[0].shape == want.shape and outs[0].dtype == np.uint8
+    assert np.array_equal(outs[0], want), f"{name}: {int((outs[0] != want).sum())} bytes differ"
+    assert cases.digest(outs[0]) == edge_fixture_digests[name]
+    assert st["num_batches"] == 1 and st["num_resized"] == int(takes_the_prepass(cam, dst))
+
+
+def test_known_answers_on_the_device(amc_ctx):
+    """The (g) cases against integer arithmetic alone (cases.known_answers), whatever the reference says."""
+    by = {c[0]: c for c in cases.edge_cases()}
+    answers = cases.known_answers()
+    assert len(answers) == 8
+    for name, (want, pinned) in answers.items():
+        _, img, cam, dst = by[name]
+        outs, _ = amc_ctx.undistort_images([img], [cam], [dst])
+        assert pinned.all() and np.array_equal(outs[0], want), (name, int((outs[0] != want).sum()))
+
+
+def test_edge_batch_independence(amc_ctx, edge_reference):
+    imgs, src, dst = [r[1] for r in edge_reference], [r[2] for r in edge_reference], [r[3] for r in edge_reference]
+    single = [amc_ctx.undistort_images([i], [s], [d])[0][0] for i, s, d in zip(imgs, src, dst)]
+    resized = sum(takes_the_prepass(s, d) for s, d in zip(src, dst))
+    assert 40 <= resized <= len(imgs) - 40  # both paths many times in one batch
+    outs, st = amc_ctx.undistort_images(imgs, src, dst)
+    assert st["num_batches"] == 1 and st["num_resized"] == resized
+    for r, o, s in zip(edge_reference, outs, single):
+        assert np.array_equal(o, s) and np.array_equal(o, r[4]), r[0]
+    order = np.random.default_rng(5).permutation(len(imgs))
+    shuffled, st = amc_ctx.undistort_images([imgs[k] for k in order], [src[k] for k in order], [dst[k] for k in order])
+    assert st["num_batches"] == 1 and st["num_resized"] == resized
+    for k, o in zip(order, shuffled):
+        assert np.array_equal(o, single[k]), edge_reference[k][0]
+
+
+def test_one_array_as_two_jobs_of_a_call(amc_ctx, edge_reference):
+    by = {r[0]: r for r in edge_reference}
+    a, b = by["e-window-67x45-to-22x15-3ch"], by["k-fortran-order-3ch"]  # both RADIAL on 67 x 45, three channels
+    assert a[2][0] == b[2][0] and np.array_equal(a[2][3], b[2][3]) and a[1].shape == b[1].shape
+    img = a[1]
+    jobs = [a[3], b[3], cases.pinhole(67, 45, 58.0, 58.0, 33.25, 22.5), a[3]]  # with and without the pre-pass, one twice
+    want = [ref.warp(img, a[2], d) for d in jobs]
+    outs, st = amc_ctx.undistort_images([img] * len(jobs), [a[2]] * len(jobs), jobs)
+    assert st["num_resized"] == 2
+    for o, w in zip(outs, want):
+        assert np.array_equal(o, w)
+    assert np.array_equal(outs[0], outs[3]) and outs[0] is not outs[3] and np.array_equal(outs[0], a[4])
+
+
+EDGE_CHILD = """
+import json, sys
+sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
+import numpy as np
+import undistort_cases as cases
+from pycolmap_amd import _capi
+cs = {cases_expr}
+with _capi.Context(0) as ctx:
+    outs, st = ctx.undistort_images([c[1] for c in cs], [c[2] for c in cs], [c[3] for c in cs])
+print(json.dumps(dict(num_batches=st["num_batches"], num_resized=st["num_resized"], digests=[cases.digest(o) for o in outs])))
+"""
+
+
+def run_child(cases_expr, batch_bytes):
+    """One Context.undistort_images call in a fresh process under AMC_UNDISTORT_BATCH_BYTES (read per call)."""
+    code = EDGE_CHILD.format(root=str(ROOT), tests=str(ROOT / "tests"), cases_expr=cases_expr)
+    child = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120,
+                           env=dict(os.environ, AMC_UNDISTORT_BATCH_BYTES=str(batch_bytes)))
+    assert child.returncode == 0, child.stderr[-2000:]
+    return json.loads(child.stdout.strip().splitlines()[-1])
+
+
+def test_every_edge_case_a_batch_of_its_own(edge_reference, edge_fixture_digests):
+    """A bound below the smallest image: one batch per image, each at offset 0 of the one allocation, the pre-pass
+    tables in memory that earlier batches used."""
+    got = run_child("cases.edge_cases()", 1)
+    assert got["num_batches"] == len(edge_reference)
+    assert got["num_resized"] == sum(takes_the_prepass(r[2], r[3]) for r in edge_reference)
+    assert got["digests"] == [edge_fixture_digests[r[0]] for r in edge_reference]
+
+
+def align256(n):
+    return (n + 255) // 256 * 256
+
+
+SEVEN = ("[('seven-%d' % k, cases.make_image(cases.H, cases.W, 3, 900 + k), cases.camera('OPENCV'), "
+         "cases.pinhole(70, 50, 62.0, 64.0, 35.0, 24.75)) for k in range(7)]")
+
+
+@pytest.mark.parametrize("short_by, per_batch", [(0, 2), (1, 1)])
+def test_batch_count_at_the_bound(short_by, per_batch):
+    """14.5: an image without the pre-pass takes align256(source bytes) + align256(target bytes) of a batch; batches are
+    greedy runs under the bound, the bound included."""
+    per_image = align256(cases.W * cases.H * 3) + align256(70 * 50 * 3)
+    assert per_image == 9216 + 10752 and 70 * 50 >= cases.W * cases.H
+    want_batches = -(-7 // per_batch)
+    assert want_batches == (4, 7)[short_by]
+    got = run_child(SEVEN, 2 * per_image - short_by)
+    assert got["num_batches"] == want_batches and got["num_resized"] == 0
+    cam, dst = cases.camera("OPENCV"), cases.pinhole(70, 50, 62.0, 64.0, 35.0, 24.75)
+    assert got["digests"] == [cases.digest(ref.warp(cases.make_image(cases.H, cases.W, 3, 900 + k), cam, dst)) for k in range(7)]
+
+
+def test_degenerate_undistorted_camera_is_refused_as_a_target(amc_ctx):
+    """14.2 step 5: max_image_size = 1 on 67 x 20 rounds the height to 0 samples: fy = cy = 0, which no image can be
+    warped onto."""
+    cam = cases.camera("OPENCV", height=20)
+    und = _capi.undistort_camera(cam, max_image_size=1)
+    assert (und[1], und[2]) == (1, 1) and und[3][1] == 0.0
+    img = cases.make_image(20, cases.W, 3, 950)
+    with pytest.raises(ValueError, match="target focal length is 0"):
+        pycolmap_amd.undistort_image(dict(max_image_size=1), img, pycolmap_amd.Camera("OPENCV", cases.W, 20, [float(v) for v in cam[3]]))
+    with pytest.raises(_capi.AmcError) as e:
+        amc_ctx.undistort_images([img], [cam], [und])
+    assert e.value.code == _capi.AMC_E_INVALID
+    und_ok = _capi.undistort_camera(cases.camera("OPENCV"), max_image_size=1)  # 67 x 45: 1 x 1 with fy > 0, all black
+    outs, _ = amc_ctx.undistort_images([cases.make_image(cases.H, cases.W, 3, 951)], [cases.camera("OPENCV")], [und_ok])
+    assert outs[0].shape == (1, 1, 3) and not outs[0].any()
 
 
 # ---- undistort_images end to end ---------------------------------------------------------------------------------------------
@@ -228,6 +377,47 @@ def test_copy_policy_and_image_list(workspace, tmp_path, capfd):
         assert list(cases.parse_model_bin(out / "sparse")[1]) == list(images)
         und = ref.undistort_camera(cameras[1])
         assert np.array_equal(cases.read_pnm(out / "images" / "a.ppm"), ref.warp(pixels["a.ppm"], cameras[1], und))
+
+
+def test_driver_batches_write_the_same_workspace(tmp_path, monkeypatch):
+    """undistort_images' own batch loop (BATCH_BYTES of source pixels a device call; the previous batch's files are
+    written while the next is warped): six distorted images in four device calls give the files of one call."""
+    from pycolmap_amd import _undistortion
+    cameras, images, points3D = cases.tiny_model()
+    for iid, cid, name in ((6, 1, "d.ppm"), (7, 3, "sub/e.pgm"), (8, 1, "f.ppm")):
+        images[iid] = (images[1][0], images[2][1], cid, name, [(5.0 + iid, 6.0, -1)])
+    cases.write_model_bin(tmp_path / "model", cameras, images, points3D)
+    sizes = []
+    for iid, (_, _, cid, name, _) in images.items():
+        _, w, h, _ = cameras[cid]
+        cases.write_pnm(tmp_path / "images" / name, cases.make_image(h, w, 1 if name.endswith(".pgm") else 3, 800 + iid))
+        sizes.append(w * h * 3)
+    assert len(sizes) == 6 and all(c[0] > 1 for c in cameras.values())  # six images, every one warped
+    pycolmap_amd.undistort_images(tmp_path / "one", tmp_path / "model", tmp_path / "images")
+    st = pycolmap_amd.last_run_stats()
+    assert st["warped"] == 6 and st["num_batches"] == 1
+    bound = 16000
+    calls, i = 0, 0
+    while i < len(sizes):  # the loop of 14.8, restated: greedy runs of whole images under the bound, at least one each
+        j, total = i, 0
+        while j < len(sizes) and (j == i or total + sizes[j] <= bound):
+            total += sizes[j]
+            j += 1
+        calls, i = calls + 1, j
+    assert calls == 4
+    monkeypatch.setattr(_undistortion, "BATCH_BYTES", bound)
+    pycolmap_amd.undistort_images(tmp_path / "many", tmp_path / "model", tmp_path / "images")
+    st = pycolmap_amd.last_run_stats()
+    assert st["warped"] == 6 and st["num_batches"] == calls >= 3
+    assert tree(tmp_path / "many") == tree(tmp_path / "one")
+    files = [p for p in tree(tmp_path / "one") if not p.endswith("/")]
+    assert sum(p.startswith("images/") for p in files) == 6 and "stereo/patch-match.cfg" in files and "stereo/fusion.cfg" in files
+    assert sum(p.startswith("sparse/") for p in files) == 3
+    for p in files:
+        assert (tmp_path / "many" / p).read_bytes() == (tmp_path / "one" / p).read_bytes(), p
+    und = ref.undistort_camera(cameras[1])
+    assert np.array_equal(cases.read_pnm(tmp_path / "many" / "images" / "f.ppm"),
+                          ref.warp(cases.make_image(cases.H, cases.W, 3, 808), cameras[1], und))  # the last batch's file
 
 
 # ---- errors ------------------------------------------------------------------------------------------------------------------------

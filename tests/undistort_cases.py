@@ -79,6 +79,250 @@ def warp_cases():
     return out
 
 
+# ---- the edge list: targets given directly as PINHOLE tuples --------------------------------------------
+def pinhole(width: int, height: int, fx: float, fy: float, cx: float, cy: float):
+    return (1, int(width), int(height), np.array([fx, fy, cx, cy], dtype=np.float64))
+
+
+def small_camera(model: str, width: int, height: int):
+    """A source camera of any size: focal length = the longer side, principal point a quarter pixel off the centre,
+    weak distortion (the point of these cases is the shape, not the model)."""
+    f, cx, cy = float(max(width, height)), width / 2 + 0.25, height / 2 - 0.25
+    params = {"PINHOLE": [f, f * 1.03125, cx, cy], "SIMPLE_RADIAL": [f, cx, cy, 0.03], "RADIAL": [f, cx, cy, -0.04, 0.01],
+              "OPENCV": [f, f * 1.03125, cx, cy, -0.04, 0.01, 0.0005, -0.001]}[model]
+    return camera(model, width, height, params)
+
+
+def focal_count(model: str) -> int:
+    return 1 if model in ("SIMPLE_PINHOLE", "SIMPLE_RADIAL", "RADIAL", "SIMPLE_RADIAL_FISHEYE", "RADIAL_FISHEYE") else 2
+
+
+def focal_and_principal_point(cam):
+    p, nf = cam[3], focal_count(cam[0])
+    return float(p[0]), float(p[nf - 1]), float(p[nf]), float(p[nf + 1])
+
+
+def target_into(cam, dw: int, dh: int, frac: float = 0.83):
+    """The PINHOLE dw x dh target whose pixel centres span the central `frac` of the bilinear lookup's valid range
+    (14.3: xs in [0, W - 1)) of the image the warp reads: the source, or the dw x dh resized one when the pre-pass runs
+    (14.4).  Stated for the source's pinhole part; weak distortion moves the pixels by less than the margin."""
+    sw, sh = cam[1], cam[2]
+    fx, fy, cx, cy = focal_and_principal_point(cam)
+    ew, eh = (dw, dh) if dw * dh < sw * sh else (sw, sh)
+    one_focal = focal_count(cam[0]) == 1
+    out = []
+    for e, s, d, f, c in ((ew, sw, dw, fx, cx), (eh, sh, dh, fy, cy)):
+        z = frac * (e - 1) / max(d - 1, 1)  # read pixels per target pixel
+        # Camera::Rescale: the principal point per axis, two focal lengths per axis, one by the mean of the two factors
+        fe, ce = f * ((ew / sw + eh / sh) / 2 if one_focal else e / s), c * e / s
+        out.append((fe / z if z > 0 else fe, d / 2 - (e / 2 - ce) / z if z > 0 else d / 2))
+    return pinhole(dw, dh, out[0][0], out[1][0], out[0][1], out[1][1])
+
+
+GROUP_TAILS = [(3, 3), (3, 2), (5, 2), (5, 3), (2, 2), (4, 2)]           # pixel count mod 4 = 1, 2, 2, 3, 0, 0
+NARROW = [((1, 9), (2, 4)), ((2, 9), (3, 5)), ((3, 7), (4, 5)), ((5, 5), (4, 6))]  # (target, a source with fewer pixels)
+BLACK = [(1, 1), (3, 1), (1, 3), (1, 9)]
+# (target, channels): 63 | 64 | 65 and 255 | 256 | 257 groups of four pixels, the "+1" counts with a one-pixel tail
+WARP_BOUNDARIES = [((63, 4), 1), ((11, 23), 3), ((64, 4), 1), ((65, 4), 1), ((255, 4), 1), ((256, 4), 1), ((41, 25), 3),
+                   ((257, 4), 1)]
+WARP_LINES = [(257, 1), (1021, 1)]  # prime pixel counts: one row
+# (name, source w x h, target w x h, channels): first-pass samples dw * sh and second-pass samples dw * dh on 255 | 256 | 257
+RESIZE_BOUNDARIES = [("first-255", (40, 51), (5, 7), 3), ("first-256", (30, 32), (8, 5), 1), ("first-257", (600, 1), (257, 2), 1),
+                     ("second-255", (67, 45), (51, 5), 1), ("second-256", (67, 45), (32, 8), 3), ("second-257", (20, 30), (1, 257), 1)]
+# (source w x h, target w x h, channels): the per-axis (in -> out) pairs of WINDOW_PAIRS, each on x and on y
+WINDOWS = [((1000, 3), (3, 3), 1), ((3, 1000), (3, 3), 1), ((300, 4), (7, 4), 3), ((4, 300), (4, 7), 1),
+           ((257, 3), (1, 3), 1), ((3, 257), (3, 1), 3), ((64, 3), (1, 3), 3), ((3, 64), (3, 1), 1),
+           ((64, 5), (16, 5), 1), ((5, 64), (5, 16), 3), ((64, 5), (32, 5), 3), ((5, 64), (5, 32), 1),
+           ((64, 5), (63, 5), 1), ((5, 64), (5, 63), 3), ((67, 45), (22, 15), 3), ((45, 67), (15, 22), 1),
+           ((7, 300), (100, 2), 1), ((300, 7), (2, 100), 3)]
+WINDOW_PAIRS = [(1000, 3), (300, 7), (300, 2), (257, 1), (64, 1), (64, 16), (64, 32), (64, 63), (67, 22), (45, 15), (7, 100)]
+HUGE_FOCALS = [1e-160, 1e-150]  # u = k / f: u * u overflows for the first, not for the second
+HUGE_TARGETS = [(21, 15), (70, 75)]  # with and without the pre-pass on W x H
+POLYNOMIAL = ("SIMPLE_PINHOLE", "PINHOLE", "SIMPLE_RADIAL", "RADIAL", "OPENCV", "FULL_OPENCV")
+DYADIC = ("PINHOLE", W, H, np.array([64.0, 64.0, 33.5, 22.5]))  # every coordinate of the (g) cases is exact
+# seeds by channel count of the (g) pre-pass images: the first from 7000 for which no visible sample of a clipped window
+# (weights in 28ths, rounded in FP64) is an exact tie, so that integer arithmetic pins every byte (int_resize)
+PREPASS_SEEDS = {1: 7000, 3: 8197}
+
+
+def edge_cases():
+    """[(name, image, source camera, target camera)]: DESIGN.md 14.6's edge list.  The name's first field is the class
+    (a .. k of the list there); "black" in a name says that no target pixel can be inside."""
+    out = []
+    seed = iter(range(1000, 2000))
+
+    def add(name, img, cam, dst):
+        out.append((name, img, cam, dst))
+
+    def img_for(cam, ch):
+        return make_image(cam[2], cam[1], ch, next(seed))
+
+    # a. group tails: with a 2 x 3 source (no pre-pass; 2 x 2 for the 2 x 2 target) and through the pre-pass
+    for (dw, dh) in GROUP_TAILS:
+        for ch in (1, 3):
+            sw, sh = (2, 2) if dw * dh < 6 else (2, 3)
+            cam = small_camera("PINHOLE" if ch == 1 else "SIMPLE_RADIAL", sw, sh)
+            add(f"a-tail-{dw}x{dh}-{ch}ch", img_for(cam, ch), cam, target_into(cam, dw, dh))
+            cam = camera("RADIAL" if ch == 1 else "OPENCV")
+            add(f"a-tail-{dw}x{dh}-{ch}ch-prepass", img_for(cam, ch), cam, target_into(cam, dw, dh))
+    # b. narrow targets: a group spans 4, 2, 2 and 1 to 2 rows; the all-black ones
+    for (dw, dh), (sw, sh) in NARROW:
+        for ch in (1, 3):
+            cam = small_camera("SIMPLE_RADIAL" if ch == 1 else "PINHOLE", sw, sh)
+            add(f"b-narrow-{dw}x{dh}-{ch}ch", img_for(cam, ch), cam, target_into(cam, dw, dh))
+    for i, (dw, dh) in enumerate(BLACK):
+        ch = 3 if i % 2 else 1
+        cam = camera("OPENCV")
+        add(f"b-black-{dw}x{dh}-{ch}ch", img_for(cam, ch), cam, target_into(cam, dw, dh))
+    # c. wave and block boundaries of the warp (no pre-pass: a 12 x 9 source), and the two prime counts as one row:
+    # black through the pre-pass of W x H (the resized source is one row), with pixels from a 16 x 9 source
+    for (dw, dh), ch in WARP_BOUNDARIES:
+        cam = small_camera("RADIAL", 12, 9)
+        add(f"c-warp-{dw * dh}-{dw}x{dh}-{ch}ch", img_for(cam, ch), cam, target_into(cam, dw, dh))
+    for (dw, dh) in WARP_LINES:
+        cam = camera("RADIAL")
+        add(f"c-warp-{dw * dh}-{dw}x{dh}-3ch-black", img_for(cam, 3), cam, target_into(cam, dw, dh))
+        cam = small_camera("OPENCV", 16, 9)
+        add(f"c-warp-{dw * dh}-{dw}x{dh}-3ch-line", img_for(cam, 3), cam, target_into(cam, dw, dh))
+    # d. block boundaries of the two resize kernels
+    for name, (sw, sh), (dw, dh), ch in RESIZE_BOUNDARIES:
+        cam = camera("OPENCV") if (sw, sh) == (W, H) else small_camera("SIMPLE_RADIAL", sw, sh)
+        add(f"d-{name}-{sw}x{sh}-to-{dw}x{dh}-{ch}ch" + ("-black" if min(dw, dh) == 1 else ""), img_for(cam, ch), cam,
+            target_into(cam, dw, dh))
+    # e. windows
+    for (sw, sh), (dw, dh), ch in WINDOWS:
+        cam = camera("RADIAL") if (sw, sh) == (W, H) else small_camera("PINHOLE" if ch == 1 else "SIMPLE_RADIAL", sw, sh)
+        add(f"e-window-{sw}x{sh}-to-{dw}x{dh}-{ch}ch" + ("-black" if min(dw, dh) == 1 else ""), img_for(cam, ch), cam,
+            target_into(cam, dw, dh))
+    # f. every model through a pre-pass that enlarges x and reduces y
+    for i, model in enumerate(CAMERAS):
+        cam = camera(model)
+        fx, fy, cx, cy = focal_and_principal_point(cam)
+        add(f"f-mixed-{model}-{1 + 2 * (i % 2)}ch", img_for(cam, 1 + 2 * (i % 2)), cam,
+            pinhole(100, 9, fx * 100 / W, fy * 9 / H, cx * 100 / W, cy * 9 / H))
+    # g. dyadic known answers (known_answers() states them in integer arithmetic)
+    for ch in (1, 3):
+        add(f"g-identity-{ch}ch", img_for(DYADIC, ch), DYADIC, pinhole(W, H, 64.0, 64.0, 33.5, 22.5))
+    add("g-halfx-1ch", img_for(DYADIC, 1), DYADIC, pinhole(W, H, 64.0, 64.0, 33.0, 22.5))
+    add("g-halfy-3ch", img_for(DYADIC, 3), DYADIC, pinhole(W, H, 64.0, 64.0, 33.5, 22.0))
+    add("g-halfxy-1ch", img_for(DYADIC, 1), DYADIC, pinhole(W, H, 64.0, 64.0, 33.0, 22.0))
+    add("g-mirror-3ch", img_for(DYADIC, 3), DYADIC, pinhole(W, H, -64.0, 64.0, 32.5, 22.5))
+    for ch in (1, 3):
+        cam = ("PINHOLE", 64, 48, np.array([64.0, 64.0, 32.5, 24.5]))
+        add(f"g-prepass-{ch}ch", make_image(48, 64, ch, PREPASS_SEEDS[ch]), cam, pinhole(16, 12, 16.0, 16.0, 8.125, 6.125))
+    # h. coordinates that are not finite, or huge; the principal point on the centre of pixel (10, 7)
+    for i, model in enumerate(CAMERAS):
+        for f in HUGE_FOCALS:
+            for (dw, dh) in HUGE_TARGETS:
+                ch = 1 + 2 * ((i + (dw > 21)) % 2)
+                cam = camera(model)
+                add(f"h-huge-{model}-{f:g}-{dw}x{dh}-{ch}ch", img_for(cam, ch), cam, pinhole(dw, dh, f, f, 10.5, 7.5))
+    # i. camera branches: r = 0 of the fisheye family on a pixel centre, FOV's small-omega and small-radius branches
+    for i, model in enumerate(("OPENCV_FISHEYE", "SIMPLE_RADIAL_FISHEYE", "RADIAL_FISHEYE", "THIN_PRISM_FISHEYE")):
+        cam = camera(model)
+        add(f"i-centre-{model}-{1 + 2 * (i % 2)}ch", img_for(cam, 1 + 2 * (i % 2)), cam, pinhole(21, 15, 8.0, 8.0, 10.5, 7.5))
+    for omega in (1e-3, 0.0):
+        cam = camera("FOV", params=[60.0, 59.0, 33.0, 22.5, omega])
+        add(f"i-fov-omega-{omega:g}-3ch", img_for(cam, 3), cam, pinhole(70, 50, 62.0, 61.0, 35.5, 25.5))
+    cam = camera("FOV")
+    add("i-fov-small-radius-1ch", img_for(cam, 1), cam, pinhole(70, 50, 500.0, 500.0, 35.5, 25.5))
+    # j. saturation
+    for value in (255, 0):
+        cam = camera("RADIAL")
+        for (dw, dh) in ((130, 90), (30, 20)):
+            add(f"j-all-{value}-{dw}x{dh}-3ch", np.full((H, W, 3), value, np.uint8), cam,
+                pinhole(dw, dh, 58.0 * dw / W, 58.0 * dh / H, 33.25 * dw / W, 22.5 * dh / H))
+    yy, xx = np.mgrid[0:64, 0:64]
+    cam = small_camera("PINHOLE", 64, 64)
+    add("j-checkerboard-64-to-63-1ch", (((xx + yy) % 2) * 255).astype(np.uint8), cam, target_into(cam, 63, 63))
+    # k. input layouts
+    cam = camera("OPENCV", W, 23, [60.0, 62.0, 33.0, 11.25, -0.2, 0.05, 0.001, -0.002])
+    add("k-rows-subsampled-3ch", make_image(46, W, 3, next(seed))[::2], cam, target_into(cam, 70, 24))
+    cam = camera("RADIAL")
+    add("k-trailing-1-axis", make_image(H, W, 1, next(seed))[..., None], cam, target_into(cam, 40, 30))
+    add("k-fortran-order-3ch", np.asfortranarray(make_image(H, W, 3, next(seed))), cam, target_into(cam, 75, 50))
+    add("k-negative-row-stride-1ch", make_image(H, W, 1, next(seed))[::-1], cam, target_into(cam, 75, 50))
+    return out
+
+
+def round_half_up_div(n, d):
+    """floor(n / d + 1 / 2) of non-negative integers."""
+    return (2 * n + d) // (2 * d)
+
+
+def int_axis_weights(n_in, n_out):
+    """14.4 for a reduction by an even integer factor r = n_in / n_out, in integers: [(left, integer weights, their
+    sum)] per output sample.  Centre r u + r / 2, window r u - r / 2 .. r u + r + r / 2 - 1 clipped to the image; the
+    tent's weights at these half-integer offsets are the odd numbers 1 .. 2 r - 1 over 2 r^2.  An interior window sums
+    to 2 r^2 (a power of two for r = 4: every product and sum is then exact in FP64); the clipped windows at the two
+    ends sum to less."""
+    r = n_in // n_out
+    assert r * n_out == n_in and r >= 2 and r % 2 == 0
+    out = []
+    for u in range(n_out):
+        left, right = max(0, r * u - r // 2), min(r * u + r + r // 2, n_in)
+        w = [2 * r - abs(2 * i + 1 - (2 * u + 1) * r) for i in range(left, right)]
+        assert all(k > 0 for k in w)
+        out.append((left, w, sum(w)))
+    return out
+
+
+def int_resize(img, dw, dh):
+    """14.4 in integer arithmetic for integer reduction factors: (the resized image, mask of the samples whose value
+    depends on an exact tie of a window whose weight sum is no power of two; there the floating-point sum of the
+    rounded weights may fall on either side)."""
+    a = img.reshape(img.shape[0], img.shape[1], -1).astype(np.int64)
+    doubt = np.zeros(a.shape, bool)
+    for axis, n_out in ((1, dw), (0, dh)):
+        a, doubt = np.moveaxis(a, axis, 0), np.moveaxis(doubt, axis, 0)
+        res, dres = [], []
+        for left, w, d in int_axis_weights(a.shape[0], n_out):
+            n = sum(k * a[left + j] for j, k in enumerate(w))
+            tie = (2 * (n % d) == d) & (d & (d - 1) != 0)
+            res.append(round_half_up_div(n, d))
+            dres.append(tie | doubt[left:left + len(w)].any(axis=0))
+        a, doubt = np.moveaxis(np.stack(res), 0, axis), np.moveaxis(np.stack(dres), 0, axis)
+    shape = (dh, dw) + img.shape[2:]
+    return a.astype(np.uint8).reshape(shape), doubt.reshape(shape)
+
+
+def known_answers():
+    """{name: (expected image, mask of the pixels it pins)} of the (g) cases, in integer arithmetic from 14.3 and 14.4
+    alone.  PINHOLE source fx = fy = 64, principal point on half-integers: s = (x + 0.5 + shift_x, y + 0.5 + shift_y)
+    exactly, so x0 = x (+ dx = 1/2 when the target's cx is lower by 1/2) and, bottom-up, y0 = H - 1 - y (or H - 2 - y
+    with dy = 1/2: the rows y and y + 1).  A two-pixel mean is n / 2, a four-pixel mean n / 4, rounded half up."""
+    by = {c[0]: c for c in edge_cases()}
+    out = {}
+
+    def blank(shape):
+        return np.zeros(shape, np.int64), np.ones(shape[:2], bool)
+
+    for name, (_, img, _, _) in by.items():
+        if not name.startswith("g-"):
+            continue
+        a = img.astype(np.int64)
+        want, pinned = blank(a.shape)
+        kind = name.split("-")[1]
+        if kind == "identity":    # the input; the top row (y0 + 1 = H) and the last column (x0 + 1 = W) are outside
+            want[1:, :-1] = a[1:, :-1]
+        elif kind == "halfx":
+            want[1:, :-1] = round_half_up_div(a[1:, :-1] + a[1:, 1:], 2)
+        elif kind == "halfy":     # rows y and y + 1; the last row has y0 = -1, the top row is inside (y0 + 1 = H - 1)
+            want[:-1, :-1] = round_half_up_div(a[:-1, :-1] + a[1:, :-1], 2)
+        elif kind == "halfxy":
+            want[:-1, :-1] = round_half_up_div(a[:-1, :-1] + a[:-1, 1:] + a[1:, :-1] + a[1:, 1:], 4)
+        elif kind == "mirror":    # s.x = 65.5 - x: x0 = 65 - x = W - 2 - x with dx = 0; x = W - 1 has x0 = -1
+            want[1:, :-1] = a[1:, -2::-1]
+        elif kind == "prepass":   # the identity on the 16 x 12 resized image
+            small, doubt = int_resize(img, 16, 12)
+            want, pinned = blank(small.shape)
+            want[1:, :-1] = small.astype(np.int64)[1:, :-1]
+            pinned = ~doubt.reshape(12, 16, -1).any(axis=2)
+            pinned[0], pinned[:, -1] = True, True
+        out[name] = (want.astype(np.uint8), pinned)
+    return out
+
+
 def digest(a: np.ndarray) -> str:
     return hashlib.sha256(str(a.shape).encode() + np.ascontiguousarray(a).tobytes()).hexdigest()
 

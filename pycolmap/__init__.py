@@ -15,7 +15,9 @@ anything else raises AttributeError naming this package, so that a script reachi
 fails at the attribute, not later.  Track completion and merging (`complete_tracks`,
 `complete_all_tracks`, `merge_tracks`, `merge_all_tracks`: module-level functions that take the `IncrementalTriangulator`
 first) resolve too, and so does `retriangulate(triangulator, options)` for under-reconstructed image
-pairs."""
+pairs.  The three steps of the mapper in front of them resolve as well: `IncrementalMapper(triangulator)`
+with `find_next_images`, `register_next_image` and `find_local_bundle`, `IncrementalMapperOptions` and
+`ImageSelectionMethod`; the initial pair, `adjust_*` and the drivers stay undefined."""
 import pycolmap_amd as _impl
 from pycolmap_amd import *  # noqa: F401,F403
 from pycolmap_amd import __version__  # noqa: F401
@@ -26,4 +28,4 @@ globals().update({n: getattr(_impl, n) for n in _PUBLIC})
 
 def __getattr__(name):
     raise AttributeError(f"pycolmap.{name} is outside pycolmap_amd's scope (SIFT feature extraction, exhaustive / sequential "
-                         f"matching + two-view verification, known-pose triangulation, absolute pose, image undistortion, bundle adjustment of a minimal Reconstruction behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}; also in scope: point filtering, and incremental triangulation of an image (CorrespondenceGraph, IncrementalTriangulator.triangulate_image), and the adjustment of a part of the model (BundleAdjustmentConfig, BundleAdjuster.solve), and track completion and merging (complete_tracks, complete_all_tracks, merge_tracks, merge_all_tracks with the triangulator as first argument), and retriangulation of under-reconstructed image pairs (retriangulate with the triangulator as first argument)")
+                         f"matching + two-view verification, known-pose triangulation, absolute pose, image undistortion, bundle adjustment of a minimal Reconstruction behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}; also in scope: point filtering, and incremental triangulation of an image (CorrespondenceGraph, IncrementalTriangulator.triangulate_image), and the adjustment of a part of the model (BundleAdjustmentConfig, BundleAdjuster.solve), and track completion and merging (complete_tracks, complete_all_tracks, merge_tracks, merge_all_tracks with the triangulator as first argument), and retriangulation of under-reconstructed image pairs (retriangulate with the triangulator as first argument), and the mapper's image ranking, registration and local bundle (IncrementalMapper.find_next_images, register_next_image, find_local_bundle with IncrementalMapperOptions and ImageSelectionMethod)")

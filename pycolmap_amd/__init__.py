@@ -15,7 +15,7 @@ __version__ = "0.1.0"
 
 try:  # the compiled host layer; absent only before `python -m pycolmap_amd.build`
     from ._pycolmap import (  # noqa: F401
-        AbsolutePoseEstimationOptions, AbsolutePoseRefinementOptions, BundleAdjuster, BundleAdjustmentConfig, BundleAdjustmentOptions, Correspondence, CorrespondenceGraph, IncrementalTriangulator, IncrementalTriangulatorOptions, CeresSolverOptions, LossFunctionType, Point2D, Point3D, Reconstruction, Track, TrackElement, bundle_adjustment, complete_all_tracks, complete_tracks, COLMAP_build, COLMAP_version, Camera, CopyType, UndistortCameraOptions, undistort_camera, undistort_image, CameraMode, CameraModelId, Database, DatabaseTransaction, Device, EstimateTriangulationOptions, ExhaustiveMatchingOptions, Image, ImageReaderOptions, Normalization, PointData, RANSACOptions, Rigid3d,
+        AbsolutePoseEstimationOptions, AbsolutePoseRefinementOptions, BundleAdjuster, BundleAdjustmentConfig, BundleAdjustmentOptions, Correspondence, CorrespondenceGraph, ImageSelectionMethod, IncrementalMapper, IncrementalMapperOptions, IncrementalTriangulator, IncrementalTriangulatorOptions, CeresSolverOptions, LossFunctionType, Point2D, Point3D, Reconstruction, Track, TrackElement, bundle_adjustment, complete_all_tracks, complete_tracks, COLMAP_build, COLMAP_version, Camera, CopyType, UndistortCameraOptions, undistort_camera, undistort_image, CameraMode, CameraModelId, Database, DatabaseTransaction, Device, EstimateTriangulationOptions, ExhaustiveMatchingOptions, Image, ImageReaderOptions, Normalization, PointData, RANSACOptions, Rigid3d,
         Rotation3d, Sift, SiftExtractionOptions,
         SequentialMatchingOptions, SiftMatchingOptions, SpatialMatchingOptions, TwoViewGeometry, TwoViewGeometryConfiguration,
         VocabTreeMatchingOptions,

@@ -41,6 +41,8 @@ EXPORTED_SYMBOLS = [
     "amc_complete_opts_default", "amc_complete_tracks", "amc_complete_result_free",
     "amc_merge_opts_default", "amc_merge_tracks", "amc_merge_result_free",
     "amc_retri_opts_default", "amc_retriangulate_pairs", "amc_retri_result_free",
+    "amc_image_visibility", "amc_visibility_result_free",
+    "amc_pair_angle_opts_default", "amc_shared_point_angles", "amc_pair_angle_result_free",
 ]
 COMM_ID_BYTES = 128
 RANSAC_F, RANSAC_H, RANSAC_E = 0, 1, 2
@@ -441,6 +443,98 @@ class RetriResult(C.Structure):  # amc_retri_result
                 ("num_launches", C.c_uint32), ("reserved", C.c_uint32),
                 ("host_ms", C.c_double), ("device_ms", C.c_double), ("kernel_ms", C.c_double), ("copy_ms", C.c_double),
                 ("alloc_ms", C.c_double)]
+
+
+class VisibilityProblem(C.Structure):  # amc_visibility_problem (include/amc_mapper.h)
+    _fields_ = [("num_graph_images", C.c_size_t), ("image_point_offsets", C.c_void_p), ("point2D_point3D", C.c_void_p),
+                ("num_candidates", C.c_size_t), ("cand_width", C.c_void_p), ("cand_height", C.c_void_p),
+                ("cand_point_offsets", C.c_void_p), ("cand_xy", C.c_void_p), ("corr_offsets", C.c_void_p),
+                ("corr_image", C.c_void_p), ("corr_point2D", C.c_void_p)]
+
+
+class VisibilityResult(C.Structure):  # amc_visibility_result
+    _fields_ = [("num_candidates", C.c_uint64), ("num_observations", C.POINTER(C.c_uint32)),
+                ("num_visible_points3D", C.POINTER(C.c_uint32)), ("score", C.POINTER(C.c_uint64)),
+                ("max_score", C.c_uint64), ("num_batches", C.c_uint32), ("reserved", C.c_uint32),
+                ("host_ms", C.c_double), ("device_ms", C.c_double), ("kernel_ms", C.c_double), ("copy_ms", C.c_double),
+                ("alloc_ms", C.c_double)]
+
+
+class PairAngleOpts(C.Structure):  # amc_pair_angle_opts
+    _fields_ = [("percentile", C.c_double)]
+
+
+class PairAngleProblem(C.Structure):  # amc_pair_angle_problem
+    _fields_ = [("num_images", C.c_size_t), ("qvec", C.c_void_p), ("tvec", C.c_void_p),
+                ("num_points", C.c_size_t), ("point_xyz", C.c_void_p),
+                ("num_pairs", C.c_size_t), ("pair_images", C.c_void_p), ("pair_offsets", C.c_void_p),
+                ("shared_points", C.c_void_p)]
+
+
+class PairAngleResult(C.Structure):  # amc_pair_angle_result
+    _fields_ = [("num_pairs", C.c_uint64), ("angle", C.POINTER(C.c_double)), ("num_batches", C.c_uint32),
+                ("reserved", C.c_uint32), ("host_ms", C.c_double), ("device_ms", C.c_double), ("kernel_ms", C.c_double),
+                ("copy_ms", C.c_double), ("alloc_ms", C.c_double)]
+
+
+MAPPER_NO_POINT3D = (1 << 64) - 1
+MAPPER_MAX_SCORE = 17895696
+MAPPER_MAX_PAIR_POINTS = 1 << 20
+
+
+def _u32_index(who, name, a):
+    a = np.array(a, dtype=np.int64).reshape(-1)
+    if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+        raise ValueError(f"{who}: {name} has a value outside 0 .. 2^32 - 1")
+    return a.astype(np.uint32)
+
+
+def _offsets(who, name, a):
+    a = np.array(a, dtype=np.int64).reshape(-1)
+    if a.size < 1 or a.min() < 0:
+        raise ValueError(f"{who}: {name} needs at least one entry, none negative")
+    return a.astype(np.uint64)
+
+
+def visibility_inputs(image_point_offsets, point2D_point3D, cand_width, cand_height, cand_point_offsets, cand_xy,
+                      corr_offsets, corr_image, corr_point2D):
+    """The flat problem of amc_image_visibility as contiguous arrays (copies): image_point_offsets (G + 1,) uint64,
+    point2D_point3D (T,) uint64 (MAPPER_NO_POINT3D = none), cand_width / cand_height (K,) uint32, cand_point_offsets
+    (K + 1,) uint64, cand_xy (N, 2), corr_offsets (N + 1,) uint64, corr_image / corr_point2D (M,) uint32."""
+    who = "image_visibility"
+    ipoff = _offsets(who, "image_point_offsets", image_point_offsets)
+    table = np.array(point2D_point3D, dtype=np.uint64).reshape(-1)
+    cw, ch = _u32_index(who, "cand_width", cand_width), _u32_index(who, "cand_height", cand_height)
+    cpoff = _offsets(who, "cand_point_offsets", cand_point_offsets)
+    xy = np.array(cand_xy, dtype=np.float64).reshape(-1, 2)
+    coff = _offsets(who, "corr_offsets", corr_offsets)
+    ci, cp = _u32_index(who, "corr_image", corr_image), _u32_index(who, "corr_point2D", corr_point2D)
+    if int(ipoff[-1]) != table.size:
+        raise ValueError(f"{who}: image_point_offsets ends at {int(ipoff[-1])}, {table.size} table rows")
+    if not (cw.size == ch.size == cpoff.size - 1):
+        raise ValueError(f"{who}: {cw.size} widths, {ch.size} heights, {cpoff.size} candidate offsets")
+    if int(cpoff[-1]) != xy.shape[0] or coff.size != xy.shape[0] + 1:
+        raise ValueError(f"{who}: cand_point_offsets ends at {int(cpoff[-1])}, {xy.shape[0]} pixels, {coff.size} correspondence offsets")
+    if int(coff[-1]) != ci.size or ci.size != cp.size:
+        raise ValueError(f"{who}: corr_offsets ends at {int(coff[-1])}, {ci.size} images, {cp.size} point2D indices")
+    return ipoff, table, cw, ch, cpoff, xy, coff, ci, cp
+
+
+def pair_angle_inputs(qvec, tvec, point_xyz, pair_images, pair_offsets, shared_points):
+    """The flat problem of amc_shared_point_angles as contiguous arrays (copies): qvec (I, 4) x y z w, tvec (I, 3),
+    point_xyz (P, 3), pair_images (K, 2) uint32, pair_offsets (K + 1,) uint64, shared_points (S,) uint32."""
+    who = "shared_point_angles"
+    q = np.array(qvec, dtype=np.float64).reshape(-1, 4)
+    t = np.array(tvec, dtype=np.float64).reshape(-1, 3)
+    X = np.array(point_xyz, dtype=np.float64).reshape(-1, 3)
+    pi = np.ascontiguousarray(_u32_index(who, "pair_images", pair_images).reshape(-1, 2))
+    poff = _offsets(who, "pair_offsets", pair_offsets)
+    sp = _u32_index(who, "shared_points", shared_points)
+    if q.shape[0] != t.shape[0]:
+        raise ValueError(f"{who}: {q.shape[0]} rotations, {t.shape[0]} translations")
+    if poff.size != pi.shape[0] + 1 or int(poff[-1]) != sp.size:
+        raise ValueError(f"{who}: {pi.shape[0]} pairs, {poff.size} offsets ending at {int(poff[-1])}, {sp.size} shared points")
+    return q, t, X, pi, poff, sp
 
 
 RETRI_NONE, RETRI_CONTINUE_1TO2, RETRI_CONTINUE_2TO1, RETRI_CREATED = 0, 1, 2, 3
@@ -931,6 +1025,18 @@ def load() -> C.CDLL:
         lib.amc_retriangulate_pairs.restype = C.c_int
         lib.amc_retri_result_free.argtypes = [C.POINTER(RetriResult)]
         lib.amc_retri_result_free.restype = None
+    if hasattr(lib, "amc_image_visibility"):  # (absent from a library built from an older revision)
+        lib.amc_image_visibility.argtypes = [C.c_void_p, C.POINTER(VisibilityProblem), C.POINTER(VisibilityResult)]
+        lib.amc_image_visibility.restype = C.c_int
+        lib.amc_visibility_result_free.argtypes = [C.POINTER(VisibilityResult)]
+        lib.amc_visibility_result_free.restype = None
+        lib.amc_pair_angle_opts_default.argtypes = [C.POINTER(PairAngleOpts)]
+        lib.amc_pair_angle_opts_default.restype = None
+        lib.amc_shared_point_angles.argtypes = [C.c_void_p, C.POINTER(PairAngleProblem), C.POINTER(PairAngleOpts),
+                                                C.POINTER(PairAngleResult)]
+        lib.amc_shared_point_angles.restype = C.c_int
+        lib.amc_pair_angle_result_free.argtypes = [C.POINTER(PairAngleResult)]
+        lib.amc_pair_angle_result_free.restype = None
     if hasattr(lib, "amc_triangulate_tracks"):  # (absent from a library built from an older revision)
         lib.amc_tri_opts_default.argtypes = [C.POINTER(TriOpts)]
         lib.amc_tri_opts_default.restype = None
@@ -1529,6 +1635,54 @@ class Context:
                    "copy_ms": res.copy_ms, "alloc_ms": res.alloc_ms}
         finally:
             self._lib.amc_retri_result_free(C.byref(res))
+        return out
+
+    def image_visibility(self, image_point_offsets, point2D_point3D, cand_width, cand_height, cand_point_offsets, cand_xy,
+                         corr_offsets, corr_image, corr_point2D):
+        """amc_image_visibility: for a batch of candidate images, what COLMAP's Image keeps incrementally (DESIGN.md
+        section 20).  image_point_offsets (G + 1,) CSR over point2D_point3D (T,), the point3D id of every point2D of
+        every graph image or MAPPER_NO_POINT3D; cand_width / cand_height (K,); cand_point_offsets (K + 1,) CSR over
+        cand_xy (N, 2) pixels; corr_offsets (N + 1,) CSR over corr_image / corr_point2D (M,), graph image index and
+        point2D index.  The inputs are not modified.  Returns a dict: num_observations, num_visible_points3D (K,)
+        uint32, score (K,) uint64, max_score, num_batches, host_ms, device_ms, kernel_ms, copy_ms, alloc_ms."""
+        ipoff, table, cw, ch, cpoff, xy, coff, ci, cp = visibility_inputs(
+            image_point_offsets, point2D_point3D, cand_width, cand_height, cand_point_offsets, cand_xy, corr_offsets,
+            corr_image, corr_point2D)
+        ptr = lambda v: v.ctypes.data_as(C.c_void_p)  # noqa: E731
+        pb = VisibilityProblem(ipoff.size - 1, ptr(ipoff), ptr(table), cw.size, ptr(cw), ptr(ch), ptr(cpoff), ptr(xy),
+                               ptr(coff), ptr(ci), ptr(cp))
+        res = VisibilityResult()
+        _check(self._lib.amc_image_visibility(self._h, C.byref(pb), C.byref(res)))
+        try:
+            k = cw.size
+            arr = lambda p, n: np.ctypeslib.as_array(p, (max(n, 1),))[:n].copy()  # noqa: E731
+            out = {"num_observations": arr(res.num_observations, k), "num_visible_points3D": arr(res.num_visible_points3D, k),
+                   "score": arr(res.score, k), "max_score": int(res.max_score), "num_batches": int(res.num_batches),
+                   "host_ms": res.host_ms, "device_ms": res.device_ms, "kernel_ms": res.kernel_ms,
+                   "copy_ms": res.copy_ms, "alloc_ms": res.alloc_ms}
+        finally:
+            self._lib.amc_visibility_result_free(C.byref(res))
+        return out
+
+    def shared_point_angles(self, qvec, tvec, point_xyz, pair_images, pair_offsets, shared_points, percentile=75.0):
+        """amc_shared_point_angles: per image pair the percentile of the triangulation angles at the points the two
+        images share (DESIGN.md section 20).  qvec (I, 4) x y z w, tvec (I, 3); point_xyz (P, 3); pair_images (K, 2);
+        pair_offsets (K + 1,) CSR over shared_points (S,), point indices, every pair holding 1 .. MAPPER_MAX_PAIR_POINTS.
+        The inputs are not modified.  Returns a dict: angle (K,) radians, num_batches, host_ms, device_ms, kernel_ms,
+        copy_ms, alloc_ms."""
+        q, t, X, pi, poff, sp = pair_angle_inputs(qvec, tvec, point_xyz, pair_images, pair_offsets, shared_points)
+        ptr = lambda v: v.ctypes.data_as(C.c_void_p)  # noqa: E731
+        o = PairAngleOpts(float(percentile))
+        pb = PairAngleProblem(q.shape[0], ptr(q), ptr(t), X.shape[0], ptr(X), pi.shape[0], ptr(pi), ptr(poff), ptr(sp))
+        res = PairAngleResult()
+        _check(self._lib.amc_shared_point_angles(self._h, C.byref(pb), C.byref(o), C.byref(res)))
+        try:
+            k = pi.shape[0]
+            out = {"angle": np.ctypeslib.as_array(res.angle, (max(k, 1),))[:k].copy(), "num_batches": int(res.num_batches),
+                   "host_ms": res.host_ms, "device_ms": res.device_ms, "kernel_ms": res.kernel_ms,
+                   "copy_ms": res.copy_ms, "alloc_ms": res.alloc_ms}
+        finally:
+            self._lib.amc_pair_angle_result_free(C.byref(res))
         return out
 
     def estimate_rig_absolute_poses(self, offsets, camera_offsets, camera_models, camera_params, cams_from_rig,

@@ -28,6 +28,7 @@
 #include <condition_variable>
 #include <exception>
 #include <fstream>
+#include <functional>
 #include <sstream>
 #include <thread>
 #include <unordered_set>
@@ -42,6 +43,7 @@
 #include "undistort_host.h"
 #include "ba_config_host.h"
 #include "ba_host.h"
+#include "mapper_host.h"
 #include "reconstruction.h"
 #include "retriangulate_host.h"
 #include "track_ops_host.h"
@@ -2353,6 +2355,433 @@ PYBIND11_MODULE(_pycolmap, m) {
           }, "triangulator"_a, "The trial counters of retriangulate, {(image_id1, image_id2): trials} (test hook, a copy).");
     m.def("_retriangulate_rounds", [](const std::vector<std::pair<uint32_t, uint32_t>>& pairs) { return ColourRetriRounds(pairs); },
           "pairs"_a, "The round of every image pair under retriangulate's greedy colouring, pairs in the given order (test hook).");
+
+    // ---- IncrementalMapper (mapper_host.h) ----
+    // The three steps in front of triangulate_image: which candidate to register next, the registration itself and the
+    // images of the local adjustment after it.  The graph and the reconstruction are the triangulator's.  An image that
+    // is not registered is not in the reconstruction (R1), so the mapper keeps its candidates itself.  Every method
+    // takes a device first: without one it raises pycolmap_amd._capi.AmcError and changes nothing.  The `_with`
+    // variants put a callable in the library's place (test hooks: the CPU tests pass the references).
+    py::enum_<ImageSelectionMethod> PySelection(m, "ImageSelectionMethod");
+    PySelection.value("MAX_VISIBLE_POINTS_NUM", ImageSelectionMethod::MAX_VISIBLE_POINTS_NUM)
+        .value("MAX_VISIBLE_POINTS_RATIO", ImageSelectionMethod::MAX_VISIBLE_POINTS_RATIO)
+        .value("MIN_UNCERTAINTY", ImageSelectionMethod::MIN_UNCERTAINTY);
+    PySelection.def(py::init([](const std::string& s) {
+        if (s == "MAX_VISIBLE_POINTS_NUM") return ImageSelectionMethod::MAX_VISIBLE_POINTS_NUM;
+        if (s == "MAX_VISIBLE_POINTS_RATIO") return ImageSelectionMethod::MAX_VISIBLE_POINTS_RATIO;
+        if (s == "MIN_UNCERTAINTY") return ImageSelectionMethod::MIN_UNCERTAINTY;
+        throw py::value_error("Invalid string value " + s + " for enum ImageSelectionMethod");
+    }));
+    py::implicitly_convertible<std::string, ImageSelectionMethod>();
+    py::class_<MapperOptions> PyMapOpts(m, "IncrementalMapperOptions");
+    PyMapOpts.def(py::init<>())
+        .def_readwrite("init_min_num_inliers", &MapperOptions::init_min_num_inliers, "Minimum number of inliers for initial image pair.")
+        .def_readwrite("init_max_error", &MapperOptions::init_max_error, "Maximum error in pixels for two-view geometry estimation for initial image pair.")
+        .def_readwrite("init_max_forward_motion", &MapperOptions::init_max_forward_motion, "Maximum forward motion for initial image pair.")
+        .def_readwrite("init_min_tri_angle", &MapperOptions::init_min_tri_angle, "Minimum triangulation angle for initial image pair.")
+        .def_readwrite("init_max_reg_trials", &MapperOptions::init_max_reg_trials, "Maximum number of trials to use an image for initialization.")
+        .def_readwrite("abs_pose_max_error", &MapperOptions::abs_pose_max_error, "Maximum reprojection error in absolute pose estimation.")
+        .def_readwrite("abs_pose_min_num_inliers", &MapperOptions::abs_pose_min_num_inliers, "Minimum number of inliers in absolute pose estimation.")
+        .def_readwrite("abs_pose_min_inlier_ratio", &MapperOptions::abs_pose_min_inlier_ratio, "Minimum inlier ratio in absolute pose estimation.")
+        .def_readwrite("abs_pose_refine_focal_length", &MapperOptions::abs_pose_refine_focal_length, "Whether to estimate the focal length in absolute pose estimation.")
+        .def_readwrite("abs_pose_refine_extra_params", &MapperOptions::abs_pose_refine_extra_params, "Whether to estimate the extra parameters in absolute pose estimation.")
+        .def_readwrite("local_ba_num_images", &MapperOptions::local_ba_num_images, "Number of images to optimize in local bundle adjustment.")
+        .def_readwrite("local_ba_min_tri_angle", &MapperOptions::local_ba_min_tri_angle, "Minimum triangulation for images to be chosen in local bundle adjustment.")
+        .def_readwrite("min_focal_length_ratio", &MapperOptions::min_focal_length_ratio, "The threshold used to filter and ignore images with degenerate intrinsics.")
+        .def_readwrite("max_focal_length_ratio", &MapperOptions::max_focal_length_ratio, "The threshold used to filter and ignore images with degenerate intrinsics.")
+        .def_readwrite("max_extra_param", &MapperOptions::max_extra_param, "The threshold used to filter and ignore images with degenerate intrinsics.")
+        .def_readwrite("filter_max_reproj_error", &MapperOptions::filter_max_reproj_error, "Maximum reprojection error in pixels for observations.")
+        .def_readwrite("filter_min_tri_angle", &MapperOptions::filter_min_tri_angle, "Minimum triangulation angle in degrees for stable 3D points.")
+        .def_readwrite("max_reg_trials", &MapperOptions::max_reg_trials, "Maximum number of trials to register an image.")
+        .def_readwrite("fix_existing_images", &MapperOptions::fix_existing_images, "If reconstruction is provided as input, fix the existing image poses.")
+        .def_readwrite("num_threads", &MapperOptions::num_threads, "Number of threads.")
+        .def_readwrite("image_selection_method", &MapperOptions::image_selection_method, "Method to find and select next best image to register.");
+    MakeDataclass(PyMapOpts, {"init_min_num_inliers", "init_max_error", "init_max_forward_motion", "init_min_tri_angle", "init_max_reg_trials",
+                              "abs_pose_max_error", "abs_pose_min_num_inliers", "abs_pose_min_inlier_ratio", "abs_pose_refine_focal_length",
+                              "abs_pose_refine_extra_params", "local_ba_num_images", "local_ba_min_tri_angle", "min_focal_length_ratio",
+                              "max_focal_length_ratio", "max_extra_param", "filter_max_reproj_error", "filter_min_tri_angle", "max_reg_trials",
+                              "fix_existing_images", "num_threads", "image_selection_method"});
+
+    struct PyMapper {
+        py::object triangulator;
+        MapperCandidates candidates;
+        std::map<uint32_t, py::object> candidate_images;  // a copy of what add_candidate was given, for the reconstruction
+        MapperTrials trials;
+        size_t num_total_reg_images = 0;
+        py::dict last;  // last_registration()
+    };
+    // one library call under the estimator context's lock with the GIL released; fn == nullptr only takes the device
+    auto call_library = [](const std::function<int(amc_ctx*)>& fn, const char* name) {
+        int rc = AMC_OK;
+        std::string err;
+        {
+            py::gil_scoped_release release;
+            EstimatorCtx& E = TheEstimatorCtx();
+            std::lock_guard<std::mutex> lock(E.mu);
+            amc_ctx* ctx = nullptr;
+            try {
+                ctx = E.Get();
+            } catch (const std::runtime_error& e) {
+                rc = AMC_E_HIP;
+                err = e.what();
+            }
+            if (ctx && fn) {
+                rc = fn(ctx);
+                if (rc != AMC_OK) err = std::string(name) + ": " + amc_last_error();
+            }
+        }
+        if (rc == AMC_E_INVALID) throw std::invalid_argument(err);
+        if (rc != AMC_OK) {
+            const py::object cls = py::module_::import("pycolmap_amd._capi").attr("AmcError");
+            const py::object exc = cls(rc, err);
+            PyErr_SetObject(cls.ptr(), exc.ptr());
+            throw py::error_already_set();
+        }
+    };
+    auto np_array = [](const auto& v, py::ssize_t cols) {
+        using T = typename std::decay<decltype(v)>::type::value_type;
+        py::array_t<T> a({static_cast<py::ssize_t>(v.size()) / cols, cols});
+        std::copy(v.begin(), v.end(), a.mutable_data());
+        return a;
+    };
+    auto checked_mapper_options = [](const MapperOptions& o) {
+        const std::string bad = o.Check();
+        if (!bad.empty()) throw py::value_error(CheckMessage(__FILE__, __LINE__, bad));
+    };
+    auto find_next_images_with = [checked_model, call_library, np_array, checked_mapper_options](PyMapper& mp, const MapperOptions& o, const py::object& solver) {
+        const auto t0 = std::chrono::steady_clock::now();
+        checked_mapper_options(o);
+        if (solver.is_none()) call_library(nullptr, "");
+        PyTriangulator& t = mp.triangulator.cast<PyTriangulator&>();
+        const CorrespondenceGraph& graph = t.graph.cast<const CorrespondenceGraph&>();
+        const SparseModel model = checked_model(t.reconstruction.cast<PyReconstruction&>());
+        const ModelIndex ix(model, o.BogusThresholds());
+        const FlatVisibility flat = PlanVisibility(graph, model, ix, mp.candidates);
+        std::vector<uint32_t> ranked;
+        double device_ms = 0, kernel_ms = 0, copy_ms = 0;
+        uint64_t calls = 0;
+        const size_t nc = flat.cand_ids.size();
+        if (nc == 0) {
+        } else if (!solver.is_none()) {
+            py::dict d;
+            d["image_point_offsets"] = np_array(flat.image_point_offsets, 1);
+            d["point2D_point3D"] = np_array(flat.point2D_point3D, 1);
+            d["cand_width"] = np_array(flat.cand_width, 1);
+            d["cand_height"] = np_array(flat.cand_height, 1);
+            d["cand_point_offsets"] = np_array(flat.cand_point_offsets, 1);
+            d["cand_xy"] = np_array(flat.cand_xy, 2);
+            d["corr_offsets"] = np_array(flat.corr_offsets, 1);
+            d["corr_image"] = np_array(flat.corr_image, 1);
+            d["corr_point2D"] = np_array(flat.corr_point2D, 1);
+            const py::dict out = solver(d);
+            const auto nobs = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>::ensure(out["num_observations"]);
+            const auto nvis = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>::ensure(out["num_visible_points3D"]);
+            const auto score = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>::ensure(out["score"]);
+            if (!nobs || !nvis || !score || static_cast<size_t>(nobs.size()) != nc || static_cast<size_t>(nvis.size()) != nc || static_cast<size_t>(score.size()) != nc)
+                throw py::value_error("find_next_images: the solver's result does not have the problem's shape");
+            ranked = RankNextImages(flat, nobs.data(), nvis.data(), score.data(), o, mp.trials);
+        } else {
+            const amc_visibility_problem pb = flat.Problem();
+            amc_visibility_result res{};
+            call_library([&](amc_ctx* ctx) { return amc_image_visibility(ctx, &pb, &res); }, "amc_image_visibility");
+            calls = 1;
+            device_ms = res.device_ms;
+            kernel_ms = res.kernel_ms;
+            copy_ms = res.copy_ms;
+            try {
+                ranked = RankNextImages(flat, res.num_observations, res.num_visible_points3D, res.score, o, mp.trials);
+            } catch (...) {
+                amc_visibility_result_free(&res);
+                throw;
+            }
+            amc_visibility_result_free(&res);
+        }
+        py::dict st;
+        st["call"] = "find_next_images";
+        st["num_candidates"] = nc;
+        st["num_ranked"] = ranked.size();
+        st["num_correspondences"] = flat.corr_image.size();
+        st["num_device_calls"] = calls;
+        st["device_ms"] = device_ms;
+        st["kernel_ms"] = kernel_ms;
+        st["copy_ms"] = copy_ms;
+        st["host_ms"] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - device_ms;
+        py::module_::import("pycolmap_amd._pycolmap").attr("_last_stats") = st;
+        return ranked;
+    };
+    auto register_next_image_with = [checked_model, update_from_model, call_library, np_array, checked_mapper_options](
+                                        PyMapper& mp, const MapperOptions& o, uint32_t image_id, const py::object& solver) -> bool {
+        const auto t0 = std::chrono::steady_clock::now();
+        checked_mapper_options(o);
+        if (solver.is_none()) call_library(nullptr, "");
+        PyTriangulator& t = mp.triangulator.cast<PyTriangulator&>();
+        PyReconstruction& r = t.reconstruction.cast<PyReconstruction&>();
+        const CorrespondenceGraph& graph = t.graph.cast<const CorrespondenceGraph&>();
+        const auto cand = mp.candidates.find(image_id);
+        if (cand == mp.candidates.end() || r.images.contains(py::int_(image_id)))
+            throw py::value_error(CheckMessage(__FILE__, __LINE__, "!image.IsRegistered() && IsCandidate(image_id)", "image_id=" + std::to_string(image_id)));
+        const MapperCandidate& c = cand->second;
+        SparseModel model = checked_model(r);
+        ModelIndex ix(model, o.BogusThresholds());
+        const auto cam = ix.camera.find(c.camera_id);
+        if (cam == ix.camera.end()) throw py::value_error("register_next_image: candidate " + std::to_string(image_id) + " names a camera the reconstruction does not hold");
+        const RegistrationPairs pairs = CollectRegistrationPairs(graph, model, ix, c);
+        PyCamera& pycam = r.cameras[py::int_(c.camera_id)].cast<PyCamera&>();
+        pycam.CheckParams();
+        const RegistrationRule rule = PlanRegistration(model, model.cameras[cam->second], pycam.has_prior_focal_length, o);
+        // everything that can refuse the call has: from here on the trial counts
+        mp.trials[image_id] += 1;
+        py::dict last;
+        last["image_id"] = image_id;
+        last["success"] = false;
+        last["num_visible_points3D"] = pairs.num_visible;
+        last["num_pairs"] = pairs.size();
+        last["num_inliers"] = 0;
+        last["focal_factor"] = 1.0;
+        last["estimate_focal_length"] = rule.estimate_focal_length;
+        last["would_refine_focal_length"] = rule.refine_focal_length;
+        last["would_refine_extra_params"] = rule.refine_extra_params;
+        double device_ms = 0, kernel_ms = 0;
+        uint64_t calls = 0;
+        bool ok = pairs.num_visible >= static_cast<size_t>(o.abs_pose_min_num_inliers) && pairs.size() >= static_cast<size_t>(o.abs_pose_min_num_inliers);
+        if (ok) {
+            amc_abspose_opts eo;
+            amc_abspose_opts_default(&eo);
+            eo.estimate_focal_length = rule.estimate_focal_length ? 1 : 0;
+            eo.num_focal_length_samples = 30;
+            eo.min_focal_length_ratio = o.min_focal_length_ratio;
+            eo.max_focal_length_ratio = o.max_focal_length_ratio;
+            eo.max_error = o.abs_pose_max_error;
+            eo.min_inlier_ratio = o.abs_pose_min_inlier_ratio;
+            eo.confidence = 0.99999;
+            eo.dyn_num_trials_multiplier = 3.0;
+            eo.min_num_trials = 100;
+            eo.max_num_trials = 10000;
+            amc_abspose_refine_opts ro;
+            amc_abspose_refine_opts_default(&ro);  // AbsolutePoseRefinementOptions(); intrinsics are never refined (J5)
+            const std::array<double, 12> prm = CameraParams12(pycam);
+            const int32_t cmodel = pycam.model;
+            const size_t n = pairs.size();
+            bool success = false;
+            size_t num_inliers = 0;
+            double focal_factor = 1.0, q[4] = {0, 0, 0, 1}, tv[3] = {0, 0, 0};
+            std::vector<uint8_t> mask(n, 0);
+            if (!solver.is_none()) {
+                py::dict d, est;
+                d["camera_model"] = cmodel;
+                d["camera_params"] = np_array(std::vector<double>(prm.begin(), prm.end()), 12);
+                d["points2D"] = np_array(pairs.points2D, 2);
+                d["points3D"] = np_array(pairs.points3D, 3);
+                est["estimate_focal_length"] = rule.estimate_focal_length;
+                est["num_focal_length_samples"] = eo.num_focal_length_samples;
+                est["min_focal_length_ratio"] = eo.min_focal_length_ratio;
+                est["max_focal_length_ratio"] = eo.max_focal_length_ratio;
+                est["max_error"] = eo.max_error;
+                est["min_inlier_ratio"] = eo.min_inlier_ratio;
+                est["confidence"] = eo.confidence;
+                est["dyn_num_trials_multiplier"] = eo.dyn_num_trials_multiplier;
+                est["min_num_trials"] = eo.min_num_trials;
+                est["max_num_trials"] = eo.max_num_trials;
+                d["estimation"] = est;
+                const py::dict out = solver(d);
+                const auto sq = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(out["qvec"]);
+                const auto stv = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(out["tvec"]);
+                const auto sm = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>::ensure(out["inlier_mask"]);
+                if (!sq || !stv || !sm || sq.size() != 4 || stv.size() != 3 || static_cast<size_t>(sm.size()) != n)
+                    throw py::value_error("register_next_image: the solver's result does not have the problem's shape");
+                success = out["success"].cast<bool>();
+                num_inliers = out["num_inliers"].cast<size_t>();
+                focal_factor = out["focal_factor"].cast<double>();
+                std::copy(sq.data(), sq.data() + 4, q);
+                std::copy(stv.data(), stv.data() + 3, tv);
+                std::copy(sm.data(), sm.data() + n, mask.begin());
+            } else {
+                const uint64_t off[2] = {0, n};
+                amc_abspose_result res{};
+                call_library([&](amc_ctx* ctx) {
+                    return amc_estimate_absolute_poses(ctx, off, 1, &cmodel, prm.data(), pairs.points2D.data(), pairs.points3D.data(), &eo, &ro, 0, &res);
+                }, "amc_estimate_absolute_poses");
+                calls = 1;
+                device_ms = res.device_ms;
+                kernel_ms = res.kernel_ms;
+                success = res.success[0] != 0;
+                num_inliers = res.num_inliers[0];
+                focal_factor = res.focal_factor[0];
+                std::copy(res.qvec, res.qvec + 4, q);
+                std::copy(res.tvec, res.tvec + 3, tv);
+                std::copy(res.inlier_mask, res.inlier_mask + n, mask.begin());
+                amc_abspose_result_free(&res);
+            }
+            last["num_inliers"] = num_inliers;
+            last["focal_factor"] = focal_factor;
+            ok = success && num_inliers >= static_cast<size_t>(o.abs_pose_min_num_inliers);
+            if (ok) {
+                std::set<uint64_t> modified = t.modified;
+                ApplyRegistration(c, pairs, mask.data(), q, tv, rule.estimate_focal_length, focal_factor, &model, &ix, &modified);
+                r.images[py::int_(image_id)] = py::module_::import("copy").attr("copy")(mp.candidate_images.at(image_id));
+                update_from_model(r, model);
+                t.modified.swap(modified);
+                mp.num_total_reg_images += 1;
+                mp.candidate_images.erase(image_id);
+                mp.candidates.erase(cand);
+            }
+        }
+        last["success"] = ok;
+        mp.last = last;
+        py::dict st;
+        st["call"] = "register_next_image";
+        st["num_pairs"] = pairs.size();
+        st["num_device_calls"] = calls;
+        st["device_ms"] = device_ms;
+        st["kernel_ms"] = kernel_ms;
+        st["copy_ms"] = 0.0;
+        st["host_ms"] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - device_ms;
+        py::module_::import("pycolmap_amd._pycolmap").attr("_last_stats") = st;
+        return ok;
+    };
+    auto find_local_bundle_with = [checked_model, call_library, np_array, checked_mapper_options](PyMapper& mp, const MapperOptions& o, uint32_t image_id,
+                                                                                               const py::object& solver, uint64_t max_pair_points) {
+        const auto t0 = std::chrono::steady_clock::now();
+        checked_mapper_options(o);
+        if (solver.is_none()) call_library(nullptr, "");
+        PyTriangulator& t = mp.triangulator.cast<PyTriangulator&>();
+        const SparseModel model = checked_model(t.reconstruction.cast<PyReconstruction&>());
+        const ModelIndex ix(model, o.BogusThresholds());
+        const FlatBundle flat = PlanLocalBundle(model, ix, o, image_id, max_pair_points);
+        std::vector<uint32_t> bundle;
+        double device_ms = 0, kernel_ms = 0, copy_ms = 0;
+        uint64_t calls = 0;
+        if (flat.NumPairs() == 0) {
+            bundle = SelectLocalBundle(flat, o, nullptr);
+        } else if (!solver.is_none()) {
+            py::dict d;
+            d["qvec"] = np_array(flat.qvec, 4);
+            d["tvec"] = np_array(flat.tvec, 3);
+            d["point_xyz"] = np_array(flat.point_xyz, 3);
+            d["pair_images"] = np_array(flat.pair_images, 2);
+            d["pair_offsets"] = np_array(flat.pair_offsets, 1);
+            d["shared_points"] = np_array(flat.shared_points, 1);
+            d["percentile"] = 75.0;
+            const py::dict out = solver(d);
+            const auto angle = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(out["angle"]);
+            if (!angle || static_cast<size_t>(angle.size()) != flat.NumPairs())
+                throw py::value_error("find_local_bundle: the solver's result does not have the problem's shape");
+            bundle = SelectLocalBundle(flat, o, angle.data());
+        } else {
+            const amc_pair_angle_problem pb = flat.Problem();
+            amc_pair_angle_opts po;
+            amc_pair_angle_opts_default(&po);
+            amc_pair_angle_result res{};
+            call_library([&](amc_ctx* ctx) { return amc_shared_point_angles(ctx, &pb, &po, &res); }, "amc_shared_point_angles");
+            calls = 1;
+            device_ms = res.device_ms;
+            kernel_ms = res.kernel_ms;
+            copy_ms = res.copy_ms;
+            try {
+                bundle = SelectLocalBundle(flat, o, res.angle);
+            } catch (...) {
+                amc_pair_angle_result_free(&res);
+                throw;
+            }
+            amc_pair_angle_result_free(&res);
+        }
+        py::dict st;
+        st["call"] = "find_local_bundle";
+        st["num_overlapping_images"] = flat.overlapping.size();
+        st["num_pairs"] = flat.NumPairs();
+        st["num_shared_points"] = flat.shared_points.size();
+        st["num_device_calls"] = calls;
+        st["device_ms"] = device_ms;
+        st["kernel_ms"] = kernel_ms;
+        st["copy_ms"] = copy_ms;
+        st["host_ms"] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - device_ms;
+        py::module_::import("pycolmap_amd._pycolmap").attr("_last_stats") = st;
+        return bundle;
+    };
+    py::class_<PyMapper>(m, "IncrementalMapper")
+        .def(py::init([](const py::object& triangulator) {
+                 if (!py::isinstance<PyTriangulator>(triangulator)) throw py::type_error("IncrementalMapper(triangulator: IncrementalTriangulator)");
+                 PyMapper mp;
+                 mp.triangulator = triangulator;
+                 // BeginReconstruction: every image the model holds already counts as registered
+                 mp.num_total_reg_images = triangulator.cast<PyTriangulator&>().reconstruction.cast<PyReconstruction&>().images.size();
+                 return mp;
+             }), "triangulator"_a)
+        .def("add_candidate", [](PyMapper& mp, const py::object& image) {
+                 const PyImage& im = image.cast<const PyImage&>();
+                 PyTriangulator& t = mp.triangulator.cast<PyTriangulator&>();
+                 const PyReconstruction& r = t.reconstruction.cast<const PyReconstruction&>();
+                 const CorrespondenceGraph& graph = t.graph.cast<const CorrespondenceGraph&>();
+                 if (im.image_id == 0xFFFFFFFFu) throw py::value_error("add_candidate: the image has no image_id");
+                 if (r.images.contains(py::int_(im.image_id))) throw py::value_error("add_candidate: image " + std::to_string(im.image_id) + " is in the reconstruction");
+                 if (mp.candidates.count(im.image_id)) throw py::value_error("add_candidate: image " + std::to_string(im.image_id) + " is a candidate already");
+                 if (!r.cameras.contains(py::int_(im.camera_id))) throw py::value_error("add_candidate: the reconstruction has no camera " + std::to_string(im.camera_id));
+                 if (graph.NumPoints2D(im.image_id) != im.points2D.size())  // an image the graph does not hold: the graph's ValueError
+                     throw py::value_error("add_candidate: image " + std::to_string(im.image_id) + " has " + std::to_string(im.points2D.size()) +
+                                           " points2D, the graph gives it " + std::to_string(graph.NumPoints2D(im.image_id)));
+                 MapperCandidate c;
+                 c.image_id = im.image_id;
+                 c.camera_id = im.camera_id;
+                 for (const PyPoint2D& p : im.points2D) {
+                     if (p.point3D_id != kInvalidPoint3DId) throw py::value_error("add_candidate: a point2D of image " + std::to_string(im.image_id) + " carries a point3D");
+                     c.xy.push_back(p.xy[0]);
+                     c.xy.push_back(p.xy[1]);
+                 }
+                 mp.candidate_images[im.image_id] = py::module_::import("copy").attr("copy")(image);
+                 mp.candidates[im.image_id] = std::move(c);
+             }, "image"_a, "An image that may be registered: an Image with points2D, none carrying a point3D, whose camera the reconstruction holds and whose id the graph knows.")
+        .def_property_readonly("candidates", [](const PyMapper& mp) {
+                 std::vector<uint32_t> ids;
+                 for (const auto& kv : mp.candidates) ids.push_back(kv.first);
+                 return ids;
+             }, "The ids of the candidates, ascending.")
+        .def("num_reg_trials", [](const PyMapper& mp, uint32_t image_id) {
+                 const auto it = mp.trials.find(image_id);
+                 return it == mp.trials.end() ? 0 : it->second;
+             }, "image_id"_a)
+        .def("num_total_reg_images", [](const PyMapper& mp) { return mp.num_total_reg_images; })
+        .def("last_registration", [](const PyMapper& mp) { return py::dict(mp.last.attr("copy")()); },
+             "What the last register_next_image call saw: image_id, success, num_visible_points3D, num_pairs, num_inliers, focal_factor,\n"
+             "estimate_focal_length, and the two refinement flags COLMAP would have set (the refinement here never refines intrinsics).")
+        .def("find_next_images", [find_next_images_with](PyMapper& mp, const MapperOptions& o) { return find_next_images_with(mp, o, py::none()); }, "options"_a,
+             "The candidates worth trying next, best first: never-tried ones before the others, each group by descending rank\n"
+             "(visible points, their ratio or the visibility pyramid score), on the GPU (DESIGN.md section 20).")
+        .def("_find_next_images_with", find_next_images_with, "options"_a, "solver"_a, "find_next_images with a callable in the library's place (test hook).")
+        .def("register_next_image", [register_next_image_with](PyMapper& mp, const MapperOptions& o, uint32_t image_id) {
+                 return register_next_image_with(mp, o, image_id, py::none());
+             }, "options"_a, "image_id"_a,
+             "Estimate the pose of a candidate from its 2D-3D correspondences on the GPU, add it to the reconstruction and\n"
+             "continue the tracks of its inliers (DESIGN.md section 20).  False changes nothing but the trial count.")
+        .def("_register_next_image_with", register_next_image_with, "options"_a, "image_id"_a, "solver"_a,
+             "register_next_image with a callable in the library's place (test hook).")
+        .def("find_local_bundle", [find_local_bundle_with](PyMapper& mp, const MapperOptions& o, uint32_t image_id) {
+                 return find_local_bundle_with(mp, o, image_id, py::none(), AMC_MAPPER_MAX_PAIR_POINTS);
+             }, "options"_a, "image_id"_a,
+             "The images of the local bundle adjustment around a model image: its most overlapping images with a sufficient\n"
+             "75th-percentile triangulation angle, on the GPU (DESIGN.md section 20).  The image itself is not in the list.")
+        .def("_find_local_bundle_with", find_local_bundle_with, "options"_a, "image_id"_a, "solver"_a,
+             "max_pair_points"_a = static_cast<uint64_t>(AMC_MAPPER_MAX_PAIR_POINTS), "find_local_bundle with a callable in the library's place (test hook).")
+        .def_property_readonly("triangulator", [](const PyMapper& mp) { return mp.triangulator; })
+        .def_property_readonly("reconstruction", [](const PyMapper& mp) { return mp.triangulator.cast<PyTriangulator&>().reconstruction; })
+        .def_property_readonly("correspondence_graph", [](const PyMapper& mp) { return mp.triangulator.cast<PyTriangulator&>().graph; })
+        .def("__copy__", [](const PyMapper& mp) {
+                 PyMapper c(mp);
+                 c.last = py::dict(mp.last.attr("copy")());
+                 return c;
+             })
+        .def("__deepcopy__", [](const PyMapper& mp, const py::dict& memo) {
+                 const py::object deepcopy = py::module_::import("copy").attr("deepcopy");
+                 PyMapper c(mp);
+                 c.triangulator = deepcopy(mp.triangulator, memo);
+                 for (auto& kv : c.candidate_images) kv.second = deepcopy(kv.second, memo);
+                 c.last = py::dict(mp.last.attr("copy")());
+                 return c;
+             })
+        .def("__repr__", [](const PyMapper& mp) {
+            const PyReconstruction& r = mp.triangulator.cast<PyTriangulator&>().reconstruction.cast<const PyReconstruction&>();
+            return "IncrementalMapper(num_reg_images=" + std::to_string(r.images.size()) + ", num_candidates=" + std::to_string(mp.candidates.size()) +
+                   ", num_total_reg_images=" + std::to_string(mp.num_total_reg_images) + ")";
+        });
 
     // ---- estimate_triangulation (/root/reference/pycolmap/estimators/triangulation.h; tri_host.h) ----------------------
     py::class_<TriPointData>(m, "PointData")

@@ -15,14 +15,14 @@ __version__ = "0.1.0"
 
 try:  # the compiled host layer; absent only before `python -m pycolmap_amd.build`
     from ._pycolmap import (  # noqa: F401
-        AbsolutePoseEstimationOptions, AbsolutePoseRefinementOptions, BundleAdjuster, BundleAdjustmentConfig, BundleAdjustmentOptions, Correspondence, CorrespondenceGraph, ImageSelectionMethod, IncrementalMapper, IncrementalMapperOptions, IncrementalTriangulator, IncrementalTriangulatorOptions, CeresSolverOptions, LossFunctionType, Point2D, Point3D, Reconstruction, Track, TrackElement, bundle_adjustment, complete_all_tracks, complete_tracks, COLMAP_build, COLMAP_version, Camera, CopyType, UndistortCameraOptions, undistort_camera, undistort_image, CameraMode, CameraModelId, Database, DatabaseTransaction, Device, EstimateTriangulationOptions, ExhaustiveMatchingOptions, Image, ImageReaderOptions, Normalization, PointData, RANSACOptions, Rigid3d,
+        AbsolutePoseEstimationOptions, AbsolutePoseRefinementOptions, BundleAdjuster, BundleAdjustmentConfig, BundleAdjustmentOptions, Correspondence, CorrespondenceGraph, ImageSelectionMethod, IncrementalMapper, IncrementalMapperOptions, IncrementalTriangulator, IncrementalTriangulatorOptions, CeresSolverOptions, LossFunctionType, Point2D, Point3D, Reconstruction, Track, TrackElement, adjust_global_bundle, bundle_adjustment, complete_all_tracks, complete_tracks, COLMAP_build, COLMAP_version, Camera, CopyType, UndistortCameraOptions, undistort_camera, undistort_image, CameraMode, CameraModelId, Database, DatabaseTransaction, Device, EstimateTriangulationOptions, ExhaustiveMatchingOptions, Image, ImageReaderOptions, Normalization, PointData, RANSACOptions, Rigid3d,
         Rotation3d, Sift, SiftExtractionOptions,
         SequentialMatchingOptions, SiftMatchingOptions, SpatialMatchingOptions, TwoViewGeometry, TwoViewGeometryConfiguration,
         VocabTreeMatchingOptions,
         TwoViewGeometryOptions, absolute_pose_estimation, essential_matrix_estimation, estimate_calibrated_two_view_geometry,
-        estimate_triangulation, estimate_two_view_geometry, estimate_two_view_geometry_pose, fundamental_matrix_estimation, has_cuda,
+        estimate_triangulation, estimate_two_view_geometry, estimate_two_view_geometry_pose, filter_images, fundamental_matrix_estimation, has_cuda,
         has_hip, homography_decomposition, homography_matrix_estimation, last_run_stats, logging, match_exhaustive, merge_all_tracks, merge_tracks, match_sequential,
-        match_spatial, match_vocabtree, pose_refinement, retriangulate, rig_absolute_pose_estimation, squared_sampson_error, verify_matches,
+        match_spatial, match_vocabtree, pose_refinement, register_initial_image_pair, retriangulate, rig_absolute_pose_estimation, squared_sampson_error, verify_matches,
     )
     from ._extraction import extract_features  # noqa: F401
     from ._undistortion import _undistort_plan, undistort_images  # noqa: F401

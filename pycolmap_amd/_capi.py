@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "amc_retri_opts_default", "amc_retriangulate_pairs", "amc_retri_result_free",
     "amc_image_visibility", "amc_visibility_result_free",
     "amc_pair_angle_opts_default", "amc_shared_point_angles", "amc_pair_angle_result_free",
+    "amc_pair_tri_opts_default", "amc_triangulate_pairs", "amc_pair_tri_result_free",
 ]
 COMM_ID_BYTES = 128
 RANSAC_F, RANSAC_H, RANSAC_E = 0, 1, 2
@@ -535,6 +536,58 @@ def pair_angle_inputs(qvec, tvec, point_xyz, pair_images, pair_offsets, shared_p
     if poff.size != pi.shape[0] + 1 or int(poff[-1]) != sp.size:
         raise ValueError(f"{who}: {pi.shape[0]} pairs, {poff.size} offsets ending at {int(poff[-1])}, {sp.size} shared points")
     return q, t, X, pi, poff, sp
+
+
+class PairTriOpts(C.Structure):  # amc_pair_tri_opts (include/amc_initpair.h)
+    _fields_ = [("min_tri_angle", C.c_double), ("reserved", C.c_double)]
+
+
+class PairTriProblem(C.Structure):  # amc_pair_tri_problem
+    _fields_ = [("num_cameras", C.c_size_t), ("camera_models", C.c_void_p), ("camera_params", C.c_void_p),
+                ("num_images", C.c_size_t), ("image_cameras", C.c_void_p), ("qvec", C.c_void_p), ("tvec", C.c_void_p),
+                ("num_pairs", C.c_size_t), ("pair_images", C.c_void_p), ("pair_offsets", C.c_void_p),
+                ("corr_xy1", C.c_void_p), ("corr_xy2", C.c_void_p)]
+
+
+class PairTriResult(C.Structure):  # amc_pair_tri_result
+    _fields_ = [("num_pairs", C.c_uint64), ("num_corrs", C.c_uint64), ("num_accepted", C.c_uint64),
+                ("accepted", C.POINTER(C.c_uint8)), ("xyz", C.POINTER(C.c_double)), ("tri_angle", C.POINTER(C.c_double)),
+                ("num_batches", C.c_uint32), ("reserved", C.c_uint32),
+                ("host_ms", C.c_double), ("device_ms", C.c_double), ("kernel_ms", C.c_double), ("copy_ms", C.c_double),
+                ("alloc_ms", C.c_double)]
+
+
+INITPAIR_MAX_CORRS = 1 << 26
+INITPAIR_DEFAULT_MIN_TRI_ANGLE = 0.017453292519943295 * 16.0  # DegToRad(IncrementalMapperOptions.init_min_tri_angle)
+
+
+def pair_tri_inputs(camera_models, camera_params, image_cameras, qvec, tvec, pair_images, pair_offsets, corr_xy1, corr_xy2):
+    """The flat problem of amc_triangulate_pairs as contiguous arrays (copies: the caller's arrays are not touched):
+    models (C,) int32, params (C, 12), image_cameras (I,) uint32, qvec (I, 4) x y z w, tvec (I, 3), pair_images (K, 2)
+    uint32, pair_offsets (K + 1,) uint64, corr_xy1 / corr_xy2 (M, 2) pixels."""
+    who = "triangulate_pairs"
+    models = np.array(camera_models, dtype=np.int32).reshape(-1)
+    if len(camera_params) != models.size:
+        raise ValueError(f"{who}: {models.size} camera models, {len(camera_params)} parameter sets")
+    prm = np.zeros((models.size, 12), np.float64)
+    for i, p in enumerate(camera_params):
+        p = np.asarray(p, dtype=np.float64).reshape(-1)
+        if p.size > 12:
+            raise ValueError(f"{who}: camera {i} has {p.size} parameters (at most 12)")
+        prm[i, :p.size] = p
+    icam = _u32_index(who, "image_cameras", image_cameras)
+    q = np.array(qvec, dtype=np.float64).reshape(-1, 4)
+    t = np.array(tvec, dtype=np.float64).reshape(-1, 3)
+    pi = np.ascontiguousarray(_u32_index(who, "pair_images", pair_images).reshape(-1, 2))
+    poff = _offsets(who, "pair_offsets", pair_offsets)
+    xy1 = np.array(corr_xy1, dtype=np.float64).reshape(-1, 2)
+    xy2 = np.array(corr_xy2, dtype=np.float64).reshape(-1, 2)
+    if q.shape[0] != icam.size or t.shape[0] != icam.size:
+        raise ValueError(f"{who}: {icam.size} images by image_cameras, {q.shape[0]} rotations, {t.shape[0]} translations")
+    if poff.size != pi.shape[0] + 1 or int(poff[-1]) != xy1.shape[0] or xy1.shape[0] != xy2.shape[0]:
+        raise ValueError(f"{who}: {pi.shape[0]} pairs, {poff.size} offsets ending at {int(poff[-1])}, {xy1.shape[0]} and "
+                         f"{xy2.shape[0]} pixels")
+    return models, prm, icam, q, t, pi, poff, xy1, xy2
 
 
 RETRI_NONE, RETRI_CONTINUE_1TO2, RETRI_CONTINUE_2TO1, RETRI_CREATED = 0, 1, 2, 3
@@ -1037,6 +1090,13 @@ def load() -> C.CDLL:
         lib.amc_shared_point_angles.restype = C.c_int
         lib.amc_pair_angle_result_free.argtypes = [C.POINTER(PairAngleResult)]
         lib.amc_pair_angle_result_free.restype = None
+    if hasattr(lib, "amc_triangulate_pairs"):  # (absent from a library built from an older revision)
+        lib.amc_pair_tri_opts_default.argtypes = [C.POINTER(PairTriOpts)]
+        lib.amc_pair_tri_opts_default.restype = None
+        lib.amc_triangulate_pairs.argtypes = [C.c_void_p, C.POINTER(PairTriProblem), C.POINTER(PairTriOpts), C.POINTER(PairTriResult)]
+        lib.amc_triangulate_pairs.restype = C.c_int
+        lib.amc_pair_tri_result_free.argtypes = [C.POINTER(PairTriResult)]
+        lib.amc_pair_tri_result_free.restype = None
     if hasattr(lib, "amc_triangulate_tracks"):  # (absent from a library built from an older revision)
         lib.amc_tri_opts_default.argtypes = [C.POINTER(TriOpts)]
         lib.amc_tri_opts_default.restype = None
@@ -1683,6 +1743,33 @@ class Context:
                    "copy_ms": res.copy_ms, "alloc_ms": res.alloc_ms}
         finally:
             self._lib.amc_pair_angle_result_free(C.byref(res))
+        return out
+
+    def triangulate_pairs(self, camera_models, camera_params, image_cameras, qvec, tvec, pair_images, pair_offsets, corr_xy1,
+                          corr_xy2, min_tri_angle=INITPAIR_DEFAULT_MIN_TRI_ANGLE):
+        """amc_triangulate_pairs: the two-view triangulation of every correspondence of a batch of image pairs, as
+        COLMAP's RegisterInitialImagePair does it.  The cameras and images as in
+        triangulate_observations; pair_images (K, 2); pair_offsets (K + 1,) CSR over corr_xy1 / corr_xy2 (M, 2), the
+        pixels in the pair's first and second image.  min_tri_angle is in radians.  The inputs are not modified.
+        Returns a dict: accepted (M,) bool, xyz (M, 3), tri_angle (M,) radians, num_accepted, num_batches, host_ms,
+        device_ms, kernel_ms, copy_ms, alloc_ms."""
+        models, prm, icam, q, t, pi, poff, xy1, xy2 = pair_tri_inputs(camera_models, camera_params, image_cameras, qvec, tvec,
+                                                                      pair_images, pair_offsets, corr_xy1, corr_xy2)
+        ptr = lambda v: v.ctypes.data_as(C.c_void_p)  # noqa: E731
+        o = PairTriOpts(float(min_tri_angle), 0.0)
+        pb = PairTriProblem(models.size, ptr(models), ptr(prm), icam.size, ptr(icam), ptr(q), ptr(t), pi.shape[0], ptr(pi),
+                            ptr(poff), ptr(xy1), ptr(xy2))
+        res = PairTriResult()
+        _check(self._lib.amc_triangulate_pairs(self._h, C.byref(pb), C.byref(o), C.byref(res)))
+        try:
+            n = xy1.shape[0]
+            arr = lambda p, k: np.ctypeslib.as_array(p, (max(k, 1),))[:k].copy()  # noqa: E731
+            out = {"accepted": arr(res.accepted, n).astype(bool), "xyz": arr(res.xyz, 3 * n).reshape(n, 3),
+                   "tri_angle": arr(res.tri_angle, n), "num_accepted": int(res.num_accepted),
+                   "num_batches": int(res.num_batches), "host_ms": res.host_ms, "device_ms": res.device_ms,
+                   "kernel_ms": res.kernel_ms, "copy_ms": res.copy_ms, "alloc_ms": res.alloc_ms}
+        finally:
+            self._lib.amc_pair_tri_result_free(C.byref(res))
         return out
 
     def estimate_rig_absolute_poses(self, offsets, camera_offsets, camera_models, camera_params, cams_from_rig,

@@ -164,9 +164,11 @@ inline FlatVisibility PlanVisibility(const CorrespondenceGraph& graph, const Spa
 }
 
 // 20.1: drop, rank as float, never-tried candidates first, each group by descending rank then ascending image id; a NaN
-// rank (which Check() excludes) would come last.  The arrays have amc_visibility_result's shapes.
+// rank (which Check() excludes) would come last.  The arrays have amc_visibility_result's shapes.  A candidate that
+// filter_images removed from the model (`filtered`, 21.4) goes with the tried ones, as COLMAP's filtered_images_ does.
 inline std::vector<uint32_t> RankNextImages(const FlatVisibility& f, const uint32_t* num_observations, const uint32_t* num_visible,
-                                            const uint64_t* score, const MapperOptions& o, const MapperTrials& trials) {
+                                            const uint64_t* score, const MapperOptions& o, const MapperTrials& trials,
+                                            const std::set<uint32_t>* filtered = nullptr) {
     std::vector<std::pair<uint32_t, float>> groups[2];
     for (size_t c = 0; c < f.cand_ids.size(); ++c) {
         if (static_cast<size_t>(num_visible[c]) < static_cast<size_t>(o.abs_pose_min_num_inliers)) continue;
@@ -179,7 +181,8 @@ inline std::vector<uint32_t> RankNextImages(const FlatVisibility& f, const uint3
             case ImageSelectionMethod::MAX_VISIBLE_POINTS_RATIO: rank = static_cast<float>(num_visible[c]) / static_cast<float>(num_observations[c]); break;
             case ImageSelectionMethod::MIN_UNCERTAINTY: rank = static_cast<float>(score[c]); break;
         }
-        groups[tried == 0 ? 0 : 1].emplace_back(f.cand_ids[c], rank);
+        const bool was_filtered = filtered && filtered->count(f.cand_ids[c]);
+        groups[tried == 0 && !was_filtered ? 0 : 1].emplace_back(f.cand_ids[c], rank);
     }
     std::vector<uint32_t> out;
     for (auto& g : groups) {

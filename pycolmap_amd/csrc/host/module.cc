@@ -43,6 +43,7 @@
 #include "undistort_host.h"
 #include "ba_config_host.h"
 #include "ba_host.h"
+#include "initial_pair_host.h"
 #include "mapper_host.h"
 #include "reconstruction.h"
 #include "retriangulate_host.h"
@@ -2409,6 +2410,11 @@ PYBIND11_MODULE(_pycolmap, m) {
         MapperTrials trials;
         size_t num_total_reg_images = 0;
         py::dict last;  // last_registration()
+        // the registered images in COLMAP's reg_image_ids_ order, the images the model held when the mapper
+        // was made (existing_image_ids_), the images filter_images removed (filtered_images_)
+        std::vector<uint32_t> reg_image_ids;
+        std::set<uint32_t> existing_image_ids, filtered_images;
+        py::dict last_pair;  // last_initial_pair()
     };
     // one library call under the estimator context's lock with the GIL released; fn == nullptr only takes the device
     auto call_library = [](const std::function<int(amc_ctx*)>& fn, const char* name) {
@@ -2479,7 +2485,7 @@ PYBIND11_MODULE(_pycolmap, m) {
             const auto score = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>::ensure(out["score"]);
             if (!nobs || !nvis || !score || static_cast<size_t>(nobs.size()) != nc || static_cast<size_t>(nvis.size()) != nc || static_cast<size_t>(score.size()) != nc)
                 throw py::value_error("find_next_images: the solver's result does not have the problem's shape");
-            ranked = RankNextImages(flat, nobs.data(), nvis.data(), score.data(), o, mp.trials);
+            ranked = RankNextImages(flat, nobs.data(), nvis.data(), score.data(), o, mp.trials, &mp.filtered_images);
         } else {
             const amc_visibility_problem pb = flat.Problem();
             amc_visibility_result res{};
@@ -2489,7 +2495,7 @@ PYBIND11_MODULE(_pycolmap, m) {
             kernel_ms = res.kernel_ms;
             copy_ms = res.copy_ms;
             try {
-                ranked = RankNextImages(flat, res.num_observations, res.num_visible_points3D, res.score, o, mp.trials);
+                ranked = RankNextImages(flat, res.num_observations, res.num_visible_points3D, res.score, o, mp.trials, &mp.filtered_images);
             } catch (...) {
                 amc_visibility_result_free(&res);
                 throw;
@@ -2622,6 +2628,7 @@ PYBIND11_MODULE(_pycolmap, m) {
                 update_from_model(r, model);
                 t.modified.swap(modified);
                 mp.num_total_reg_images += 1;
+                mp.reg_image_ids.push_back(image_id);
                 mp.candidate_images.erase(image_id);
                 mp.candidates.erase(cand);
             }
@@ -2698,13 +2705,238 @@ PYBIND11_MODULE(_pycolmap, m) {
         py::module_::import("pycolmap_amd._pycolmap").attr("_last_stats") = st;
         return bundle;
     };
+
+    // ---- the initial pair, the global adjustment and the image filter (initial_pair_host.h) ----
+    // Module-level functions that take the mapper first, as complete_tracks takes the triangulator: existing tests pin
+    // that the class has no such methods.
+    // reg_image_ids against a reconstruction that changed behind the mapper's back (K2): ids that left the model leave
+    // the list, model images the list lacks join it in ascending id
+    auto sync_reg_image_ids = [](PyMapper& mp) {
+        const PyReconstruction& r = mp.triangulator.cast<PyTriangulator&>().reconstruction.cast<const PyReconstruction&>();
+        std::vector<uint32_t> kept, extra;
+        std::set<uint32_t> seen;
+        for (uint32_t id : mp.reg_image_ids)
+            if (r.images.contains(py::int_(id)) && seen.insert(id).second) kept.push_back(id);
+        for (auto item : r.images)
+            if (!seen.count(item.first.cast<uint32_t>())) extra.push_back(item.first.cast<uint32_t>());
+        std::sort(extra.begin(), extra.end());
+        kept.insert(kept.end(), extra.begin(), extra.end());
+        mp.reg_image_ids.swap(kept);
+    };
+    // RegisterInitialImagePair (21.1, 21.2).  two_view_solver: None, or a callable (camera1, points1, camera2, points2,
+    // matches, options) -> dict of the geometry after the pose step (pose_ok, config, inlier_matches (K, 2), qvec x y z w,
+    // tvec, tri_angle) in the place of estimate_calibrated_two_view_geometry and estimate_two_view_geometry_pose; pair_solver: None, or a callable that takes
+    // the flat problem of amc_triangulate_pairs as a dict of arrays and returns accepted, xyz and tri_angle.
+    auto register_initial_image_pair_with = [checked_model, update_with_new_points, call_library, np_array, checked_mapper_options](
+                                                PyMapper& mp, const MapperOptions& o, uint32_t id1, uint32_t id2, const py::object& two_view_solver,
+                                                const py::object& pair_solver) -> bool {
+        const auto t0 = std::chrono::steady_clock::now();
+        checked_mapper_options(o);
+        if (two_view_solver.is_none() || pair_solver.is_none()) call_library(nullptr, "");
+        PyTriangulator& t = mp.triangulator.cast<PyTriangulator&>();
+        PyReconstruction& r = t.reconstruction.cast<PyReconstruction&>();
+        const CorrespondenceGraph& graph = t.graph.cast<const CorrespondenceGraph&>();
+        const auto cand1 = mp.candidates.find(id1), cand2 = mp.candidates.find(id2);
+        if (id1 == id2 || cand1 == mp.candidates.end() || cand2 == mp.candidates.end() || r.images.contains(py::int_(id1)) || r.images.contains(py::int_(id2)))
+            throw py::value_error(CheckMessage(__FILE__, __LINE__, "image_id1 != image_id2 && IsCandidate(image_id1) && IsCandidate(image_id2)",
+                                               "image_id1=" + std::to_string(id1) + ", image_id2=" + std::to_string(id2)));
+        const MapperCandidate& c1 = cand1->second;
+        const MapperCandidate& c2 = cand2->second;
+        SparseModel model = checked_model(r);
+        ModelIndex ix(model, o.BogusThresholds());
+        const auto cam1 = ix.camera.find(c1.camera_id), cam2 = ix.camera.find(c2.camera_id);
+        if (cam1 == ix.camera.end() || cam2 == ix.camera.end()) throw py::value_error("register_initial_image_pair: a candidate names a camera the reconstruction does not hold");
+        const py::object pycam1 = r.cameras[py::int_(c1.camera_id)], pycam2 = r.cameras[py::int_(c2.camera_id)];
+        pycam1.cast<PyCamera&>().CheckParams();
+        pycam2.cast<PyCamera&>().CheckParams();
+        if (graph.NumPoints2D(id1) != c1.NumPoints2D() || graph.NumPoints2D(id2) != c2.NumPoints2D())
+            throw py::value_error("register_initial_image_pair: a candidate's number of points2D differs from the graph's");
+        const std::vector<uint32_t> matches = graph.FindCorrespondencesBetweenImages(id1, id2);
+        const double identity_q[4] = {0, 0, 0, 1}, zero_t[3] = {0, 0, 0};
+        FlatInitialPair flat = PlanInitialPair(model.cameras[cam1->second], model.cameras[cam2->second], c1, c2, matches, identity_q, zero_t);
+        // EstimateInitialTwoViewGeometry
+        TwoViewGeometryOptions tvo;
+        tvo.ransac_options.min_num_trials = 30;
+        tvo.ransac_options.max_error = o.init_max_error;
+        const py::object pts1 = np_array(c1.xy, 2), pts2 = np_array(c2.xy, 2), marr = MatchesArray(matches);
+        PyTwoViewGeometry G;
+        bool pose_ok = false;
+        if (two_view_solver.is_none()) {
+            const py::module_ mod = py::module_::import("pycolmap_amd._pycolmap");
+            const py::object geometry = mod.attr("estimate_calibrated_two_view_geometry")(pycam1, pts1, pycam2, pts2, marr, tvo);
+            pose_ok = mod.attr("estimate_two_view_geometry_pose")(pycam1, pts1, pycam2, pts2, geometry).cast<bool>();
+            G = geometry.cast<PyTwoViewGeometry>();
+        } else {
+            const py::dict out = two_view_solver(pycam1, pts1, pycam2, pts2, marr, tvo);
+            const auto im = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>::ensure(out["inlier_matches"]);
+            const auto sq = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(out["qvec"]);
+            const auto stv = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(out["tvec"]);
+            if (!im || !sq || !stv || im.size() % 2 != 0 || sq.size() != 4 || stv.size() != 3)
+                throw py::value_error("register_initial_image_pair: the two-view solver's result does not have the expected shape");
+            pose_ok = out["pose_ok"].cast<bool>();
+            G.config = out["config"].cast<int>();
+            G.inlier_matches.assign(im.data(), im.data() + im.size());
+            std::copy(sq.data(), sq.data() + 4, G.cam2_from_cam1.rotation.xyzw.begin());
+            std::copy(stv.data(), stv.data() + 3, G.cam2_from_cam1.translation.begin());
+            G.tri_angle = out["tri_angle"].cast<double>();
+        }
+        // everything that can refuse the call has: from here on the trials count
+        mp.trials[id1] += 1;
+        mp.trials[id2] += 1;
+        const size_t num_inliers = G.inlier_matches.size() / 2;
+        const double tz = G.cam2_from_cam1.translation[2];
+        bool ok = InitialPairAccepted(pose_ok, num_inliers, tz, G.tri_angle, o);
+        py::dict last;
+        last["image_id1"] = id1;
+        last["image_id2"] = id2;
+        last["success"] = false;
+        last["num_correspondences"] = flat.NumCorrs();
+        last["num_inliers"] = num_inliers;
+        last["tri_angle"] = G.tri_angle;
+        last["translation_z"] = tz;
+        last["config"] = G.config;
+        last["num_points3D"] = 0;
+        double device_ms = 0, kernel_ms = 0, copy_ms = 0;
+        uint64_t calls = 0;
+        if (ok) {
+            for (int k = 0; k < 4; ++k) flat.qvec[4 + k] = G.cam2_from_cam1.rotation.xyzw[k];
+            for (int k = 0; k < 3; ++k) flat.tvec[3 + k] = G.cam2_from_cam1.translation[k];
+            const size_t n = flat.NumCorrs();
+            const double min_tri_angle = kMapperDegToRad * o.init_min_tri_angle;
+            std::vector<uint8_t> accepted(n, 0);
+            std::vector<double> xyz(3 * n, 0.0);
+            if (!pair_solver.is_none()) {
+                py::dict d;
+                d["camera_models"] = np_array(flat.camera_models, 1);
+                d["camera_params"] = np_array(flat.camera_params, 12);
+                d["image_cameras"] = np_array(flat.image_cameras, 1);
+                d["qvec"] = np_array(flat.qvec, 4);
+                d["tvec"] = np_array(flat.tvec, 3);
+                d["pair_images"] = np_array(flat.pair_images, 2);
+                d["pair_offsets"] = np_array(flat.pair_offsets, 1);
+                d["corr_xy1"] = np_array(flat.corr_xy1, 2);
+                d["corr_xy2"] = np_array(flat.corr_xy2, 2);
+                d["min_tri_angle"] = min_tri_angle;
+                const py::dict out = pair_solver(d);
+                const auto sa = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>::ensure(out["accepted"]);
+                const auto sx = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(out["xyz"]);
+                if (!sa || !sx || static_cast<size_t>(sa.size()) != n || static_cast<size_t>(sx.size()) != 3 * n)
+                    throw py::value_error("register_initial_image_pair: the solver's result does not have the problem's shape");
+                std::copy(sa.data(), sa.data() + n, accepted.begin());
+                std::copy(sx.data(), sx.data() + 3 * n, xyz.begin());
+            } else {
+                const amc_pair_tri_problem pb = flat.Problem();
+                amc_pair_tri_opts po;
+                amc_pair_tri_opts_default(&po);
+                po.min_tri_angle = min_tri_angle;
+                amc_pair_tri_result res{};
+                call_library([&](amc_ctx* ctx) { return amc_triangulate_pairs(ctx, &pb, &po, &res); }, "amc_triangulate_pairs");
+                calls = 1;
+                device_ms = res.device_ms;
+                kernel_ms = res.kernel_ms;
+                copy_ms = res.copy_ms;
+                std::copy(res.accepted, res.accepted + n, accepted.begin());
+                std::copy(res.xyz, res.xyz + 3 * n, xyz.begin());
+                amc_pair_tri_result_free(&res);
+            }
+            const size_t created = ApplyInitialPair(c1, c2, flat, accepted.data(), xyz.data(), &model, &ix);
+            const py::object copy = py::module_::import("copy").attr("copy");
+            r.images[py::int_(id1)] = copy(mp.candidate_images.at(id1));
+            r.images[py::int_(id2)] = copy(mp.candidate_images.at(id2));
+            update_with_new_points(r, model);  // (the created points do not enter the triangulator's modified set, as in COLMAP)
+            last["num_points3D"] = created;
+            mp.num_total_reg_images += 2;
+            mp.reg_image_ids.push_back(id1);
+            mp.reg_image_ids.push_back(id2);
+            mp.candidate_images.erase(id1);
+            mp.candidate_images.erase(id2);
+            mp.candidates.erase(id1);
+            mp.candidates.erase(id2);
+        }
+        last["success"] = ok;
+        mp.last_pair = last;
+        py::dict st;
+        st["call"] = "register_initial_image_pair";
+        st["num_correspondences"] = flat.NumCorrs();
+        st["num_device_calls"] = calls;
+        st["device_ms"] = device_ms;
+        st["kernel_ms"] = kernel_ms;
+        st["copy_ms"] = copy_ms;
+        st["host_ms"] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - device_ms;
+        py::module_::import("pycolmap_amd._pycolmap").attr("_last_stats") = st;
+        return ok;
+    };
+    // AdjustGlobalBundle with Reconstruction::Normalize (21.3).  solver: None, or BundleAdjuster._solve_with's callable.
+    auto adjust_global_bundle_with = [checked_model, update_from_model, adjuster_solve, call_library, checked_mapper_options, sync_reg_image_ids](
+                                         PyMapper& mp, const MapperOptions& o, const BundleAdjustmentOptions& ba_options, const py::object& solver) -> bool {
+        checked_mapper_options(o);
+        sync_reg_image_ids(mp);
+        if (mp.reg_image_ids.size() < 2) throw py::value_error(CheckMessage(__FILE__, __LINE__, "reg_image_ids.size() >= 2", "adjust_global_bundle"));
+        if (solver.is_none()) call_library(nullptr, "");
+        PyReconstruction& r = mp.triangulator.cast<PyTriangulator&>().reconstruction.cast<PyReconstruction&>();
+        {
+            SparseModel m = checked_model(r);  // "avoid degeneracies in bundle adjustment"
+            FilterObservationsWithNegativeDepth(&m);
+            update_from_model(r, m);
+        }
+        PyBundleAdjuster adjuster{ba_options, GlobalBundleConfig(mp.reg_image_ids, mp.existing_image_ids, o.fix_existing_images), py::dict()};
+        if (!adjuster_solve(adjuster, r, solver)) return false;
+        const py::object stats = py::module_::import("pycolmap_amd._pycolmap").attr("_last_stats");
+        SparseModel m = checked_model(r);
+        const NormalizeResult nr = NormalizeModel(&m, mp.reg_image_ids);
+        update_from_model(r, m);
+        py::dict st(stats.attr("copy")());
+        st["call"] = "adjust_global_bundle";
+        st["normalize_scale"] = nr.scale;
+        py::module_::import("pycolmap_amd._pycolmap").attr("_last_stats") = st;
+        return true;
+    };
+    // FilterImages (21.4): host code, no device
+    auto filter_images = [checked_model, update_from_model, checked_mapper_options, sync_reg_image_ids](PyMapper& mp, const MapperOptions& o) -> size_t {
+        checked_mapper_options(o);
+        sync_reg_image_ids(mp);
+        PyTriangulator& t = mp.triangulator.cast<PyTriangulator&>();
+        PyReconstruction& r = t.reconstruction.cast<PyReconstruction&>();
+        SparseModel m = checked_model(r);
+        const std::vector<uint32_t> gone = PlanFilterImages(m, mp.reg_image_ids, o);
+        if (gone.empty()) return 0;
+        for (uint32_t id : gone) DeRegisterImage(&m, id);
+        const py::object copy = py::module_::import("copy").attr("copy");
+        for (uint32_t id : gone) {
+            // the image becomes a candidate again, none of its points2D carrying a point3D
+            py::object image = copy(r.images[py::int_(id)]);
+            PyImage& im = image.cast<PyImage&>();
+            MapperCandidate c;
+            c.image_id = id;
+            c.camera_id = im.camera_id;
+            for (PyPoint2D& p : im.points2D) {
+                p.point3D_id = kInvalidPoint3DId;
+                c.xy.push_back(p.xy[0]);
+                c.xy.push_back(p.xy[1]);
+            }
+            mp.candidate_images[id] = image;
+            mp.candidates[id] = std::move(c);
+            mp.filtered_images.insert(id);
+            r.images.attr("pop")(py::int_(id));
+        }
+        update_from_model(r, m);
+        std::set<uint64_t> modified;  // points that left the model leave the triangulator's modified set
+        for (uint64_t pid : t.modified)
+            if (r.points3D.contains(py::int_(pid))) modified.insert(pid);
+        t.modified.swap(modified);
+        sync_reg_image_ids(mp);
+        return gone.size();
+    };
     py::class_<PyMapper>(m, "IncrementalMapper")
         .def(py::init([](const py::object& triangulator) {
                  if (!py::isinstance<PyTriangulator>(triangulator)) throw py::type_error("IncrementalMapper(triangulator: IncrementalTriangulator)");
                  PyMapper mp;
                  mp.triangulator = triangulator;
                  // BeginReconstruction: every image the model holds already counts as registered
-                 mp.num_total_reg_images = triangulator.cast<PyTriangulator&>().reconstruction.cast<PyReconstruction&>().images.size();
+                 const PyReconstruction& r = triangulator.cast<PyTriangulator&>().reconstruction.cast<PyReconstruction&>();
+                 mp.num_total_reg_images = r.images.size();
+                 for (auto item : r.images) mp.existing_image_ids.insert(item.first.cast<uint32_t>());
+                 mp.reg_image_ids.assign(mp.existing_image_ids.begin(), mp.existing_image_ids.end());
                  return mp;
              }), "triangulator"_a)
         .def("add_candidate", [](PyMapper& mp, const py::object& image) {
@@ -2767,6 +2999,7 @@ PYBIND11_MODULE(_pycolmap, m) {
         .def("__copy__", [](const PyMapper& mp) {
                  PyMapper c(mp);
                  c.last = py::dict(mp.last.attr("copy")());
+                 c.last_pair = py::dict(mp.last_pair.attr("copy")());
                  return c;
              })
         .def("__deepcopy__", [](const PyMapper& mp, const py::dict& memo) {
@@ -2775,13 +3008,52 @@ PYBIND11_MODULE(_pycolmap, m) {
                  c.triangulator = deepcopy(mp.triangulator, memo);
                  for (auto& kv : c.candidate_images) kv.second = deepcopy(kv.second, memo);
                  c.last = py::dict(mp.last.attr("copy")());
+                 c.last_pair = py::dict(mp.last_pair.attr("copy")());
                  return c;
              })
+        .def("last_initial_pair", [](const PyMapper& mp) { return py::dict(mp.last_pair.attr("copy")()); },
+             "What the last register_initial_image_pair call saw: image_id1, image_id2, success, num_correspondences, num_inliers,\n"
+             "tri_angle, translation_z, config and num_points3D (DESIGN.md section 21); empty before the first call.")
+        .def_property_readonly("reg_image_ids", [sync_reg_image_ids](PyMapper& mp) {
+                 sync_reg_image_ids(mp);
+                 return mp.reg_image_ids;
+             }, "The registered images in COLMAP's order: those the model held when the mapper was made, ascending, then every\n"
+                "registered image in registration order (DESIGN.md section 21).")
+        .def_property_readonly("filtered_images", [](const PyMapper& mp) { return std::vector<uint32_t>(mp.filtered_images.begin(), mp.filtered_images.end()); },
+             "The ids of the images filter_images removed from the model, ascending.")
         .def("__repr__", [](const PyMapper& mp) {
             const PyReconstruction& r = mp.triangulator.cast<PyTriangulator&>().reconstruction.cast<const PyReconstruction&>();
             return "IncrementalMapper(num_reg_images=" + std::to_string(r.images.size()) + ", num_candidates=" + std::to_string(mp.candidates.size()) +
                    ", num_total_reg_images=" + std::to_string(mp.num_total_reg_images) + ")";
         });
+
+    m.def("register_initial_image_pair", [register_initial_image_pair_with](PyMapper& mp, const MapperOptions& o, uint32_t image_id1, uint32_t image_id2) {
+              return register_initial_image_pair_with(mp, o, image_id1, image_id2, py::none(), py::none());
+          }, "mapper"_a, "options"_a, "image_id1"_a, "image_id2"_a,
+          "Start a model from two candidates of the mapper: estimate their calibrated two-view geometry and relative pose on\n"
+          "the GPU, put image 1 at the identity and image 2 at cam2_from_cam1, and triangulate every correspondence the graph\n"
+          "holds between them in one device call (DESIGN.md section 21).  False changes nothing but the two trial counts.");
+    m.def("_register_initial_image_pair_with", register_initial_image_pair_with, "mapper"_a, "options"_a, "image_id1"_a, "image_id2"_a,
+          "two_view_solver"_a, "pair_solver"_a, "register_initial_image_pair with callables in the library's place (test hook; DESIGN.md section 21).");
+    m.def("adjust_global_bundle", [adjust_global_bundle_with](PyMapper& mp, const MapperOptions& o, const BundleAdjustmentOptions& ba_options) {
+              return adjust_global_bundle_with(mp, o, ba_options, py::none());
+          }, "mapper"_a, "options"_a, "ba_options"_a,
+          "Adjust every registered image and the points they see on the GPU, the first image's pose and the second's x position\n"
+          "held, after deleting the observations with negative depth; then normalise the scene to an extent of 10\n"
+          "(DESIGN.md section 21).  False when the model gives no residual.");
+    m.def("_adjust_global_bundle_with", adjust_global_bundle_with, "mapper"_a, "options"_a, "ba_options"_a, "solver"_a,
+          "adjust_global_bundle with a callable in the library's place (test hook; DESIGN.md section 21).");
+    m.def("filter_images", filter_images, "mapper"_a, "options"_a,
+          "From 20 registered images on, remove every registered image that sees no point3D or whose camera has bogus\n"
+          "parameters: it leaves the reconstruction with its observations and becomes a candidate again (DESIGN.md section 21).\n"
+          "Returns the number of images removed.  Host code: it needs no GPU.");
+    m.def("_normalize_model", [checked_model, update_from_model](PyReconstruction& r, const std::vector<uint32_t>& reg_image_ids, double extent, double p0, double p1) {
+              SparseModel model = checked_model(r);
+              const NormalizeResult nr = NormalizeModel(&model, reg_image_ids, extent, p0, p1);
+              update_from_model(r, model);
+              return py::make_tuple(nr.applied, nr.scale, std::array<double, 3>{{nr.centroid[0], nr.centroid[1], nr.centroid[2]}});
+          }, "reconstruction"_a, "reg_image_ids"_a, "extent"_a = 10.0, "p0"_a = 0.1, "p1"_a = 0.9,
+          "adjust_global_bundle's normalisation on its own: (applied, scale, centroid) (test hook; DESIGN.md section 21).");
 
     // ---- estimate_triangulation (/root/reference/pycolmap/estimators/triangulation.h; tri_host.h) ----------------------
     py::class_<TriPointData>(m, "PointData")

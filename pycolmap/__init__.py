@@ -20,7 +20,11 @@ with `find_next_images`, `register_next_image` and `find_local_bundle`, `Increme
 `ImageSelectionMethod`.  A model starts from verified matches alone with
 `register_initial_image_pair(mapper, options, image_id1, image_id2)`, `adjust_global_bundle(mapper, options, ba_options)` and
 `filter_images(mapper, options)`: module-level functions that take the `IncrementalMapper` first (DESIGN.md section 21);
-`find_initial_image_pair`, `adjust_local_bundle` and the drivers stay undefined."""
+`find_initial_image_pair`, `adjust_local_bundle` and the drivers stay undefined.  The dense side reads the workspace of
+`undistort_images` again: `PatchMatchController(options, workspace_path).run()` with `PatchMatchOptions` writes COLMAP's
+photometric and geometric depth and normal maps, and `read_array` / `write_array` are this
+package's helpers for COLMAP's array files; the function `patch_match_stereo` stays undefined, and so does
+`stereo_fusion`."""
 import pycolmap_amd as _impl
 from pycolmap_amd import *  # noqa: F401,F403
 from pycolmap_amd import __version__  # noqa: F401
@@ -31,4 +35,4 @@ globals().update({n: getattr(_impl, n) for n in _PUBLIC})
 
 def __getattr__(name):
     raise AttributeError(f"pycolmap.{name} is outside pycolmap_amd's scope (SIFT feature extraction, exhaustive / sequential "
-                         f"matching + two-view verification, known-pose triangulation, absolute pose, image undistortion, bundle adjustment of a minimal Reconstruction behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}; also in scope: point filtering, and incremental triangulation of an image (CorrespondenceGraph, IncrementalTriangulator.triangulate_image), and the adjustment of a part of the model (BundleAdjustmentConfig, BundleAdjuster.solve), and track completion and merging (complete_tracks, complete_all_tracks, merge_tracks, merge_all_tracks with the triangulator as first argument), and retriangulation of under-reconstructed image pairs (retriangulate with the triangulator as first argument), and the mapper's image ranking, registration and local bundle (IncrementalMapper.find_next_images, register_next_image, find_local_bundle with IncrementalMapperOptions and ImageSelectionMethod), and the start of a model (register_initial_image_pair, adjust_global_bundle, filter_images with the mapper as first argument)")
+                         f"matching + two-view verification, known-pose triangulation, absolute pose, image undistortion, bundle adjustment of a minimal Reconstruction behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}; also in scope: point filtering, and incremental triangulation of an image (CorrespondenceGraph, IncrementalTriangulator.triangulate_image), and the adjustment of a part of the model (BundleAdjustmentConfig, BundleAdjuster.solve), and track completion and merging (complete_tracks, complete_all_tracks, merge_tracks, merge_all_tracks with the triangulator as first argument), and retriangulation of under-reconstructed image pairs (retriangulate with the triangulator as first argument), and the mapper's image ranking, registration and local bundle (IncrementalMapper.find_next_images, register_next_image, find_local_bundle with IncrementalMapperOptions and ImageSelectionMethod), and the start of a model (register_initial_image_pair, adjust_global_bundle, filter_images with the mapper as first argument), and PatchMatch stereo on a dense workspace (PatchMatchController(options, workspace_path).run() with PatchMatchOptions, and read_array, write_array for its files; patch_match_stereo and stereo_fusion stay undefined)")

@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = [
     "amc_image_visibility", "amc_visibility_result_free",
     "amc_pair_angle_opts_default", "amc_shared_point_angles", "amc_pair_angle_result_free",
     "amc_pair_tri_opts_default", "amc_triangulate_pairs", "amc_pair_tri_result_free",
+    "amc_patch_match_opts_default", "amc_patch_match", "amc_patch_match_result_free",
 ]
 COMM_ID_BYTES = 128
 RANSAC_F, RANSAC_H, RANSAC_E = 0, 1, 2
@@ -590,6 +591,133 @@ def pair_tri_inputs(camera_models, camera_params, image_cameras, qvec, tvec, pai
     return models, prm, icam, q, t, pi, poff, xy1, xy2
 
 
+class PatchMatchOpts(C.Structure):  # amc_patch_match_opts (include/amc_patchmatch.h)
+    _fields_ = [("window_radius", C.c_int32), ("window_step", C.c_int32), ("num_samples", C.c_int32),
+                ("num_iterations", C.c_int32), ("geom_consistency", C.c_int32), ("filter", C.c_int32),
+                ("filter_min_num_consistent", C.c_int32), ("want_costs", C.c_int32), ("seed", C.c_uint32),
+                ("reserved", C.c_uint32), ("sigma_spatial", C.c_double), ("sigma_color", C.c_double),
+                ("ncc_sigma", C.c_double), ("min_triangulation_angle", C.c_double), ("incident_angle_sigma", C.c_double),
+                ("geom_consistency_regularizer", C.c_double), ("geom_consistency_max_cost", C.c_double),
+                ("filter_min_ncc", C.c_double), ("filter_min_triangulation_angle", C.c_double),
+                ("filter_geom_consistency_max_cost", C.c_double)]
+
+
+class PatchMatchProblem(C.Structure):  # amc_patch_match_problem
+    _fields_ = [("num_images", C.c_size_t), ("pixels", C.c_void_p), ("pixel_offsets", C.c_void_p), ("widths", C.c_void_p),
+                ("heights", C.c_void_p), ("K", C.c_void_p), ("R", C.c_void_p), ("t", C.c_void_p),
+                ("num_problems", C.c_size_t), ("ref_images", C.c_void_p), ("src_offsets", C.c_void_p),
+                ("src_images", C.c_void_p), ("depth_ranges", C.c_void_p), ("in_depth", C.c_void_p),
+                ("in_normal", C.c_void_p), ("in_map_offsets", C.c_void_p)]
+
+
+class PatchMatchResult(C.Structure):  # amc_patch_match_result
+    _fields_ = [("num_problems", C.c_uint64), ("num_pixels", C.c_uint64), ("num_costs", C.c_uint64),
+                ("map_offsets", C.POINTER(C.c_uint64)), ("cost_offsets", C.POINTER(C.c_uint64)),
+                ("depth", C.POINTER(C.c_float)), ("normal", C.POINTER(C.c_float)),
+                ("num_consistent", C.POINTER(C.c_uint8)), ("costs", C.POINTER(C.c_float)),
+                ("num_batches", C.c_uint32), ("num_launches", C.c_uint32),
+                ("host_ms", C.c_double), ("device_ms", C.c_double), ("kernel_ms", C.c_double), ("copy_ms", C.c_double),
+                ("alloc_ms", C.c_double)]
+
+
+PATCHMATCH_MAX_SOURCES = 32
+PATCHMATCH_NO_MAP = 0xFFFFFFFFFFFFFFFF
+PATCHMATCH_DEFAULTS = dict(
+    window_radius=5, window_step=1, num_samples=15, num_iterations=5, geom_consistency=0, filter=0,
+    filter_min_num_consistent=2, want_costs=0, seed=0, sigma_spatial=-1.0, sigma_color=0.2, ncc_sigma=0.6,
+    min_triangulation_angle=1.0, incident_angle_sigma=0.9, geom_consistency_regularizer=0.3,
+    geom_consistency_max_cost=3.0, filter_min_ncc=0.1, filter_min_triangulation_angle=3.0,
+    filter_geom_consistency_max_cost=1.0)
+
+
+def patch_match_options(**kw) -> PatchMatchOpts:
+    """amc_patch_match_opts with the library's defaults (PATCHMATCH_DEFAULTS) and the given fields."""
+    unknown = set(kw) - set(PATCHMATCH_DEFAULTS)
+    if unknown:
+        raise ValueError(f"patch_match: unknown option {sorted(unknown)[0]!r}")
+    o = PatchMatchOpts()
+    for k, v in {**PATCHMATCH_DEFAULTS, **kw}.items():
+        setattr(o, k, type(PATCHMATCH_DEFAULTS[k])(v))
+    return o
+
+
+def patch_match_inputs(images, K, R, t, ref_images, src_offsets, src_images, depth_ranges, in_depth=None, in_normal=None):
+    """The flat problem of amc_patch_match as contiguous arrays (copies: the caller's arrays are not touched).  images: a
+    list of H x W uint8 arrays; K (I, 4) fx fy cx cy; R (I, 3, 3) and t (I, 3) cam_from_world; ref_images (P,);
+    src_offsets (P + 1,) CSR over src_images; depth_ranges (P, 2).  in_depth / in_normal: per image an H x W and a
+    3 x H x W float32 array or None, or None for no maps at all.  Returns (problem, keep): the PatchMatchProblem and the
+    arrays it points into."""
+    who = "patch_match"
+    imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+    for i, a in enumerate(imgs):
+        if a.ndim != 2 or a.size == 0:
+            raise ValueError(f"{who}: image {i} is not a non-empty H x W grey image")
+    n = len(imgs)
+    sizes = np.array([a.size for a in imgs], dtype=np.uint64)
+    poff = np.zeros(n + 1, np.uint64)
+    poff[1:] = np.cumsum(sizes)
+    pixels = np.concatenate([a.reshape(-1) for a in imgs]) if n else np.zeros(1, np.uint8)
+    w = np.array([a.shape[1] for a in imgs], dtype=np.int32)
+    h = np.array([a.shape[0] for a in imgs], dtype=np.int32)
+    Kf = np.array(K, dtype=np.float64).reshape(-1, 4)
+    Rf = np.array(R, dtype=np.float64).reshape(-1, 9)
+    tf = np.array(t, dtype=np.float64).reshape(-1, 3)
+    if not (Kf.shape[0] == Rf.shape[0] == tf.shape[0] == n):
+        raise ValueError(f"{who}: {n} images, {Kf.shape[0]} K, {Rf.shape[0]} R, {tf.shape[0]} t")
+    ref = _u32_index(who, "ref_images", ref_images)
+    soff = _offsets(who, "src_offsets", src_offsets)
+    src = _u32_index(who, "src_images", src_images)
+    rng = np.array(depth_ranges, dtype=np.float64).reshape(-1, 2)
+    if soff.size != ref.size + 1 or int(soff[-1]) != src.size or rng.shape[0] != ref.size:
+        raise ValueError(f"{who}: {ref.size} problems, {soff.size} offsets ending at {int(soff[-1])}, {src.size} sources, "
+                         f"{rng.shape[0]} depth ranges")
+    keep = [pixels, poff, w, h, Kf, Rf, tf, ref, soff, src, rng]
+    ptr = lambda v: v.ctypes.data_as(C.c_void_p)  # noqa: E731
+    pd = pn = pm = None
+    if (in_depth is None) != (in_normal is None):
+        raise ValueError(f"{who}: in_depth and in_normal are given together")
+    if in_depth is not None:
+        if len(in_depth) != n or len(in_normal) != n:
+            raise ValueError(f"{who}: {n} images, {len(in_depth)} depth maps, {len(in_normal)} normal maps")
+        moff = np.full(n, PATCHMATCH_NO_MAP, np.uint64)
+        ds, ns, at = [], [], 0
+        for i in range(n):
+            if in_depth[i] is None:
+                continue
+            dm = np.ascontiguousarray(in_depth[i], dtype=np.float32)
+            nm = np.ascontiguousarray(in_normal[i], dtype=np.float32)
+            if dm.shape != imgs[i].shape or nm.shape != (3,) + imgs[i].shape:
+                raise ValueError(f"{who}: image {i} is {imgs[i].shape}, its depth map {dm.shape}, its normal map {nm.shape}")
+            moff[i] = at
+            ds.append(dm.reshape(-1))
+            # the call addresses the normal maps at three times the depth maps' offsets
+            ns.append(nm.reshape(-1))
+            at += dm.size
+        dflat = np.concatenate(ds) if ds else np.zeros(1, np.float32)
+        nflat = np.concatenate(ns) if ns else np.zeros(3, np.float32)
+        keep += [dflat, nflat, moff]
+        pd, pn, pm = ptr(dflat), ptr(nflat), ptr(moff)
+    pb = PatchMatchProblem(n, ptr(pixels), ptr(poff), ptr(w), ptr(h), ptr(Kf), ptr(Rf), ptr(tf), ref.size, ptr(ref), ptr(soff),
+                           ptr(src), ptr(rng), pd, pn, pm)
+    return pb, keep
+
+
+def patch_match_unpack(keep, num_problems, map_offsets, cost_offsets, depth, normal, num_consistent, costs):
+    """The per-problem arrays of a patch match result (copies) from its flat ones; `keep` as patch_match_inputs returns it."""
+    w, h, ref, soff = keep[2], keep[3], keep[7], keep[8]
+    out = {"depth": [], "normal": [], "num_consistent": [], "costs": [] if costs is not None else None}
+    for p in range(int(num_problems)):
+        H, W, S = int(h[ref[p]]), int(w[ref[p]]), int(soff[p + 1] - soff[p])
+        m, c = int(map_offsets[p]), int(cost_offsets[p])
+        arr = lambda ptr, at, k: np.ctypeslib.as_array(ptr, (at + k,))[at:].copy()  # noqa: E731
+        out["depth"].append(arr(depth, m, H * W).reshape(H, W))
+        out["normal"].append(arr(normal, 3 * m, 3 * H * W).reshape(3, H, W))
+        out["num_consistent"].append(arr(num_consistent, m, H * W).reshape(H, W))
+        if costs is not None:
+            out["costs"].append(arr(costs, c, S * H * W).reshape(S, H, W))
+    return out
+
+
 RETRI_NONE, RETRI_CONTINUE_1TO2, RETRI_CONTINUE_2TO1, RETRI_CREATED = 0, 1, 2, 3
 RETRI_MAX_CORRS = 1 << 24
 
@@ -1090,6 +1218,13 @@ def load() -> C.CDLL:
         lib.amc_shared_point_angles.restype = C.c_int
         lib.amc_pair_angle_result_free.argtypes = [C.POINTER(PairAngleResult)]
         lib.amc_pair_angle_result_free.restype = None
+    if hasattr(lib, "amc_patch_match"):  # (absent from a library built from an older revision)
+        lib.amc_patch_match_opts_default.argtypes = [C.POINTER(PatchMatchOpts)]
+        lib.amc_patch_match_opts_default.restype = None
+        lib.amc_patch_match.argtypes = [C.c_void_p, C.POINTER(PatchMatchOpts), C.POINTER(PatchMatchProblem), C.POINTER(PatchMatchResult)]
+        lib.amc_patch_match.restype = C.c_int
+        lib.amc_patch_match_result_free.argtypes = [C.POINTER(PatchMatchResult)]
+        lib.amc_patch_match_result_free.restype = None
     if hasattr(lib, "amc_triangulate_pairs"):  # (absent from a library built from an older revision)
         lib.amc_pair_tri_opts_default.argtypes = [C.POINTER(PairTriOpts)]
         lib.amc_pair_tri_opts_default.restype = None
@@ -1770,6 +1905,27 @@ class Context:
                    "kernel_ms": res.kernel_ms, "copy_ms": res.copy_ms, "alloc_ms": res.alloc_ms}
         finally:
             self._lib.amc_pair_tri_result_free(C.byref(res))
+        return out
+
+    def patch_match(self, images, K, R, t, ref_images, src_offsets, src_images, depth_ranges, in_depth=None, in_normal=None,
+                    **options):
+        """amc_patch_match: one pass of PatchMatch stereo over a list of problems.  The arrays as
+        in patch_match_inputs; the options are the fields of amc_patch_match_opts (PATCHMATCH_DEFAULTS).  The inputs are
+        not modified.  Returns a dict: depth, normal, num_consistent and (with want_costs) costs, each a list with one
+        array per problem (H x W float32, 3 x H x W float32, H x W uint8, S x H x W float32), num_batches, num_launches,
+        host_ms, device_ms, kernel_ms, copy_ms, alloc_ms."""
+        o = patch_match_options(**options)
+        pb, keep = patch_match_inputs(images, K, R, t, ref_images, src_offsets, src_images, depth_ranges, in_depth, in_normal)
+        res = PatchMatchResult()
+        _check(self._lib.amc_patch_match(self._h, C.byref(o), C.byref(pb), C.byref(res)))
+        try:
+            out = patch_match_unpack(keep, res.num_problems, res.map_offsets, res.cost_offsets, res.depth, res.normal,
+                                     res.num_consistent, res.costs if o.want_costs else None)
+            out.update({"num_batches": int(res.num_batches), "num_launches": int(res.num_launches), "host_ms": res.host_ms,
+                        "device_ms": res.device_ms, "kernel_ms": res.kernel_ms, "copy_ms": res.copy_ms,
+                        "alloc_ms": res.alloc_ms})
+        finally:
+            self._lib.amc_patch_match_result_free(C.byref(res))
         return out
 
     def estimate_rig_absolute_poses(self, offsets, camera_offsets, camera_models, camera_params, cams_from_rig,

@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "amc_pair_angle_opts_default", "amc_shared_point_angles", "amc_pair_angle_result_free",
     "amc_pair_tri_opts_default", "amc_triangulate_pairs", "amc_pair_tri_result_free",
     "amc_patch_match_opts_default", "amc_patch_match", "amc_patch_match_result_free",
+    "amc_fusion_opts_default", "amc_fuse_depth_maps", "amc_fusion_result_free",
 ]
 COMM_ID_BYTES = 128
 RANSAC_F, RANSAC_H, RANSAC_E = 0, 1, 2
@@ -718,6 +719,124 @@ def patch_match_unpack(keep, num_problems, map_offsets, cost_offsets, depth, nor
     return out
 
 
+class FusionOpts(C.Structure):  # amc_fusion_opts (include/amc_fusion.h)
+    _fields_ = [("min_num_pixels", C.c_int32), ("max_num_pixels", C.c_int32), ("max_traversal_depth", C.c_int32),
+                ("reserved", C.c_int32), ("max_reproj_error", C.c_double), ("max_depth_error", C.c_double),
+                ("max_normal_error", C.c_double), ("bounding_box", C.c_double * 6)]
+
+
+class FusionProblem(C.Structure):  # amc_fusion_problem
+    _fields_ = [("num_images", C.c_size_t), ("rgb", C.c_void_p), ("rgb_offsets", C.c_void_p), ("widths", C.c_void_p),
+                ("heights", C.c_void_p), ("K", C.c_void_p), ("R", C.c_void_p), ("t", C.c_void_p), ("depth", C.c_void_p),
+                ("normal", C.c_void_p), ("map_offsets", C.c_void_p), ("nb_offsets", C.c_void_p), ("nb_images", C.c_void_p)]
+
+
+class FusionResult(C.Structure):  # amc_fusion_result
+    _fields_ = [("num_points", C.c_uint64), ("xyz", C.POINTER(C.c_float)), ("normal", C.POINTER(C.c_float)),
+                ("color", C.POINTER(C.c_uint8)), ("seed_image", C.POINTER(C.c_uint32)), ("seed_pixel", C.POINTER(C.c_uint32)),
+                ("num_fused", C.POINTER(C.c_uint32)), ("vis_offsets", C.POINTER(C.c_uint64)),
+                ("vis_images", C.POINTER(C.c_uint32)), ("num_seeds", C.c_uint64), ("num_truncated", C.c_uint64),
+                ("num_batches", C.c_uint32), ("num_launches", C.c_uint32),
+                ("host_ms", C.c_double), ("device_ms", C.c_double), ("kernel_ms", C.c_double), ("copy_ms", C.c_double),
+                ("alloc_ms", C.c_double)]
+
+
+FUSION_MAX_NEIGHBOURS = 64
+FUSION_MAX_TRAVERSAL_DEPTH = 128
+FUSION_MAX_CLUSTER = 256
+FUSION_NO_MAP = 0xFFFFFFFFFFFFFFFF
+FLOAT32_MAX = 3.4028234663852886e38
+FUSION_DEFAULTS = dict(
+    min_num_pixels=5, max_num_pixels=10000, max_traversal_depth=100, max_reproj_error=2.0, max_depth_error=0.01,
+    max_normal_error=10.0, bounding_box=((-FLOAT32_MAX,) * 3, (FLOAT32_MAX,) * 3))
+
+
+def fusion_options(**kw) -> FusionOpts:
+    """amc_fusion_opts with the library's defaults (FUSION_DEFAULTS) and the given fields; bounding_box is a pair of
+    3-vectors (min, max)."""
+    unknown = set(kw) - set(FUSION_DEFAULTS)
+    if unknown:
+        raise ValueError(f"fuse_depth_maps: unknown option {sorted(unknown)[0]!r}")
+    o = FusionOpts()
+    for k, v in {**FUSION_DEFAULTS, **kw}.items():
+        if k == "bounding_box":
+            box = np.array(v, dtype=np.float64).reshape(-1)
+            if box.size != 6:
+                raise ValueError("fuse_depth_maps: bounding_box is not a pair of 3-vectors")
+            o.bounding_box = (C.c_double * 6)(*box)
+        else:
+            setattr(o, k, type(FUSION_DEFAULTS[k])(v))
+    return o
+
+
+def fusion_inputs(images, K, R, t, depth_maps, normal_maps, neighbours):
+    """The flat problem of amc_fuse_depth_maps as contiguous arrays (copies: the caller's arrays are not touched).
+    images: a list of H x W x 3 uint8 arrays in fusion order; K (I, 4) fx fy cx cy; R (I, 3, 3) and t (I, 3)
+    cam_from_world; depth_maps / normal_maps: per image an H x W and a 3 x H x W float32 array, or None for an image
+    without maps; neighbours: per image the ordered list of image indices.  Returns (problem, keep)."""
+    who = "fuse_depth_maps"
+    imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+    for i, a in enumerate(imgs):
+        if a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+            raise ValueError(f"{who}: image {i} is not a non-empty H x W x 3 image")
+    n = len(imgs)
+    roff = np.zeros(n + 1, np.uint64)
+    roff[1:] = np.cumsum([a.size for a in imgs], dtype=np.uint64)
+    rgb = np.concatenate([a.reshape(-1) for a in imgs]) if n else np.zeros(1, np.uint8)
+    w = np.array([a.shape[1] for a in imgs], dtype=np.int32)
+    h = np.array([a.shape[0] for a in imgs], dtype=np.int32)
+    Kf = np.array(K, dtype=np.float64).reshape(-1, 4)
+    Rf = np.array(R, dtype=np.float64).reshape(-1, 9)
+    tf = np.array(t, dtype=np.float64).reshape(-1, 3)
+    if not (Kf.shape[0] == Rf.shape[0] == tf.shape[0] == n):
+        raise ValueError(f"{who}: {n} images, {Kf.shape[0]} K, {Rf.shape[0]} R, {tf.shape[0]} t")
+    if len(depth_maps) != n or len(normal_maps) != n or len(neighbours) != n:
+        raise ValueError(f"{who}: {n} images, {len(depth_maps)} depth maps, {len(normal_maps)} normal maps, "
+                         f"{len(neighbours)} neighbour lists")
+    moff = np.full(max(n, 1), FUSION_NO_MAP, np.uint64)
+    ds, ns, at = [], [], 0
+    for i in range(n):
+        if (depth_maps[i] is None) != (normal_maps[i] is None):
+            raise ValueError(f"{who}: image {i} has one map of the two")
+        if depth_maps[i] is None:
+            continue
+        dm = np.ascontiguousarray(depth_maps[i], dtype=np.float32)
+        nm = np.ascontiguousarray(normal_maps[i], dtype=np.float32)
+        if dm.shape != imgs[i].shape[:2] or nm.shape != (3,) + imgs[i].shape[:2]:
+            raise ValueError(f"{who}: image {i} is {imgs[i].shape[:2]}, its depth map {dm.shape}, its normal map {nm.shape}")
+        moff[i] = at
+        ds.append(dm.reshape(-1))
+        ns.append(nm.reshape(-1))  # the call addresses the normal maps at three times the depth maps' offsets
+        at += dm.size
+    dflat = np.concatenate(ds) if ds else np.zeros(1, np.float32)
+    nflat = np.concatenate(ns) if ns else np.zeros(3, np.float32)
+    noff = np.zeros(n + 1, np.uint64)
+    lists = []
+    for i, lst in enumerate(neighbours):
+        lst = _u32_index(who, f"neighbours[{i}]", lst)
+        if lst.size > FUSION_MAX_NEIGHBOURS:
+            raise ValueError(f"{who}: image {i} has {lst.size} neighbours, more than {FUSION_MAX_NEIGHBOURS} "
+                             "(AMC_FUSION_MAX_NEIGHBOURS)")
+        lists.append(lst)
+        noff[i + 1] = noff[i] + np.uint64(lst.size)
+    nb = np.concatenate(lists + [np.zeros(1, np.uint32)]).astype(np.uint32)
+    keep = [rgb, roff, w, h, Kf, Rf, tf, dflat, nflat, moff, noff, nb]
+    ptr = lambda v: v.ctypes.data_as(C.c_void_p)  # noqa: E731
+    pb = FusionProblem(n, ptr(rgb), ptr(roff), ptr(w), ptr(h), ptr(Kf), ptr(Rf), ptr(tf), ptr(dflat), ptr(nflat), ptr(moff),
+                       ptr(noff), ptr(nb))
+    return pb, keep
+
+
+def fusion_unpack(num_points, xyz, normal, color, seed_image, seed_pixel, num_fused, vis_offsets, vis_images):
+    """The arrays of a fusion result (copies) from its flat ones"""
+    n = int(num_points)
+    arr = lambda p, k: np.ctypeslib.as_array(p, (max(k, 1),))[:k].copy()  # noqa: E731
+    voff = arr(vis_offsets, n + 1)
+    return {"num_points": n, "xyz": arr(xyz, 3 * n).reshape(n, 3), "normal": arr(normal, 3 * n).reshape(n, 3),
+            "color": arr(color, 3 * n).reshape(n, 3), "seed_image": arr(seed_image, n), "seed_pixel": arr(seed_pixel, n),
+            "num_fused": arr(num_fused, n), "vis_offsets": voff, "vis_images": arr(vis_images, int(voff[-1]))}
+
+
 RETRI_NONE, RETRI_CONTINUE_1TO2, RETRI_CONTINUE_2TO1, RETRI_CREATED = 0, 1, 2, 3
 RETRI_MAX_CORRS = 1 << 24
 
@@ -1225,6 +1344,13 @@ def load() -> C.CDLL:
         lib.amc_patch_match.restype = C.c_int
         lib.amc_patch_match_result_free.argtypes = [C.POINTER(PatchMatchResult)]
         lib.amc_patch_match_result_free.restype = None
+    if hasattr(lib, "amc_fuse_depth_maps"):  # (absent from a library built from an older revision)
+        lib.amc_fusion_opts_default.argtypes = [C.POINTER(FusionOpts)]
+        lib.amc_fusion_opts_default.restype = None
+        lib.amc_fuse_depth_maps.argtypes = [C.c_void_p, C.POINTER(FusionOpts), C.POINTER(FusionProblem), C.POINTER(FusionResult)]
+        lib.amc_fuse_depth_maps.restype = C.c_int
+        lib.amc_fusion_result_free.argtypes = [C.POINTER(FusionResult)]
+        lib.amc_fusion_result_free.restype = None
     if hasattr(lib, "amc_triangulate_pairs"):  # (absent from a library built from an older revision)
         lib.amc_pair_tri_opts_default.argtypes = [C.POINTER(PairTriOpts)]
         lib.amc_pair_tri_opts_default.restype = None
@@ -1926,6 +2052,27 @@ class Context:
                         "alloc_ms": res.alloc_ms})
         finally:
             self._lib.amc_patch_match_result_free(C.byref(res))
+        return out
+
+    def fuse_depth_maps(self, images, K, R, t, depth_maps, normal_maps, neighbours, **options):
+        """amc_fuse_depth_maps: the maps of an ordered list of images fused into points.  The
+        arrays as in fusion_inputs; the options are the fields of amc_fusion_opts (FUSION_DEFAULTS).  The inputs are not
+        modified.  Returns a dict: num_points, xyz (P, 3) float32, normal (P, 3) float32, color (P, 3) uint8, seed_image,
+        seed_pixel, num_fused (P,) uint32, vis_offsets (P + 1,) uint64, vis_images uint32, num_seeds, num_truncated,
+        num_batches, num_launches, host_ms, device_ms, kernel_ms, copy_ms, alloc_ms."""
+        o = fusion_options(**options)
+        pb, keep = fusion_inputs(images, K, R, t, depth_maps, normal_maps, neighbours)
+        res = FusionResult()
+        _check(self._lib.amc_fuse_depth_maps(self._h, C.byref(o), C.byref(pb), C.byref(res)))
+        try:
+            out = fusion_unpack(res.num_points, res.xyz, res.normal, res.color, res.seed_image, res.seed_pixel,
+                                res.num_fused, res.vis_offsets, res.vis_images)
+            out.update({"num_seeds": int(res.num_seeds), "num_truncated": int(res.num_truncated),
+                        "num_batches": int(res.num_batches), "num_launches": int(res.num_launches), "host_ms": res.host_ms,
+                        "device_ms": res.device_ms, "kernel_ms": res.kernel_ms, "copy_ms": res.copy_ms,
+                        "alloc_ms": res.alloc_ms})
+        finally:
+            self._lib.amc_fusion_result_free(C.byref(res))
         return out
 
     def estimate_rig_absolute_poses(self, offsets, camera_offsets, camera_models, camera_params, cams_from_rig,

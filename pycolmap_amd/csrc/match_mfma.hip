@@ -61,9 +61,9 @@
 // item's chunks and X rows, decode, and meet at two barriers: 6.7 % of an item's clocks, profiles/boundary/), and
 // the partner workgroup's wave then has the SIMD to itself instead of the matrix pipe of the whole CU standing idle.
 // A chunk crossing's barrier joins four waves on four SIMDs.  Both workgroups must fit: at most 256 registers per lane
-// (amdgpu_waves_per_eu pins it; MODE 0 compiles to 254 VGPRs, MODE 1 to 236, without scratch: anything added to
-// the loop's live state will spill - check -Rpass-analysis=kernel-resource-usage after every change,
-// profiles/items4/kernel_resource_usage.txt) and at most 80 KB of LDS (66 KB); launch_match_mfma asks the runtime.
+// (amdgpu_waves_per_eu pins it; MODE 0 compiles to 222 VGPRs, MODE 1 to 192, without scratch - check
+// -Rpass-analysis=kernel-resource-usage after every change, profiles/scanloop/kernel_resource_usage.txt) and at most
+// 80 KB of LDS (66 KB, ONE __shared__ object); launch_match_mfma asks the runtime.
 // Taking the ticket two items ahead and warming the next item's X rows in L2 were both built and measured, and
 // neither paid (profiles/boundary/README.md).
 // Y streams through LDS in 128-row chunks (one block) by direct-to-LDS DMA, a ring of four buffers, a wave's four
@@ -71,6 +71,17 @@
 // arena is pre-swizzled (arena_swizzle, amc_internal.h) so the linear DMA image is bank-conflict-free for
 // ds_read_b128.  Each wave software-pipelines: the 4 MFMAs of (step, X tile) u+1 are interleaved with the
 // VALU of u, two accumulator sets.
+// The chunk loop.  Per chunk a wave issues 128 MFMAs and the 152 vector instructions of the top-2 work, and the vector
+// pipe is what bounds it - so nothing else in the loop is a vector instruction, but for three adds per chunk
+// (tools/scan_loop_census.py counts the assembly, tests/test_match_scan_loop_census_cpu.py holds it there):
+//   * LDS reads: three lane bases carry the lane's part and the ring position and move to the next buffer in place,
+//     once per chunk; step and tile are compile-time, so every ds_read_b128 is base + immediate;
+//   * DMA: the global address is a scalar base advanced on the scalar unit plus the one lane offset lane * 16 (the
+//     instruction's saddr form), the LDS address is m0;
+//   * conditions: the loop is peeled by what is in flight - a STEADY loop for the chunks c with c + 3 < nchunks
+//     (a fetch in every step, one fixed wait at the crossing), a DRAIN loop for the last up to three (no fetch, the
+//     waits that fit) - and by whether the wave has rows: a wave without rows runs loops of its own that only issue
+//     its DMA pieces, wait and meet the barriers.  Every wave of a workgroup executes the same number of s_barrier.
 #include <cstdlib>
 
 #include "amc_internal.h"
@@ -99,14 +110,14 @@ constexpr int kKeyShift = 7, kKeyCarried = 127;
 // is the prefetch distance in rows that two chunks of 256 were.
 constexpr int kNB = 4;
 constexpr int kOffRs = 0;                        // kNB x rs128 chunks (kBN ints each)
-constexpr int kOffQ = kOffRs + kNB * kBN * 4;    // queue slot
+constexpr int kOffQ = kOffRs + kNB * kBN * 4;    // queue slot, copy-part slot
 constexpr int kOffB = kOffQ + 16;                // kNB x descriptor chunks
 constexpr int kLdsBytes = kOffB + kNB * kChunkBytes;
 static_assert(kRowPad % kBN == 0, "a chunk divides the row padding: every chunk that holds a row lies inside the padded image");
 static_assert(kUR == 128 && kSPB == 4 && kBN == kUR, "a lane quarter's rows of a block are one 32-row tile; the loop body is one block, which is one chunk");
 static_assert(kRowPad % kSegRows == 0 && kSegRows % 32 == 0, "segments tile the padded rows");
 static_assert((kNB & (kNB - 1)) == 0, "the ring position is taken modulo kNB with a mask");
-static_assert(kWGPerCU * (kLdsBytes + 16) <= 160 * 1024, "LDS of one CU holds two workgroups (and their copy-part slots)");
+static_assert(kWGPerCU * kLdsBytes <= 160 * 1024, "LDS of one CU holds two workgroups");
 static_assert(kW == 4, "one wave of a workgroup per SIMD");
 static_assert(sizeof(SegDesc) == 64, "a descriptor is 16 dwords: one per lane of a quarter wave");
 
@@ -190,10 +201,12 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
     volatile uint32_t* s_q = reinterpret_cast<volatile uint32_t*>(smem + kOffQ);
     if constexpr (MODE == 0) {
         if (job.parts) {  // (wave-uniform: a kernel argument)
-            __shared__ uint32_t s_part;
-            if (tid == 0) s_part = atomicAdd(copy_head, 1u);
+            // (the slot lives in smem: with a second LDS object in the kernel the compiler orders every LDS read of
+            // the scan behind the pending DMA with an s_waitcnt vmcnt(0), one per step)
+            volatile uint32_t* s_part = reinterpret_cast<volatile uint32_t*>(smem + kOffQ + 4);
+            if (tid == 0) *s_part = atomicAdd(copy_head, 1u);
             __syncthreads();
-            const uint32_t part = s_part;
+            const uint32_t part = *s_part;
             if (part < job.parts)
                 copy_part(static_cast<const uint4*>(job.src), static_cast<uint4*>(job.dst), job.n16 * part / job.parts,
                           job.n16 * (part + 1) / job.parts, tid, 64 * kW);
@@ -215,18 +228,30 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
         return reinterpret_cast<const char*>(lo | (hi << 32));
     };
 
-    // chunk c of the Y image (prep / rs128 base pointers) -> LDS buffer `buf`, in 1 KiB pieces dealt to the waves
-    // (dest = wave-uniform base + lane*16); a wave owns kPW pieces of a chunk, wave 0 also its rs128 block
+    // chunk c of the Y image (prep / rs128 base pointers) -> LDS buffer `buf`, in 1 KiB pieces dealt to the waves; a
+    // wave owns kPW pieces of a chunk, wave 0 also its rs128 block.  A DMA instruction's global address is a scalar
+    // base, wave-uniform and computed on the scalar unit, plus ONE 32-bit lane offset that never changes, lane * 16
+    // (the instruction's `saddr` form: written as base + zero-extended offset the compiler selects it); its LDS
+    // address is m0 + lane * 16.  No vector instruction forms an address.
     constexpr int kPW = kChunkBytes / 1024 / kW;
+    uint32_t lane16 = (uint32_t)lane * 16u;
+    // (an empty asm in front of every use: the offset stays ONE 32-bit register, extended where it is used; hoisted, the
+    // extension makes it a 64-bit lane address and every DMA instruction a 64-bit vector add)
+    auto lane_off = [&]() __attribute__((always_inline)) -> uint32_t {
+        asm volatile("" : "+v"(lane16));
+        return lane16;
+    };
     auto stage_piece = [&](const char* yprep, int c, int buf, int ps) __attribute__((always_inline)) {
         const int piece = ps * kW + wid;
-        __builtin_amdgcn_global_load_lds((gvoid_t*)(yprep + (size_t)c * kChunkBytes + piece * 1024 + lane * 16),
+        const char* src = yprep + ((size_t)c * kChunkBytes + piece * 1024);
+        __builtin_amdgcn_global_load_lds((gvoid_t*)(src + lane_off()),
                                          (lvoid_t*)(smem + kOffB + buf * kChunkBytes + piece * 1024), 16, 0, 0);
     };
     auto stage_rs = [&](const char* yrs, int c, int buf) __attribute__((always_inline)) {
+        const char* src = yrs + (size_t)c * kBN * 4;
         if (wid == 0 && lane < kBN / 4)  // rs128 of this chunk's rows: 512 B, the lower half of the wave
-            __builtin_amdgcn_global_load_lds((gvoid_t*)(yrs + (size_t)c * kBN * 4 + lane * 16),
-                                             (lvoid_t*)(smem + kOffRs + buf * kBN * 4), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gvoid_t*)(src + lane_off()), (lvoid_t*)(smem + kOffRs + buf * kBN * 4), 16, 0,
+                                             0);
     };
     auto stage = [&](const char* yprep, const char* yrs, int c, int buf) __attribute__((always_inline)) {
 #pragma unroll
@@ -244,32 +269,38 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
             if (yrows > c * kBN) stage(yprep, yrs, c, c);
     };
 
-    // A-operand fragments + C blocks of step `ys` of the chunk in LDS buffer `buf`, as six 16-byte reads: parts 0, 1 =
-    // the C blocks (needed first), 2..5 = the two tiles' two k halves.  The scan spreads them over the phases of the
+    // A-operand fragments + C blocks of step `ys` of the chunk the lane bases point at, as six 16-byte reads: parts 0,
+    // 1 = the C blocks (needed first), 2..5 = the two tiles' two k halves.  The scan spreads them over the phases of the
     // previous step, one behind each phase's last MFMA, so they never pile up in one MFMA shadow.
     // This lane's A row m = l15 of tile t of block b is row b*128 + 32 (m >> 2) + 4 t + (m & 3) of the chunk; its
     // swizzle does not depend on b and t (arena_swizzle takes row bits 1, 5 and 6).
     const int yrow_lane = (kUR / 4) * (l15 >> 2) + (l15 & 3);
     const int ysw_lane = arena_swizzle(yrow_lane);
-    // per-lane byte offsets of the two k halves' slots and of the C block; what a step adds is wave-uniform
-    const int yoff0 = kOffB + yrow_lane * kDim + ((lq ^ ysw_lane) * 16);
-    const int yoff1 = kOffB + yrow_lane * kDim + (((4 + lq) ^ ysw_lane) * 16);
-    const int coff = kOffRs + (kUR / 4) * lq * 4;
-    auto load_y_part = [&](YFrag& y, int buf, int ys, int part) __attribute__((always_inline)) {
-        const int ub = (ys / kSPB) * kUR, sp = ys % kSPB;
+    // Three lane bases: the byte offsets of the two k halves' slots and of the C block in the ring buffer being read.
+    // They carry the lane's part AND the ring position (once per chunk the scan adds a wave-uniform buffer stride to
+    // them in place, `advance`); the step and the tile are compile-time, so every ds_read_b128 is base + immediate.
+    int yb0 = kOffB + yrow_lane * kDim + ((lq ^ ysw_lane) * 16);
+    int yb1 = kOffB + yrow_lane * kDim + (((4 + lq) ^ ysw_lane) * 16);
+    int cbs = kOffRs + (kUR / 4) * lq * 4;
+    auto load_y_part = [&](YFrag& y, int ys, int part) __attribute__((always_inline)) {
         if (part < 2) {
-            // accumulator register r of tile t <-> Y row 32 lq + 4 t + r of the block
-            const int so = buf * kBN * 4 + (ub + 8 * sp) * 4;
-            y.ci[part] = *reinterpret_cast<const i32x4*>(smem + (coff + so) + 16 * part);  // the -2^21 lives in xterm
+            // accumulator register r of tile t <-> Y row 32 lq + 4 t + r of the block (the -2^21 lives in xterm)
+            y.ci[part] = *reinterpret_cast<const i32x4*>(smem + cbs + (8 * ys * 4 + 16 * part));
         } else {
-            const int tt = (part - 2) >> 1, s = (part - 2) & 1;
-            const int so = buf * kChunkBytes + (ub + 8 * sp) * kDim;  // tile 2 sp of the block
-            y.f[tt][s] = *reinterpret_cast<const i32x4*>(smem + ((s ? yoff1 : yoff0) + so) + tt * 4 * kDim);
+            const int tt = (part - 2) >> 1, s = (part - 2) & 1;  // tile 2 ys + tt
+            y.f[tt][s] = *reinterpret_cast<const i32x4*>(smem + (s ? yb1 : yb0) + (8 * ys + tt * 4) * kDim);
         }
     };
-    auto load_y = [&](YFrag& y, int buf, int ys) __attribute__((always_inline)) {
+    auto load_y = [&](YFrag& y, int ys) __attribute__((always_inline)) {
 #pragma unroll
-        for (int part = 0; part < 6; ++part) load_y_part(y, buf, ys, part);
+        for (int part = 0; part < 6; ++part) load_y_part(y, ys, part);
+    };
+    // the bases move from ring buffer cb to the next one (three VALU instructions per chunk; asm, so that the compiler
+    // keeps them in place instead of holding one set of bases per buffer)
+    auto advance = [&](int cb) __attribute__((always_inline)) {
+        const int k = cb == kNB - 1 ? -(kNB - 1) : 1;
+        asm volatile("v_add_u32 %0, %3, %0\n\tv_add_u32 %1, %3, %1\n\tv_add_u32 %2, %4, %2"
+                     : "+v"(yb0), "+v"(yb1), "+v"(cbs) : "s"(k * kChunkBytes), "s"(k * kBN * 4));
     };
 
     // resident X state: B-operand fragments, one (best, second, block) per lane and X tile; part = the running
@@ -434,8 +465,52 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
             st_first = now;
         }
 #endif
+        // The sched_barriers pin the interleaving.  An accumulator is read (by inline asm, which
+        // hipcc does not hazard-check) only after FOUR further MFMAs have issued behind the one
+        // that completed it - the matrix pipe runs MFMAs in order, 16 clk each (4 passes), so two of them
+        // have run to their end since: well over the 7 wait states a 4-pass MFMA's result needs before a VALU read
+        // (two further MFMAs would do; the rule the 8-pass instruction needed, 11 states, held with two as well).
+        //
+        // The chunk loop is peeled by what is in flight.  STEADY chunks, c + 3 < nchunks: every step issues this wave's
+        // piece of chunk c + 3 into the buffer chunk c - 1 left (never bunched), and the crossing to chunk c + 1 waits
+        // with the one count that fits.  DRAIN, the last up to three chunks: nothing is fetched, the crossing's count
+        // depends on how many chunks remain, and the last chunk has no crossing.  The ring position cb = c % kNB is a
+        // scalar; where the DMA goes and by how much the read bases move are computed from it on the scalar unit.
+        static_assert(kPW == kYS, "one DMA piece per wave and step");
+        static_assert(kNB == 4, "the counted waits below are written out for three chunks ahead");
+        // Chunk c + 1 must have landed.  Loads return in the order they were issued, and behind this wave's pieces of
+        // chunk c + 1 it has issued its kPW pieces (wave 0: + 1 rs128 block) of every later chunk that exists, c + 2
+        // and c + 3: so many may stay in flight and no more.  (At the first crossing chunks 1 and 2 have landed with
+        // the item's X rows; fewer pieces are in flight than the count allows.)  rem: chunks behind chunk c, >= 1.
+        auto crossing = [&](bool steady, int rem) __attribute__((always_inline)) {
+#ifdef AMC_SCAN_STAMPS
+            const uint32_t st_t = AMC_STAMP();
+#endif
+            if (steady) {
+                if (wid == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * kPW + 2) : "memory");
+                else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * kPW) : "memory");
+            } else if (rem >= 2) {
+                if (wid == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPW + 1) : "memory");
+                else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPW) : "memory");
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // nothing further to fetch
+            }
+            // a bare barrier: __syncthreads() is a fence and would drain the pieces just issued (vmcnt(0)).
+            // Nothing is stored to LDS here by a wave itself; the DMA'd bytes are ordered by the waits above.
+            asm volatile("s_barrier" ::: "memory");
+#ifdef AMC_SCAN_STAMPS
+            st_a += AMC_STAMP() - st_t;
+#endif
+        };
+        // this wave's piece `ys` of chunk c + 3 (wave 0: with step 0 its rs128 block), into ring buffer (cb + 3) % kNB
+        auto fetch = [&](int c, int cb, int ys) __attribute__((always_inline)) {
+            const int fb = (cb + kNB - 1) & (kNB - 1);
+            stage_piece(yprep, c + kNB - 1, fb, ys);
+            if (ys == 0) stage_rs(yrs, c + kNB - 1, fb);
+        };
+        int c = 0, cb = 0;
         if (active) {
-            load_y(y0, 0, 0);
+            load_y(y0, 0);
             mfma_first(acc[0][0], y0.f[0][0], xf[0][0], y0.ci[0]);
             mfma_first(acc[0][1], y0.f[1][0], xf[0][0], y0.ci[1]);
             mfma_acc(acc[0][0], y0.f[0][1], xf[0][1]);
@@ -443,79 +518,48 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
             // the first phase inserts a pending maximum: one below every accumulator, its key is below every floor key
             part[kXT - 1] = -(1 << 24);
             __builtin_amdgcn_sched_barrier(0);
-        }
-        // The sched_barriers pin the interleaving.  An accumulator is read (by inline asm, which
-        // hipcc does not hazard-check) only after FOUR further MFMAs have issued behind the one
-        // that completed it - the matrix pipe runs MFMAs in order, 16 clk each (4 passes), so two of them
-        // have run to their end since: well over the 7 wait states a 4-pass MFMA's result needs before a VALU read
-        // (two further MFMAs would do; the rule the 8-pass instruction needed, 11 states, held with two as well).
-        // one step = 32 rows' worth of Y held in `yc`; prefetches the next step into `yn`
-        // cb / nb: LDS buffers of chunk c and c + 1 (c % kNB, (c + 1) % kNB); ys = the step of the chunk, 0 .. kYS - 1
-        auto step = [&](YFrag& yc, YFrag& yn, int c, int cb, int nb, int ys) __attribute__((always_inline)) {
-            const int sp = ys;  // a chunk is one block
-            const bool lastt = ys == kYS - 1;
-            const bool cross = lastt && (c + 1 < nchunks);
-            // chunk c + 3 goes to the buffer chunk c - 1 left, (c + 3) % kNB: this wave's kPW pieces of it, one
-            // 1 KiB piece per step, never bunched
-            const bool fetch = c + kNB - 1 < nchunks;
-            static_assert(kPW == kYS, "one DMA piece per wave and step");
-            if (fetch) {
-                const int fb = (cb + kNB - 1) & (kNB - 1);
-                stage_piece(yprep, c + kNB - 1, fb, ys);
-                if (ys == 0) stage_rs(yrs, c + kNB - 1, fb);
-            }
-            if (cross) {
-#ifdef AMC_SCAN_STAMPS
-                const uint32_t st_t = AMC_STAMP();
-#endif
-                // Chunk c + 1 must have landed.  Loads return in the order they were issued, and behind this wave's
-                // pieces of chunk c + 1 it has issued its kPW pieces (wave 0: + 1 rs128 block) of every later chunk
-                // that exists, c + 2 and c + 3: so many may stay in flight and no more.  (At the first crossing chunks
-                // 1 and 2 have landed with the item's X rows; fewer pieces are in flight than the count allows.)
-                static_assert(kNB == 4, "the counted waits below are written out for three chunks ahead");
-                if (fetch) {
-                    if (wid == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * kPW + 2) : "memory");
-                    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * kPW) : "memory");
-                } else if (c + 2 < nchunks) {
-                    if (wid == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPW + 1) : "memory");
-                    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPW) : "memory");
-                } else {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // nothing further to fetch
+            // one step = 32 rows' worth of Y held in `yc`; prefetches the next step into `yn`.  ys = the step of the
+            // chunk, 0 .. kYS - 1, `steady` as above: both compile-time.  The chunk's last step crosses to the next
+            // chunk, moves the read bases there and prefetches its first step; behind the image's last chunk that reads
+            // a buffer nobody needs (result unused), to stay branch-free.
+            auto step = [&](YFrag& yc, YFrag& yn, int ys, bool steady) __attribute__((always_inline)) {
+                if (steady) fetch(c, cb, ys);
+                if (ys == kYS - 1) {
+                    const int rem = nchunks - 1 - c;
+                    if (steady || rem >= 1) crossing(steady, rem);
+                    advance(cb);
                 }
-                // a bare barrier: __syncthreads() is a fence and would drain the pieces just issued (vmcnt(0)).
-                // Nothing is stored to LDS here by a wave itself; the DMA'd bytes are ordered by the waits above.
-                asm volatile("s_barrier" ::: "memory");
-#ifdef AMC_SCAN_STAMPS
-                st_a += AMC_STAMP() - st_t;
-#endif
-            }
-            if (active) {
-                // very last step: re-read itself (result unused) to stay branch-free
-                const int nbuf = cross ? nb : cb;
-                const int nys = lastt ? (cross ? 0 : ys) : ys + 1;
-                const int gb = c;  // the block = the chunk
+                const int nys = ys == kYS - 1 ? 0 : ys + 1;
 #pragma unroll
-                for (int xt = 0; xt < kXT; ++xt) {
+                for (int xt = 0; xt < kXT; ++xt) {  // sp = ys, gb = c: a chunk is one block
                     if (xt + 1 < kXT)
-                        phase(acc[(xt + 1) & 1], yc, xt + 1, acc[xt & 1], xt, sp, gb);
+                        phase(acc[(xt + 1) & 1], yc, xt + 1, acc[xt & 1], xt, ys, c);
                     else
-                        phase(acc[0], yn, 0, acc[xt & 1], xt, sp, gb);
+                        phase(acc[0], yn, 0, acc[xt & 1], xt, ys, c);
                     if (xt < 6) {
-                        load_y_part(yn, nbuf, nys, xt);
+                        load_y_part(yn, nys, xt);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
-            }
-        };
+            };
 #pragma unroll 1
-        for (int c = 0; c < nchunks; ++c) {  // one chunk = one block
-            const int cb = c & (kNB - 1), nb = (c + 1) & (kNB - 1);
-            step(y0, y1, c, cb, nb, 0);
-            step(y1, y0, c, cb, nb, 1);
-            step(y0, y1, c, cb, nb, 2);
-            step(y1, y0, c, cb, nb, 3);
-        }
-        if (active) {
+            for (; c + kNB - 1 < nchunks; ++c, cb = (cb + 1) & (kNB - 1)) {
+                step(y0, y1, 0, true);
+                step(y1, y0, 1, true);
+                step(y0, y1, 2, true);
+                step(y1, y0, 3, true);
+            }
+#pragma unroll 1
+            for (; c < nchunks; ++c, cb = (cb + 1) & (kNB - 1)) {
+                step(y0, y1, 0, false);
+                step(y1, y0, 1, false);
+                step(y0, y1, 2, false);
+                step(y1, y0, 3, false);
+            }
+            // the read bases back to ring buffer 0 for the next item (every chunk moved them on by one)
+            yb0 -= cb * kChunkBytes;
+            yb1 -= cb * kChunkBytes;
+            cbs -= cb * kBN * 4;
             const int lastb = nchunks - 1;
             insert(kXT - 1, 126 - (lastb & 63));  // the last unit's maximum is still pending
             flush(lastb >> 6);
@@ -524,6 +568,16 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
                 best[xt] >>= kKeyShift;
                 sec[xt] >>= kKeyShift;
             }
+        } else {
+            // a wave without rows only feeds the ring: its pieces of every chunk, the same waits, the same barriers
+#pragma unroll 1
+            for (; c + kNB - 1 < nchunks; ++c, cb = (cb + 1) & (kNB - 1)) {
+#pragma unroll
+                for (int ys = 0; ys < kYS; ++ys) fetch(c, cb, ys);
+                crossing(true, kNB - 1);
+            }
+#pragma unroll 1
+            for (; c + 1 < nchunks; ++c) crossing(false, nchunks - 1 - c);
         }
         __syncthreads();  // everyone is done with the LDS chunk buffers (and has read the queue slot)
 #ifdef AMC_SCAN_STAMPS

@@ -30,10 +30,12 @@ def main():
     ap.add_argument("--rows", type=int, default=4096)
     ap.add_argument("--grid", type=int, default=0)
     ap.add_argument("--repeat", type=int, default=3, help="matches run before the sums are read (the first is discarded)")
+    ap.add_argument("--lib", default=LIB, help="a stamped library of another revision (default: the tree's own)")
     args = ap.parse_args()
-    if not os.path.exists(LIB):
+    lib_path = os.path.abspath(args.lib)
+    if not os.path.exists(lib_path):
         sys.exit("no diagnostic library: bash tools/scan_stamps_build.sh")
-    os.environ["AMC_LIB_PATH"] = LIB
+    os.environ["AMC_LIB_PATH"] = lib_path
     if args.grid:
         os.environ["AMC_SCAN_GRID"] = str(args.grid)
     import torch
@@ -42,7 +44,7 @@ def main():
 
     arena = bench.make_arena_torch(args.images, args.rows, 1234, torch.device("cuda:0")).cpu().numpy()
     s1, s2 = synth.exhaustive_pairs(args.images)
-    lib = ctypes.CDLL(LIB)
+    lib = ctypes.CDLL(lib_path)
     lib.amc_scan_stamps_read.argtypes = [ctypes.c_void_p, ctypes.c_int]
     buf = np.zeros((2, MAX_WG, WAVES, 8), np.uint32)
     with _capi.Context(0) as ctx:

@@ -84,7 +84,8 @@ static int pose_impl(amc_ctx* c, const char* who, const uint32_t* slot1, const u
         const Slot& b = c->slots[slot2[p]];
         if (!a.has_kp || !b.has_kp || !a.has_cam || !b.has_cam)
             return api_fail(AMC_E_STATE, "%s: pair %zu: keypoints/camera not uploaded", who, p);
-        if (match_offsets[p + 1] < match_offsets[p])
+        // an offset past the last one names rows that the index check below must not read
+        if (match_offsets[p + 1] < match_offsets[p] || match_offsets[p + 1] > total)
             return api_fail(AMC_E_INVALID, "%s: match_offsets not monotone at %zu", who, p);
         const uint64_t M = match_offsets[p + 1] - match_offsets[p];
         if (M > 0xFFFFFFFFull) return api_fail(AMC_E_INVALID, "%s: pair %zu has too many matches", who, p);

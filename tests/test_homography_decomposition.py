@@ -1,9 +1,15 @@
 """pycolmap.homography_decomposition = PoseFromHomographyMatrix (/root/reference/pycolmap/geometry/homography_matrix.h:13-40):
 the oracle's restatement against the geometry it must recover (CPU), the device path against the oracle bit for bit (GPU)."""
+import sys
+
 import numpy as np
 import pytest
 
 import oracle_lib as o
+import pose_cases as pc
+
+sys.path.insert(0, str(o.ROOT / "tests" / "golden"))
+import make_pose_ref_golden as pose_golden  # noqa: E402
 
 
 def rot(rng, angle):
@@ -87,6 +93,42 @@ def test_device_matches_the_oracle(seed):
         assert g[k].shape == w[k].shape, k
         np.testing.assert_array_equal(g[k].view(np.uint64), w[k].view(np.uint64), err_msg=k)
     ctx.close()
+
+
+@pytest.fixture(scope="module")
+def hom_ctx():
+    from pycolmap_amd import _capi
+    ctx = _capi.Context(0)
+    yield ctx
+    ctx.close()
+
+
+def same_bits(got, want, tag):
+    for k in ("R", "t", "n", "points3D"):
+        assert got[k].shape == want[k].shape, f"{tag} {k}"
+        np.testing.assert_array_equal(pc.bits(got[k]), pc.bits(want[k]), err_msg=f"{tag} {k}")
+
+
+@pytest.mark.gpu
+def test_named_cases_bit_exact_order_included(hom_ctx):
+    """pose_cases.homography_cases(): counts at the lane edges, garbage rows at lanes 0, 63, 64, 127 and 129 (the
+    points3D compaction), the three formula sets, +-H, the pure rotation and both sides of its threshold - against the
+    oracle and against tests/golden/pose_ref_v1.npz; points3D row for row"""
+    hs, want = pc.build_homography_cases()
+    _, homs = pose_golden.load()
+    assert list(homs) == list(hs)
+    got = {}
+    for name, c in hs.items():
+        g = got[name] = hom_ctx.homography_decomposition(c["H"], c["K1"], c["K2"], c["p1"], c["p2"])
+        same_bits(g, want[name], name)
+        same_bits(g, homs[name], f"{name} (fixture)")
+        assert len(g["points3D"]) == c["survivors"], name
+        # two calls in a row on one context give the same bits
+        same_bits(hom_ctx.homography_decomposition(c["H"], c["K1"], c["K2"], c["p1"], c["p2"]), g, f"{name} (again)")
+    # the survivors of the garbage case are the other rows, in input order: each point reprojects to its own row
+    X = got["garbage_edges"]["points3D"]
+    keep = sorted(set(range(130)) - set(pc.EDGE_ROWS))
+    np.testing.assert_allclose(X[:, :2] / X[:, 2:], hs["garbage_edges"]["p1"][keep], atol=1e-9)
 
 
 @pytest.mark.gpu

@@ -1,11 +1,19 @@
 """GPU parity tests of the relative pose (pose.hip: amc_pose_pairs and amc_verify_pairs with
 compute_relative_pose) against the oracle's EstimateTwoViewGeometryPose on identical inputs.
-Bit-exact: R, t, quaternion, tri_angle, the number of points in front of both cameras, config."""
+Bit-exact: R, t, quaternion, tri_angle, the number of points in front of both cameras, config.
+First on random scenes, then on the named cases of tests/pose_cases.py."""
+import ctypes as C
+import sys
+
 import numpy as np
 import pytest
 
 import oracle_lib as o
+import pose_cases as pc
 from pycolmap_amd import _capi, synth
+
+sys.path.insert(0, str(o.ROOT / "tests" / "golden"))
+import make_pose_ref_golden as pose_golden  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -164,3 +172,170 @@ def test_pose_rejects_unsupported_input(amc_ctx):
     got = amc_ctx.pose_pairs(np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros(1, np.uint64),
                              np.zeros((0, 2), np.uint32), [], None)
     assert len(got) == 0
+
+
+# ------------------------------------------------------------------------------------------------
+# The named cases of tests/pose_cases.py ("what is pinned"): lane edges of the ballots and the
+# compaction, ranks of the median selection, the branches of the decompositions, the slices of the workspace.
+# ------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def pose_ctx():
+    """one context for the new tests: every case of pose_cases.cases() in its own pair of slots (2 i, 2 i + 1), then
+    the masked scenes"""
+    ctx = _capi.Context(0)
+    cs = pc.cases()
+    masked = pc.masked_scenes()
+    ctx.reserve_slots(2 * (len(cs) + len(masked)))
+    slots = {}
+    for i, (name, c) in enumerate(cs.items()):
+        for s, cam, pts in ((2 * i, c["cam1"], c["pts1"]), (2 * i + 1, c["cam2"], c["pts2"])):
+            if c["f32"]:
+                ctx.upload_keypoints(s, pts.astype(np.float32))
+            else:
+                ctx.upload_points_f64(s, pts)
+            ctx.upload_camera(s, cam[0], cam[1], cam[2], cam[3], True)
+        slots[name] = 2 * i
+    for j, (M, sc) in enumerate(masked.items()):
+        base = 2 * (len(cs) + j)
+        for s, pts in ((base, sc["pts1"]), (base + 1, sc["pts2"])):
+            ctx.upload_keypoints(s, pts.astype(np.float32))
+            ctx.upload_camera(s, *sc["cam"], True)
+        slots[M] = base
+    yield ctx, slots
+    ctx.close()
+
+
+def run_cases(ctx, slots, names, matches=None):
+    """amc_pose_pairs on the listed cases, in that order, in one call; matches: name -> rows instead of the case's"""
+    cs = pc.cases()
+    mm = [cs[n]["matches"] if matches is None or n not in matches else matches[n] for n in names]
+    s1 = np.array([slots[n] for n in names], dtype=np.uint32)
+    off = np.zeros(len(names) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(m) for m in mm])
+    return ctx.pose_pairs(s1, s1 + 1, off, np.concatenate(mm).reshape(-1, 2), [cs[n]["config"] for n in names],
+                          np.stack([cs[n]["E"] for n in names]), np.stack([cs[n]["H"] for n in names]))
+
+
+def record_bits(rec):
+    return tuple(bits(rec[k]).tobytes() for k in ("R", "tvec", "qvec", "tri_angle")) + (int(rec["ok"]), int(rec["config"]),
+                                                                                         int(rec["num_points3D"]))
+
+
+@pytest.fixture(scope="module")
+def all_at_once(pose_ctx):
+    ctx, slots = pose_ctx
+    return run_cases(ctx, slots, list(pc.cases()))
+
+
+def test_named_cases_bit_exact_against_the_oracle_and_the_fixture(all_at_once):
+    cs, want = pc.build_cases()
+    poses, _ = pose_golden.load()
+    assert list(poses) == list(cs)
+    for k, name in enumerate(cs):
+        assert_pose_equal(all_at_once[k], want[name], name)
+        assert_pose_equal(all_at_once[k], poses[name], f"{name} (fixture)")
+    # the same values through either upload
+    names = list(cs)
+    assert record_bits(all_at_once[names.index("cameras_float32")]) == record_bits(all_at_once[names.index("cameras_float64")])
+
+
+def test_one_call_each_equals_all_in_one_call(pose_ctx, all_at_once):
+    ctx, slots = pose_ctx
+    for k, name in enumerate(pc.cases()):
+        assert record_bits(run_cases(ctx, slots, [name])[0]) == record_bits(all_at_once[k]), name
+
+
+def test_a_permuted_order_gives_the_permuted_result(pose_ctx, all_at_once):
+    ctx, slots = pose_ctx
+    names = list(pc.cases())
+    perm = np.random.default_rng(5).permutation(len(names))
+    got = run_cases(ctx, slots, [names[i] for i in perm])
+    for k, i in enumerate(perm):
+        assert record_bits(got[k]) == record_bits(all_at_once[i]), names[i]
+    back = run_cases(ctx, slots, names[::-1])
+    for k, name in enumerate(names[::-1]):
+        assert record_bits(back[k]) == record_bits(all_at_once[len(names) - 1 - k]), name
+
+
+def test_an_empty_pair_between_two_full_ones_changes_neither(pose_ctx, all_at_once):
+    ctx, slots = pose_ctx
+    names = list(pc.cases())
+    a, b = "rotation_x", "angles_above_90"
+    got = run_cases(ctx, slots, [a, "rotation_small", b], matches={"rotation_small": np.zeros((0, 2), np.uint32)})
+    assert record_bits(got[0]) == record_bits(all_at_once[names.index(a)])
+    assert record_bits(got[2]) == record_bits(all_at_once[names.index(b)])
+    c = pc.cases()["rotation_small"]
+    want = o.estimate_two_view_geometry_pose(pc.ocam(c["cam1"]), c["pts1"], pc.ocam(c["cam2"]), c["pts2"],
+                                             np.zeros((0, 2), np.uint32), c["config"], E=c["E"], H=c["H"])
+    assert_pose_equal(got[1], want, "the empty pair")
+
+
+def test_thirty_pairs_on_one_pair_of_slots_agree_with_the_single_call(pose_ctx, all_at_once):
+    ctx, slots = pose_ctx
+    names = list(pc.cases())
+    for name in ("survivors_edges", "duplicates_halves_130"):
+        got = run_cases(ctx, slots, [name] * 30)
+        for k in range(30):
+            assert record_bits(got[k]) == record_bits(all_at_once[names.index(name)]), (name, k)
+
+
+def test_masked_path_with_a_hole_in_every_chunk(pose_ctx):
+    """amc_verify_pairs with compute_relative_pose hands the pose kernel the estimation's mask.  The mask is the
+    planted one - rows 0, 63, 64 and M - 1 cleared - or the test fails; then the pose, bit for bit."""
+    ctx, slots = pose_ctx
+    masked = pc.masked_scenes()
+    s1 = np.array([slots[M] for M in masked], dtype=np.uint32)
+    off = np.zeros(len(masked) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(sc["matches"]) for sc in masked.values()])
+    mm = np.concatenate([sc["matches"] for sc in masked.values()])
+    tvg, mask, st = ctx.verify_pairs(s1, s1 + 1, off, mm, _capi.tvg_options(compute_relative_pose=1), seed=0)
+    for p, (M, sc) in enumerate(masked.items()):
+        w = pc.oracle_verify(sc)
+        pc.check_masked(sc, w["inlier_mask"])
+        got = mask[int(off[p]):int(off[p + 1])]
+        np.testing.assert_array_equal(got, w["inlier_mask"], err_msg=f"M {M}")
+        pc.check_masked(sc, got)
+        assert _capi.CONFIG_NAMES[tvg[p]["config"]] == w["config_name"] == "CALIBRATED", M
+        assert_pose_equal(st["pose"][p], w, f"masked M {M}")
+        assert int(st["pose"][p]["num_points3D"]) == M - len(sc["holes"])
+
+
+def test_refused_input_leaves_the_context_usable(pose_ctx, all_at_once):
+    ctx, slots = pose_ctx
+    names = list(pc.cases())
+    cs = pc.cases()
+    a = "rotation_y"
+    c = cs[a]
+
+    def still_works():
+        assert record_bits(run_cases(ctx, slots, [a])[0]) == record_bits(all_at_once[names.index(a)])
+
+    off = np.array([0, len(c["matches"])], dtype=np.uint64)
+    past = 2 * (len(cs) + len(pc.masked_scenes()))
+    with pytest.raises(_capi.AmcError, match="slot out of range"):      # a slot past the table
+        ctx.pose_pairs([slots[a]], [past], off, c["matches"], [c["config"]], [c["E"]], [c["H"]])
+    still_works()
+    with pytest.raises(_capi.AmcError, match="slot out of range"):
+        ctx.pose_pairs([0xFFFFFFFF], [slots[a] + 1], off, c["matches"], [c["config"]], [c["E"]], [c["H"]])
+    still_works()
+    # offsets that are not monotone: the second pair ends before it begins (every row read before the refusal exists)
+    s1 = np.array([slots[a]] * 3, dtype=np.uint32)
+    bad = np.array([0, 60, 50, 130], dtype=np.uint64)
+    with pytest.raises(_capi.AmcError, match="not monotone"):
+        ctx.pose_pairs(s1, s1 + 1, bad, c["matches"], [c["config"]] * 3, [c["E"]] * 3, [c["H"]] * 3)
+    still_works()
+    # ... and a first pair that ends past the last offset: refused before any row of it is looked at
+    with pytest.raises(_capi.AmcError, match="not monotone at 0"):
+        ctx.pose_pairs(s1[:2], s1[:2] + 1, np.array([0, 100, 50], dtype=np.uint64), c["matches"][:50], [c["config"]] * 2,
+                       [c["E"]] * 2, [c["H"]] * 2)
+    still_works()
+    # a NULL geometry array, through the C entry point
+    s = np.array([slots[a]], dtype=np.uint32)
+    s2 = s + 1
+    m = np.ascontiguousarray(c["matches"], dtype=np.uint32)
+    out = np.zeros(1, dtype=_capi.POSE_DTYPE)
+    v = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
+    rc = ctx._lib.amc_pose_pairs(ctx._h, v(s), v(s2), C.c_size_t(1), v(off), v(m), None, v(out))
+    assert rc != 0 and b"NULL" in ctx._lib.amc_last_error()
+    assert not out["ok"][0]
+    still_works()

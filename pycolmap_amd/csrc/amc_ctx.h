@@ -167,7 +167,7 @@ struct amc_ctx {
     ScanAccept h_accept{};
     float accept_ratio = 0.f, accept_distance = 0.f;
     bool accept_valid = false;
-    uint32_t* d_scalars = nullptr;  // [0] cursor, [1] queue head, [2] maxsq scratch, [3] resolve errors, [4] stream overrun, [5] mfma items, [7] copy parts taken
+    uint32_t* d_scalars = nullptr;  // [0] cursor, [1] queue head, [2] maxsq scratch, [3] resolve errors, [4] stream overrun, [5] mfma items, [7] copy parts taken, [8] [9] [10] lengths of the live lists (forward order, pair order, reverse order)
     // per-batch scratch of the match loop: a batch's cross-check chain (resolve, candidate selection, reverse scan,
     // finalize) is done before the next batch's forward scan writes the tables (match_impl)
     struct MatchScratch {
@@ -181,6 +181,9 @@ struct amc_ctx {
         DevBuf<uint32_t> d_accmask;  // one accept bit per row-table entry (mfma pairs)
         DevBuf<GuidedDev> d_guided;  // guided matching: one filter model per pair of the batch
         DevBuf<uint32_t> d_pair_off, d_pair_cnt, d_matches, d_cand_cnt, d_candbuf;
+        // live pairs of the batch (launch_live_pairs): the per-pair flag and the three ordered lists the cross-check
+        // chain's kernels index - d_order's live mfma pairs, every live pair, d_order2's pairs with candidates
+        DevBuf<uint32_t> d_live, d_live_fwd, d_live_all, d_live_rev, d_live_scan;  // (d_live_scan: the compactions' scratch)
         void release_all() {
             d_pairs.release(); d_work.release(); d_order.release(); d_order2.release();
             d_grp.release(); d_grp2.release(); d_seg_base.release(); d_grp_segs.release();
@@ -188,6 +191,8 @@ struct amc_ctx {
             d_rowbuf.release(); d_colbuf.release(); d_accmask.release(); d_guided.release();
             d_pair_off.release(); d_pair_cnt.release(); d_matches.release();
             d_cand_cnt.release(); d_candbuf.release();
+            d_live.release(); d_live_fwd.release(); d_live_all.release(); d_live_rev.release();
+            d_live_scan.release();
         }
         void release_large() {  // (amc_ctx_trim)
             d_rowbuf.release(); d_colbuf.release(); d_accmask.release(); d_matches.release(); d_candbuf.release();

@@ -430,21 +430,45 @@ hipError_t launch_match_mfma(int mode, const SegDesc* segs, const uint32_t* nite
                        uint32_t* queue_head, uint32_t* accmask, const ScanAccept* accept_dev, hipStream_t s,
                        const CopyJob& job = CopyJob(), uint32_t* copy_head = nullptr);
 
-hipError_t launch_resolve_index(int side, const ImageDev* imgs, const PairDev* pairs, uint32_t npairs,
+// The live-pair lists of a batch (match_common.hip).  Behind the scans nearly every pair of an exhaustive job has
+// nothing accepted; the per-pair kernels of the cross-check chain keep their grids (one workgroup per pair that COULD be
+// listed - the host does not know the live count) but index a compacted list, whose length they read from a device
+// scalar: a workgroup beyond it returns at once.
+// launch_live_pairs: a pair is live if it is an mfma pair with a non-zero accept word, or a dot4 / guided pair with rows
+// on both sides.  live[pi] = 0 (dead), 1 (live, dot4), 3 (live, mfma); every dead pair gets cand_cnt = pair_cnt =
+// pair_off = 0 (what select_candidates and finalize would have written) and every live dot4 pair cand_cnt = 0.
+// Then two ORDERED compactions: live_fwd = the live mfma pairs of `order` (norder entries, the forward scan's
+// streamed-image order, kept), live_all = every live pair in pair order; their lengths go to nlive[0] and nlive[1].
+// scratch: live_scratch_words(npairs) words, shared by the batch's compactions (norder <= npairs).
+size_t live_scratch_words(size_t npairs);
+hipError_t launch_live_pairs(const ImageDev* imgs, const PairDev* pairs, uint32_t npairs, const uint32_t* accmask,
+                             const uint32_t* order, uint32_t norder, uint32_t* live, uint32_t* live_fwd,
+                             uint32_t* live_all, uint32_t* nlive, uint32_t* cand_cnt, uint32_t* pair_cnt,
+                             uint32_t* pair_off, uint32_t* scratch, hipStream_t s);
+// list[0 .. *nlist) = the entries pi of order[0 .. norder) with key[pi] != 0, in order (select_candidates' cand_cnt ->
+// the pairs resolve_index(side 1) has rows for)
+hipError_t launch_compact_order(const uint32_t* order, uint32_t norder, uint32_t npairs, const uint32_t* key, uint32_t* list,
+                                uint32_t* nlist, uint32_t* scratch, hipStream_t s);
+
+// order / nlist: a live list and its length on the device; max_list bounds the grid (the list's length at most)
+hipError_t launch_resolve_index(int side, const ImageDev* imgs, const PairDev* pairs,
                           Top2* table, uint32_t* accmask, const float* acos_lut, FinalizeParams fp,
                           const uint32_t* cand_cnt, const uint32_t* candbuf, uint32_t* err_count,
-                          bool grouped, const uint32_t* order, uint32_t norder, hipStream_t s);
+                          bool grouped, const uint32_t* order, const uint32_t* nlist, uint32_t max_list, hipStream_t s);
 // largest image (padded rows) the tile-grouped variant of resolve_index handles (its LDS histogram)
 uint32_t resolve_grouped_max_rows();
 constexpr uint32_t kSelectMaxCols = 1u << 20;  // select_candidates' LDS bitmap: at most 128 KiB of dynamic shared memory
 
 // max_cols: the largest image 2 (rows) among the launch's pairs - sizes the kernel's LDS bitmap
+// list / nlist: the pairs to visit (a live list, its length on the device); npairs bounds the grid.  pair_off, pair_cnt
+// and cand_cnt stay indexed by pair.
 hipError_t launch_select_candidates(const ImageDev* imgs, const PairDev* pairs, uint32_t npairs, uint32_t max_cols,
                               const Top2* rowbuf, const uint32_t* accmask, const float* acos_lut,
-                              FinalizeParams fp, uint32_t* cand_cnt, uint32_t* candbuf, hipStream_t s);
+                              FinalizeParams fp, uint32_t* cand_cnt, uint32_t* candbuf, const uint32_t* list,
+                              const uint32_t* nlist, hipStream_t s);
 
-hipError_t launch_finalize(const ImageDev* imgs, const PairDev* pairs, uint32_t npairs,
-                     const Top2* rowbuf, const Top2* colbuf, uint32_t* accmask,
+hipError_t launch_finalize(const ImageDev* imgs, const PairDev* pairs, uint32_t npairs, const uint32_t* list,
+                     const uint32_t* nlist, const Top2* rowbuf, const Top2* colbuf, uint32_t* accmask,
                      const float* acos_lut, FinalizeParams fp, uint32_t* cursor, uint32_t capacity,
                      uint32_t* pair_off, uint32_t* pair_cnt, uint32_t* matches, hipStream_t s);
 

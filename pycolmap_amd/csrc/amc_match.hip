@@ -239,7 +239,31 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
     };
     // host side of a batch: which kernel takes each pair, the work queues (mfma: one item per pair, in
     // an order that keeps co-resident workgroups on the same streamed image; dot4: one item per 64 rows)
-    auto prepare = [&](Batch& b) {
+    // The reverse scan's queue order, (image 1, image 2), and its group cuts.  Nothing needs them before the batch's
+    // forward scan is enqueued: the call's first batch builds them behind enqueue_scan, beside the scan, instead of
+    // with the device idle (every later batch is prepared beside the scan before it anyway).
+    auto build_reverse_order = [&](Batch& b) {
+        const int k = b.set;
+        const size_t nord = b.nord;
+        if (!nord || !o.cross_check) return;
+        const PairDev* hp = c->h_pairs[k].p;
+        const size_t nslots = c->slots.size();
+        std::vector<uint32_t> cnt(nslots + 1), tmp(nord);
+        auto by_slot = [&](const uint32_t* src, uint32_t* dst, bool key_is_slot2) {
+            std::fill(cnt.begin(), cnt.end(), 0u);
+            for (size_t q = 0; q < nord; ++q) ++cnt[(key_is_slot2 ? hp[src[q]].slot2 : hp[src[q]].slot1) + 1];
+            for (size_t v = 0; v < nslots; ++v) cnt[v + 1] += cnt[v];
+            for (size_t q = 0; q < nord; ++q) dst[cnt[key_is_slot2 ? hp[src[q]].slot2 : hp[src[q]].slot1]++] = src[q];
+        };
+        uint32_t* ord2 = c->h_order2[k].p;
+        by_slot(c->h_order[k].p, tmp.data(), true);  // minor key: image 2
+        by_slot(tmp.data(), ord2, false);            // major key: image 1 (stable)
+        size_t ngrp2 = 0;
+        for (size_t q = 0; q < nord; ++q)
+            if (q == 0 || hp[ord2[q]].slot1 != hp[ord2[q - 1]].slot1) c->h_grp2[k].p[ngrp2++] = (uint32_t)q;
+        c->h_grp2[k].p[ngrp2] = (uint32_t)nord;  // (ngrp2 == b.ngrp2: prepare() counted the distinct images 1)
+    };
+    auto prepare = [&](Batch& b, bool defer_reverse) {
         const int k = b.set;
         const size_t nb = b.nb, begin = b.begin;
         if (!hc(c->h_pairs[k].ensure(nb), "pinned pairs") || !hc(c->h_order[k].ensure(nb), "pinned order") ||
@@ -257,7 +281,8 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
                            (!o.cross_check || y.dev.rows_pad <= mfma_max_cols);
         }
         PairDev* hp = c->h_pairs[k].p;
-        size_t row_off = 0, col_off = 0, nwork = 0, nord = 0;
+        size_t row_off = 0, col_off = 0, nwork = 0, nord = 0, nimg1 = 0;
+        std::vector<uint8_t> seen1(c->slots.size(), 0);  // images 1 of the mfma pairs: the reverse order's groups
         b.grouped_resolve = !resolve_ungrouped;
         for (size_t i = 0; i < nb; ++i) {
             const Slot& x = c->slots[slot1[begin + i]];
@@ -283,6 +308,7 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
             if (!nonempty) continue;
             if (want_mfma[i]) {
                 c->h_order[k].p[nord++] = (uint32_t)i;
+                if (!seen1[pd.slot1]) { seen1[pd.slot1] = 1; ++nimg1; }
                 ++n_mfma;
                 b.max_cols = std::max(b.max_cols, y.dev.rows);
                 // the tile-grouped resolve needs both images' tiles to fit its LDS histogram
@@ -309,11 +335,6 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
             uint32_t* ord = c->h_order[k].p;
             by_slot(ord, tmp.data(), false);   // minor key: image 1
             by_slot(tmp.data(), ord, true);    // major key: image 2 (stable)
-            if (o.cross_check) {
-                uint32_t* ord2 = c->h_order2[k].p;
-                by_slot(ord, tmp.data(), true);    // minor key: image 2
-                by_slot(tmp.data(), ord2, false);  // major key: image 1
-            }
         }
         // Cut both orders where the streamed image changes (the packing kernels fill whole items per image),
         // and bound the number of segment descriptors: ceil(rows / 128) per pair plus up to one item of padding
@@ -332,12 +353,7 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
                 seg2 += (c->slots[pq.slot2].dev.rows + kSegRows - 1) / kSegRows;
             }
             c->h_grp[k].p[b.ngrp] = (uint32_t)nord;
-            if (o.cross_check) {
-                for (size_t q = 0; q < nord; ++q)
-                    if (q == 0 || hp[c->h_order2[k].p[q]].slot1 != hp[c->h_order2[k].p[q - 1]].slot1)
-                        c->h_grp2[k].p[b.ngrp2++] = (uint32_t)q;
-                c->h_grp2[k].p[b.ngrp2] = (uint32_t)nord;
-            }
+            if (o.cross_check) b.ngrp2 = nimg1;  // (the cuts themselves: build_reverse_order)
             b.seg_cap = std::max(seg1 + kSegsPerItem * b.ngrp, o.cross_check ? seg2 + kSegsPerItem * b.ngrp2 : 0);
         }
         b.nwork_grid = 0;
@@ -364,6 +380,7 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
         b.row_off = row_off;
         b.nwork = nwork;
         b.nord = nord;
+        if (!defer_reverse) build_reverse_order(b);
         return true;
     };
     // device side of a batch, first part, on the stream: H2D of the queues, segment packing, the scans
@@ -376,6 +393,8 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
                           S.d_rowbuf.cap < b.top_rows || S.d_colbuf.cap < b.top_cols ||
                           S.d_accmask.cap < b.top_rows / 32 + 8 || S.d_pair_off.cap < nb || S.d_pair_cnt.cap < nb ||
                           S.d_matches.cap < 2 * b.cap || S.d_cand_cnt.cap < nb || S.d_candbuf.cap < b.top_cols ||
+                          S.d_live.cap < nb || S.d_live_fwd.cap < nb || S.d_live_all.cap < nb || S.d_live_rev.cap < nb ||
+                          S.d_live_scan.cap < live_scratch_words(nb) ||
                           S.d_work.cap < nwork || (geoms && S.d_guided.cap < nb) || S.d_segs.cap < b.seg_cap ||
                           S.d_seg_base.cap < nord || S.d_grp.cap < b.ngrp + 1 || S.d_grp2.cap < b.ngrp2 + 1 ||
                           S.d_grp_segs.cap < std::max(b.ngrp, b.ngrp2) || S.d_grp_item_base.cap < std::max(b.ngrp, b.ngrp2);
@@ -387,6 +406,9 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
             !hc(S.d_pair_off.ensure(nb), "pair_off") || !hc(S.d_pair_cnt.ensure(nb), "pair_cnt") ||
             !hc(S.d_matches.ensure(2 * b.cap), "dev matches") ||
             !hc(S.d_cand_cnt.ensure(nb), "cand_cnt") || !hc(S.d_candbuf.ensure(b.top_cols), "candbuf") ||
+            !hc(S.d_live.ensure(nb), "live flags") || !hc(S.d_live_fwd.ensure(nb), "live list (forward)") ||
+            !hc(S.d_live_all.ensure(nb), "live list") || !hc(S.d_live_rev.ensure(nb), "live list (reverse)") ||
+            !hc(S.d_live_scan.ensure(live_scratch_words(nb)), "live list scratch") ||
             (nwork && !hc(S.d_work.ensure(nwork), "dev work")) || (geoms && !hc(S.d_guided.ensure(nb), "dev guided")) ||
             !hc(S.d_segs.ensure(b.seg_cap), "segment descriptors") || !hc(S.d_seg_base.ensure(nord), "segment bases") ||
             !hc(S.d_grp.ensure(b.ngrp + 1), "group cuts") || !hc(S.d_grp2.ensure(b.ngrp2 + 1), "group cuts") ||
@@ -456,20 +478,28 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
         kernel_launches += (nord ? 1 : 0) + (b.nwork_grid ? 1 : 0) + (nwork > b.nwork_grid ? 1 : 0);
         return hc(hipEventRecord(c->bev[k][1], st), "event record");
     };
-    // second part, behind the scans: tile -> index, lazy cross check, finalize, D2H of the counters
+    // second part, behind the scans: the live pairs, tile -> index, lazy cross check, finalize, D2H of the counters.
+    // Every per-pair kernel of the chain visits a live list (amc_internal.h, launch_live_pairs): d_scalars[8] pairs of
+    // d_live_fwd, [9] of d_live_all, [10] of d_live_rev.
     auto enqueue_chain = [&](Batch& b) {
         const int k = b.set;
         amc_ctx::MatchScratch& S = c->ms;
         const size_t nb = b.nb, nord = b.nord;
+        uint32_t* const nlive = c->d_scalars + 8;
+        if (!hc(launch_live_pairs(c->d_imgs.p, S.d_pairs.p, (uint32_t)nb, S.d_accmask.p, S.d_order.p, (uint32_t)nord,
+                                  S.d_live.p, S.d_live_fwd.p, S.d_live_all.p, nlive, S.d_cand_cnt.p, S.d_pair_cnt.p,
+                                  S.d_pair_off.p, S.d_live_scan.p, st), "live pairs"))
+            return false;
         if (nord &&  // tile -> exact index for the accepted rows
-            !hc(launch_resolve_index(0, c->d_imgs.p, S.d_pairs.p, (uint32_t)nb, S.d_rowbuf.p, S.d_accmask.p, c->d_lut,
+            !hc(launch_resolve_index(0, c->d_imgs.p, S.d_pairs.p, S.d_rowbuf.p, S.d_accmask.p, c->d_lut,
                                      fp, S.d_cand_cnt.p, S.d_candbuf.p, c->d_scalars + 3, b.grouped_resolve,
-                                     S.d_order.p, (uint32_t)nord, st), "resolve (rows)"))
+                                     S.d_live_fwd.p, nlive, (uint32_t)nord, st), "resolve (rows)"))
             return false;
         if (nord && o.cross_check) {
             // lazy cross check: reverse scan only for the columns accepted rows point at
             if (!hc(launch_select_candidates(c->d_imgs.p, S.d_pairs.p, (uint32_t)nb, b.max_cols, S.d_rowbuf.p,
-                                             S.d_accmask.p, c->d_lut, fp, S.d_cand_cnt.p, S.d_candbuf.p, st),
+                                             S.d_accmask.p, c->d_lut, fp, S.d_cand_cnt.p, S.d_candbuf.p,
+                                             S.d_live_all.p, nlive + 1, st),
                     "candidate selection"))
                 return false;
             if (!hc(hipMemcpyAsync(S.d_order2.p, c->h_order2[k].p, nord * sizeof(uint32_t),
@@ -477,19 +507,23 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
                 !hc(hipMemcpyAsync(S.d_grp2.p, c->h_grp2[k].p, (b.ngrp2 + 1) * sizeof(uint32_t),
                                    hipMemcpyHostToDevice, st), "H2D group cuts"))
                 return false;
-            // the candidate counts exist only on the device: the packing kernels read them there
-            if (!hc(launch_build_segments(1, c->d_imgs.p, S.d_pairs.p, S.d_order2.p, S.d_grp2.p, (uint32_t)b.ngrp2,
+            // the candidate counts exist only on the device: the packing kernels read them there, and the reverse
+            // resolve visits the pairs that have any
+            if (!hc(launch_compact_order(S.d_order2.p, (uint32_t)nord, (uint32_t)nb, S.d_cand_cnt.p, S.d_live_rev.p, nlive + 2,
+                                         S.d_live_scan.p, st),
+                    "live pairs (reverse)") ||
+                !hc(launch_build_segments(1, c->d_imgs.p, S.d_pairs.p, S.d_order2.p, S.d_grp2.p, (uint32_t)b.ngrp2,
                                           S.d_cand_cnt.p, S.d_candbuf.p, S.d_colbuf.p, S.d_seg_base.p, S.d_grp_segs.p,
                                           S.d_grp_item_base.p, S.d_segs.p, c->d_scalars + 5, st), "segment packing (reverse)") ||
                 !hc(launch_match_mfma(1, S.d_segs.p, c->d_scalars + 5, (uint32_t)std::min<size_t>(b.seg_cap, 0xFFFFFFFFu),
                                       c->d_scalars + 1, S.d_accmask.p, c->d_accept, st), "reverse scan") ||
-                !hc(launch_resolve_index(1, c->d_imgs.p, S.d_pairs.p, (uint32_t)nb, S.d_colbuf.p, S.d_accmask.p, c->d_lut,
+                !hc(launch_resolve_index(1, c->d_imgs.p, S.d_pairs.p, S.d_colbuf.p, S.d_accmask.p, c->d_lut,
                                          fp, S.d_cand_cnt.p, S.d_candbuf.p, c->d_scalars + 3, b.grouped_resolve,
-                                         S.d_order2.p, (uint32_t)nord, st), "resolve (columns)"))
+                                         S.d_live_rev.p, nlive + 2, (uint32_t)nord, st), "resolve (columns)"))
                 return false;
         }
         if (!hc(hipEventRecord(c->bev[k][2], st), "event record") ||
-            !hc(launch_finalize(c->d_imgs.p, S.d_pairs.p, (uint32_t)nb, S.d_rowbuf.p, S.d_colbuf.p,
+            !hc(launch_finalize(c->d_imgs.p, S.d_pairs.p, (uint32_t)nb, S.d_live_all.p, nlive + 1, S.d_rowbuf.p, S.d_colbuf.p,
                                 S.d_accmask.p, c->d_lut, fp, c->d_scalars, (uint32_t)std::min(b.cap, (size_t)0xFFFFFFFFu),
                                 S.d_pair_off.p, S.d_pair_cnt.p, S.d_matches.p, st), "finalize"))
             return false;
@@ -630,10 +664,12 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
     if (npairs > 0) {
         Batch cur = carve(0, 0);
         auto tp = std::chrono::steady_clock::now();
-        bool ok = prepare(cur);
+        bool ok = prepare(cur, true);
         t_prepare += since(tp);
         tp = std::chrono::steady_clock::now();
-        ok = ok && enqueue_scan(cur) && enqueue_chain(cur);
+        ok = ok && enqueue_scan(cur);
+        if (ok) build_reverse_order(cur);  // (beside the scan)
+        ok = ok && enqueue_chain(cur);
         t_enqueue += since(tp);
         // The host runs one batch ahead of the device: while batch `cur` is scanned, the next batch's lists are
         // prepared; the matches of the batch BEFORE cur are read out (scatter) only after that - their copy rides in
@@ -647,7 +683,7 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
             if (have_next) {
                 tp = std::chrono::steady_clock::now();
                 next = carve(cur.end, cur.set ^ 1);
-                ok = prepare(next);
+                ok = prepare(next, false);
                 t_prepare += since(tp);
             }
             tp = std::chrono::steady_clock::now();

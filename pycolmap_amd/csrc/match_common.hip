@@ -90,7 +90,8 @@ hipError_t launch_prep(const uint8_t* raw, uint8_t* prep, int32_t* rs128, uint32
 }
 
 // ---------------------------------------------------------------------------------------
-// finalize: one workgroup per pair.  Applies COLMAP's per-row acceptance tests
+// finalize: one workgroup per live pair (live_flag_kernel below; the grid is the batch's pair count, workgroups beyond
+// the live list's length return).  Applies COLMAP's per-row acceptance tests
 // (FindBestMatchesOneWayBruteForce) to both one-way tables, the cross check
 // (FindBestMatchesBruteForce), and emits (idx1, idx2) ascending in idx1.
 //
@@ -105,6 +106,7 @@ constexpr int kFinalizeThreads = 256;
 static_assert(kRowPad % kFinalizeThreads == 0, "finalize_kernel's pass 1 rounds a pair's rows up to its block size");
 __global__ __launch_bounds__(kFinalizeThreads) void finalize_kernel(
     const ImageDev* __restrict__ imgs, const PairDev* __restrict__ pairs,
+    const uint32_t* __restrict__ live, const uint32_t* __restrict__ nlive,
     const Top2* __restrict__ rowbuf, const Top2* __restrict__ colbuf,
     uint32_t* accmask, const float* __restrict__ lut, FinalizeParams fp,
     uint32_t* __restrict__ cursor,
@@ -112,7 +114,9 @@ __global__ __launch_bounds__(kFinalizeThreads) void finalize_kernel(
     uint32_t* __restrict__ matches) {
     __shared__ uint32_t wave_cnt[4];
     __shared__ uint32_t s_base;
-    const PairDev p = pairs[blockIdx.x];
+    if (blockIdx.x >= *nlive) return;  // (the dead pairs' pair_off / pair_cnt were written by live_flag_kernel)
+    const uint32_t pi = live[blockIdx.x];
+    const PairDev p = pairs[pi];
     const uint32_t n1 = imgs[p.slot1].rows, n2 = imgs[p.slot2].rows;
     const Top2* rows = rowbuf + p.row_off;
     const Top2* cols = colbuf + p.col_off;
@@ -159,8 +163,8 @@ __global__ __launch_bounds__(kFinalizeThreads) void finalize_kernel(
         const uint32_t total = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
         const uint32_t b = total ? atomicAdd(cursor, total) : 0u;
         s_base = b;
-        pair_off[blockIdx.x] = b;
-        pair_cnt[blockIdx.x] = total;
+        pair_off[pi] = b;
+        pair_cnt[pi] = total;
     }
     __syncthreads();
     uint32_t running = s_base;
@@ -213,8 +217,9 @@ __global__ __launch_bounds__(256) void resolve_index_kernel(
     Top2* __restrict__ table, uint32_t* __restrict__ accmask, const float* __restrict__ lut,
     FinalizeParams fp, const uint32_t* __restrict__ cand_cnt, const uint32_t* __restrict__ candbuf,
     uint32_t* __restrict__ err_count,
-    const uint32_t* __restrict__ order) {
-    const uint32_t pi = order ? order[blockIdx.x] : blockIdx.x;  // (in the streamed image's order: neighbours share Y)
+    const uint32_t* __restrict__ order, const uint32_t* __restrict__ nlist) {
+    if (blockIdx.x >= *nlist) return;  // (beyond the live list)
+    const uint32_t pi = order[blockIdx.x];  // (in the streamed image's order: neighbours share Y)
     const PairDev p = pairs[pi];
     if (p.mode == 0) return;  // dot4 pairs carry exact indices already
     const ImageDev X = imgs[side == 0 ? p.slot1 : p.slot2];
@@ -309,7 +314,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     Top2* __restrict__ table, uint32_t* __restrict__ accmask, const float* __restrict__ lut,
     FinalizeParams fp, const uint32_t* __restrict__ cand_cnt, const uint32_t* __restrict__ candbuf,
     uint32_t* __restrict__ err_count,
-    const uint32_t* __restrict__ order) {
+    const uint32_t* __restrict__ order, const uint32_t* __restrict__ nlist) {
     // 48 KB, three workgroups per CU.  While sorting: s_list | s_sorted | s_hist; while walking the rows the first
     // third holds the rows' dot products (`part`) and the last third the batch's X rows (over s_hist and beyond).
     __shared__ __attribute__((aligned(16))) uint32_t s_pool[3 * kResolveChunk];
@@ -321,7 +326,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     __shared__ uint32_t s_wsum[4];
     __shared__ uint32_t s_count;
     __shared__ uint32_t s_brow[4][32], s_btile[4][32];  // the batch's rows and tiles, by wave
-    const uint32_t pi = order ? order[blockIdx.x] : blockIdx.x;  // (in the streamed image's order: neighbours share Y)
+    if (blockIdx.x >= *nlist) return;  // (beyond the live list)
+    const uint32_t pi = order[blockIdx.x];  // (in the streamed image's order: neighbours share Y)
     const PairDev p = pairs[pi];
     if (p.mode == 0) return;  // dot4 pairs carry exact indices already
     const ImageDev X = imgs[side == 0 ? p.slot1 : p.slot2];
@@ -545,7 +551,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     Top2* __restrict__ table, uint32_t* __restrict__ accmask, const float* __restrict__ lut,
     FinalizeParams fp, const uint32_t* __restrict__ cand_cnt, const uint32_t* __restrict__ candbuf,
     uint32_t* __restrict__ err_count,
-    const uint32_t* __restrict__ order) {
+    const uint32_t* __restrict__ order, const uint32_t* __restrict__ nlist) {
     // 38 KB, four workgroups per CU: the chunk's accepted rows, the same sorted by tile, the tile histogram
     __shared__ __attribute__((aligned(16))) uint32_t s_pool[2 * kResolveChunkM + kResolveMaxTiles];
     uint32_t* const s_list = s_pool;                        // (tile << 12) | position in the chunk
@@ -554,7 +560,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     __shared__ uint32_t s_wsum[4];
     __shared__ uint32_t s_count;
     __shared__ uint32_t s_brow[4][32];  // the batch's rows, by wave
-    const uint32_t pi = order ? order[blockIdx.x] : blockIdx.x;  // (in the streamed image's order: neighbours share Y)
+    if (blockIdx.x >= *nlist) return;  // (beyond the live list)
+    const uint32_t pi = order[blockIdx.x];  // (in the streamed image's order: neighbours share Y)
     const PairDev p = pairs[pi];
     if (p.mode == 0) return;  // dot4 pairs carry exact indices already
     const ImageDev X = imgs[side == 0 ? p.slot1 : p.slot2];
@@ -764,33 +771,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
 }
 
-hipError_t launch_resolve_index(int side, const ImageDev* imgs, const PairDev* pairs, uint32_t npairs,
+hipError_t launch_resolve_index(int side, const ImageDev* imgs, const PairDev* pairs,
                           Top2* table, uint32_t* accmask, const float* acos_lut, FinalizeParams fp,
                           const uint32_t* cand_cnt, const uint32_t* candbuf, uint32_t* err_count,
-                          bool grouped, const uint32_t* order, uint32_t norder, hipStream_t s) {
-    // `order` (norder mfma pairs, sorted by the image this side STREAMS): a workgroup per listed pair, so that
+                          bool grouped, const uint32_t* order, const uint32_t* nlist, uint32_t max_list, hipStream_t s) {
+    // `order` (*nlist live mfma pairs, sorted by the image this side STREAMS): a workgroup per listed pair, so that
     // workgroups running at the same time read the same Y tiles - on the dense set a pair's workgroup reads all of
     // image Y (512 KB of tiles) and a third of image X; in plain pair order (image 1 major) neighbours shared X only
-    // and the launch moved ~0.7 MB per pair from HBM.  Without it: one workgroup per pair of the batch.
-    const uint32_t grid = order ? norder : npairs;
+    // and the launch moved ~0.7 MB per pair from HBM.  The grid is the list's bound: the host does not know its length.
+    const uint32_t grid = max_list;
     if (grid == 0) return hipSuccess;
     const bool dot4_form = std::getenv("AMC_RESOLVE_DOT4") != nullptr;  // (test hook / A/B: the v_dot4 form)
     if (grouped && !dot4_form)
         hipLaunchKernelGGL(resolve_index_mfma_kernel, dim3(grid), dim3(256), 0, s, side, imgs, pairs,
-                           table, accmask, acos_lut, fp, cand_cnt, candbuf, err_count, order);
+                           table, accmask, acos_lut, fp, cand_cnt, candbuf, err_count, order, nlist);
     else if (grouped)
         hipLaunchKernelGGL(resolve_index_grouped_kernel, dim3(grid), dim3(256), 0, s, side, imgs, pairs,
-                           table, accmask, acos_lut, fp, cand_cnt, candbuf, err_count, order);
+                           table, accmask, acos_lut, fp, cand_cnt, candbuf, err_count, order, nlist);
     else
         hipLaunchKernelGGL(resolve_index_kernel, dim3(grid), dim3(256), 0, s, side, imgs, pairs,
-                           table, accmask, acos_lut, fp, cand_cnt, candbuf, err_count, order);
+                           table, accmask, acos_lut, fp, cand_cnt, candbuf, err_count, order, nlist);
     return hipGetLastError();
 }
 uint32_t resolve_grouped_max_rows() { return kResolveMaxTiles * 32; }
 
 // ---------------------------------------------------------------------------------------
 // select_candidates: which rows of image 2 ("columns") does the cross check need?  Exactly
-// those some accepted row of image 1 points at.  One workgroup per pair: rows that pass
+// those some accepted row of image 1 points at.  One workgroup per live pair: rows that pass
 // COLMAP's one-way tests set bit best_idx in an LDS bitmap; the bitmap is then compacted,
 // ascending, into candbuf[col_off ...] and counted.  The bitmap is dynamic shared memory sized
 // by the launch's largest image 2 (kSelectMaxCols = 1 Mi columns = 128 KiB bounds it): thread t
@@ -800,13 +807,15 @@ __global__ __launch_bounds__(256) void select_candidates_kernel(
     const ImageDev* __restrict__ imgs, const PairDev* __restrict__ pairs,
     const Top2* __restrict__ rowbuf, const uint32_t* __restrict__ accmask,
     const float* __restrict__ lut, FinalizeParams fp, uint32_t* __restrict__ cand_cnt,
-    uint32_t* __restrict__ candbuf) {
+    uint32_t* __restrict__ candbuf, const uint32_t* __restrict__ live, const uint32_t* __restrict__ nlive) {
     extern __shared__ uint32_t bits[];  // 256 * per words (the launch's bound; this pair uses what its n2 needs)
     __shared__ uint32_t wsum[4];
-    const PairDev p = pairs[blockIdx.x];
+    if (blockIdx.x >= *nlive) return;  // (the dead pairs' cand_cnt = 0 was written by live_flag_kernel)
+    const uint32_t pi = live[blockIdx.x];
+    const PairDev p = pairs[pi];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     if (p.mode == 0) {  // dot4 pair: its column table is complete already
-        if (tid == 0) cand_cnt[blockIdx.x] = 0;
+        if (tid == 0) cand_cnt[pi] = 0;
         return;
     }
     const uint32_t n1 = imgs[p.slot1].rows, n2 = imgs[p.slot2].rows;
@@ -845,12 +854,13 @@ __global__ __launch_bounds__(256) void select_candidates_kernel(
             ww &= ww - 1;
         }
     }
-    if (tid == 255) cand_cnt[blockIdx.x] = base + inc;
+    if (tid == 255) cand_cnt[pi] = base + inc;
 }
 
 hipError_t launch_select_candidates(const ImageDev* imgs, const PairDev* pairs, uint32_t npairs, uint32_t max_cols,
                               const Top2* rowbuf, const uint32_t* accmask, const float* acos_lut,
-                              FinalizeParams fp, uint32_t* cand_cnt, uint32_t* candbuf, hipStream_t s) {
+                              FinalizeParams fp, uint32_t* cand_cnt, uint32_t* candbuf, const uint32_t* list,
+                              const uint32_t* nlist, hipStream_t s) {
     if (npairs == 0) return hipSuccess;
     const uint32_t per = ((max_cols + 31) / 32 + 255) / 256;
     const size_t shmem = (size_t)std::max(per, 1u) * 256 * sizeof(uint32_t);
@@ -860,8 +870,163 @@ hipError_t launch_select_candidates(const ImageDev* imgs, const PairDev* pairs, 
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(select_candidates_kernel, dim3(npairs), dim3(256), shmem, s, imgs, pairs,
-                       rowbuf, accmask, acos_lut, fp, cand_cnt, candbuf);
+                       rowbuf, accmask, acos_lut, fp, cand_cnt, candbuf, list, nlist);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// Live pairs.  Of an exhaustive job's pairs a few per cent have anything accepted behind the forward scan; the
+// kernels of the cross-check chain above run a workgroup per pair, and for a dead pair that workgroup loaded the
+// pair, swept its accept words, met its barriers and left.  live_flag_kernel sweeps the accept words once (a wave per
+// pair, 16 bytes per lane: a 4,096-row pair is half a kilobyte), writes for the dead pairs what select_candidates and
+// finalize would have written, and compact_count_kernel / compact_scatter_kernel turn the flags into ordered lists the chain's kernels index.
+// ---------------------------------------------------------------------------------------
+static_assert(kRowPad % 128 == 0, "live_flag_kernel reads a pair's accept words 16 bytes (128 rows) at a time");
+__global__ __launch_bounds__(256) void live_flag_kernel(const ImageDev* __restrict__ imgs, const PairDev* __restrict__ pairs,
+                                                        uint32_t npairs, const uint32_t* __restrict__ accmask,
+                                                        uint32_t* __restrict__ live, uint32_t* __restrict__ cand_cnt,
+                                                        uint32_t* __restrict__ pair_cnt, uint32_t* __restrict__ pair_off) {
+    const uint32_t pi = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (pi >= npairs) return;
+    const PairDev p = pairs[pi];
+    uint32_t flag;
+    if (p.mode) {
+        // the pair's words: accmask[row_off / 32 ...), rows_pad / 32 of them, inside the pair's own region of the mask
+        const uint4* w = reinterpret_cast<const uint4*>(accmask + (p.row_off >> 5));
+        const uint32_t n16 = imgs[p.slot1].rows_pad / 128;
+        uint32_t any = 0;
+        for (uint32_t k = lane; k < n16; k += 64) {
+            const uint4 v = w[k];
+            any |= v.x | v.y | v.z | v.w;
+        }
+        flag = __ballot(any != 0) ? 3u : 0u;
+    } else {  // dot4 / guided: complete tables, always finalized
+        flag = (imgs[p.slot1].rows != 0 && imgs[p.slot2].rows != 0) ? 1u : 0u;
+    }
+    if (lane == 0) {
+        live[pi] = flag;
+        if (flag != 3u) cand_cnt[pi] = 0;
+        if (flag == 0u) {
+            pair_cnt[pi] = 0;
+            pair_off[pi] = 0;
+        }
+    }
+}
+
+// Ordered compaction: list = the entries pi of order[0 .. n) (order == nullptr: pi = 0 .. n - 1) with key[pi] & mask != 0,
+// in that order; *nlist = how many.  Two kernels, a 256-thread block per segment of kCompactSeg entries, two jobs to a
+// launch: compact_count_kernel reads a thread's kCompactPer consecutive entries and their keys (for the forward order a
+// gather, a cache line per entry - one block doing all of a 65,536-pair batch spent 34 us in its CU's address unit),
+// leaves the thread's keep bits and the segment's count; compact_scatter_kernel adds the counts of the segments
+// before its own, scans its threads' counts (the scan of seg_count_kernel, match_mfma.hip) and writes the entries.
+constexpr uint32_t kCompactPer = 8, kCompactThreads = 256, kCompactSeg = kCompactPer * kCompactThreads;
+static_assert(kCompactPer == 8, "a thread's entries are read as two uint4");
+struct CompactJob {
+    const uint32_t* order;
+    const uint32_t* key;
+    uint32_t* list;
+    uint32_t* nlist;
+    uint32_t* keep;    // nseg * kCompactThreads words: a thread's keep bits
+    uint32_t* segcnt;  // nseg words
+    uint32_t n, mask, nseg;
+};
+static uint32_t compact_segments(uint32_t n) { return std::max(1u, (n + kCompactSeg - 1) / kCompactSeg); }
+size_t live_scratch_words(size_t npairs) { return 3 * (size_t)compact_segments((uint32_t)npairs) * (kCompactThreads + 1); }
+static CompactJob compact_job(const uint32_t* order, uint32_t n, const uint32_t* key, uint32_t mask, uint32_t* list,
+                              uint32_t* nlist, uint32_t* scratch) {
+    const uint32_t nseg = compact_segments(n);
+    return CompactJob{order, key, list, nlist, scratch, scratch + (size_t)nseg * kCompactThreads, n, mask, nseg};
+}
+__global__ __launch_bounds__(kCompactThreads) void compact_count_kernel(CompactJob j0, CompactJob j1) {
+    __shared__ uint32_t wsum[4];
+    const bool first = blockIdx.x < j0.nseg;
+    const CompactJob j = first ? j0 : j1;
+    const uint32_t seg = first ? blockIdx.x : blockIdx.x - j0.nseg;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint32_t i0 = seg * kCompactSeg + tid * kCompactPer;
+    uint32_t keep = 0;
+    if (i0 < j.n) {
+        uint32_t pi[kCompactPer], kv[kCompactPer];
+        if (j.order && i0 + kCompactPer <= j.n) {  // (a thread's entries are 32 bytes, aligned)
+            const uint4 a = *reinterpret_cast<const uint4*>(j.order + i0), b = *reinterpret_cast<const uint4*>(j.order + i0 + 4);
+            pi[0] = a.x; pi[1] = a.y; pi[2] = a.z; pi[3] = a.w; pi[4] = b.x; pi[5] = b.y; pi[6] = b.z; pi[7] = b.w;
+        } else {
+#pragma unroll
+            for (uint32_t u = 0; u < kCompactPer; ++u) {
+                const uint32_t i = min(i0 + u, j.n - 1);
+                pi[u] = j.order ? j.order[i] : i;
+            }
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < kCompactPer; ++u) kv[u] = j.key[pi[u]];
+#pragma unroll
+        for (uint32_t u = 0; u < kCompactPer; ++u)
+            if (i0 + u < j.n && (kv[u] & j.mask) != 0) keep |= 1u << u;
+    }
+    j.keep[seg * kCompactThreads + tid] = keep;
+    uint32_t c = __popc(keep);
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) c += __shfl_xor(c, m);
+    if (lane == 0) wsum[wid] = c;
+    __syncthreads();
+    if (tid == 0) j.segcnt[seg] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+__global__ __launch_bounds__(kCompactThreads) void compact_scatter_kernel(CompactJob j0, CompactJob j1) {
+    __shared__ uint32_t wsum[4], psum[4];
+    const bool first = blockIdx.x < j0.nseg;
+    const CompactJob j = first ? j0 : j1;
+    const uint32_t seg = first ? blockIdx.x : blockIdx.x - j0.nseg;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint32_t i0 = seg * kCompactSeg + tid * kCompactPer;
+    uint32_t part = 0;  // entries kept in the segments before this one
+    for (uint32_t k = tid; k < seg; k += kCompactThreads) part += j.segcnt[k];
+    uint32_t keep = j.keep[seg * kCompactThreads + tid];
+    const uint32_t c = __popc(keep);
+    uint32_t inc = c;
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        const uint32_t o = __shfl_up(inc, m);
+        if (lane >= (uint32_t)m) inc += o;
+        part += __shfl_xor(part, m);
+    }
+    if (lane == 63) wsum[wid] = inc;
+    if (lane == 0) psum[wid] = part;
+    __syncthreads();
+    const uint32_t base = psum[0] + psum[1] + psum[2] + psum[3];
+    uint32_t wbase = 0;
+    for (uint32_t k = 0; k < wid; ++k) wbase += wsum[k];
+    uint32_t dst = base + wbase + inc - c;
+    while (keep) {  // (a set bit is an entry below n)
+        const uint32_t i = i0 + (uint32_t)(__ffs(keep) - 1);
+        keep &= keep - 1;
+        j.list[dst++] = j.order ? j.order[i] : i;
+    }
+    if (seg == j.nseg - 1 && tid == 0) *j.nlist = base + wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+static hipError_t launch_compact(const CompactJob& a, const CompactJob* b, hipStream_t s) {
+    const CompactJob second = b ? *b : a;
+    const uint32_t grid = a.nseg + (b ? b->nseg : 0u);  // (one job: no block is beyond the first job's segments)
+    hipLaunchKernelGGL(compact_count_kernel, dim3(grid), dim3(kCompactThreads), 0, s, a, second);
+    hipLaunchKernelGGL(compact_scatter_kernel, dim3(grid), dim3(kCompactThreads), 0, s, a, second);
+    return hipGetLastError();
+}
+
+hipError_t launch_live_pairs(const ImageDev* imgs, const PairDev* pairs, uint32_t npairs, const uint32_t* accmask,
+                             const uint32_t* order, uint32_t norder, uint32_t* live, uint32_t* live_fwd,
+                             uint32_t* live_all, uint32_t* nlive, uint32_t* cand_cnt, uint32_t* pair_cnt,
+                             uint32_t* pair_off, uint32_t* scratch, hipStream_t s) {
+    if (npairs == 0) return memset_async(nlive, 0, 2 * sizeof(uint32_t), s);
+    hipLaunchKernelGGL(live_flag_kernel, dim3((npairs + 3) / 4), dim3(256), 0, s, imgs, pairs, npairs, accmask, live,
+                       cand_cnt, pair_cnt, pair_off);
+    const size_t third = live_scratch_words(npairs) / 3;
+    const CompactJob fwd = compact_job(order, norder, live, 2u, live_fwd, nlive, scratch);
+    const CompactJob all = compact_job(nullptr, npairs, live, 1u, live_all, nlive + 1, scratch + third);
+    return launch_compact(fwd, &all, s);
+}
+hipError_t launch_compact_order(const uint32_t* order, uint32_t norder, uint32_t npairs, const uint32_t* key, uint32_t* list,
+                                uint32_t* nlist, uint32_t* scratch, hipStream_t s) {
+    const CompactJob job = compact_job(order, norder, key, 0xFFFFFFFFu, list, nlist, scratch + 2 * (live_scratch_words(npairs) / 3));
+    return launch_compact(job, nullptr, s);
 }
 
 // Pair p's matches sit at src + 2 * src_off[p] (finalize_kernel's atomic-cursor order); move them to
@@ -932,13 +1097,13 @@ hipError_t launch_host_copy(void* dst_pinned, const void* src_dev, size_t bytes,
     return hipGetLastError();
 }
 
-hipError_t launch_finalize(const ImageDev* imgs, const PairDev* pairs, uint32_t npairs,
-                           const Top2* rowbuf, const Top2* colbuf, uint32_t* accmask,
+hipError_t launch_finalize(const ImageDev* imgs, const PairDev* pairs, uint32_t npairs, const uint32_t* list,
+                           const uint32_t* nlist, const Top2* rowbuf, const Top2* colbuf, uint32_t* accmask,
                            const float* acos_lut, FinalizeParams fp, uint32_t* cursor, uint32_t capacity,
                            uint32_t* pair_off, uint32_t* pair_cnt, uint32_t* matches, hipStream_t s) {
     if (npairs == 0) return hipSuccess;
-    hipLaunchKernelGGL(finalize_kernel, dim3(npairs), dim3(kFinalizeThreads), 0, s, imgs, pairs, rowbuf,
-                       colbuf, accmask, acos_lut, fp, cursor, capacity, pair_off, pair_cnt, matches);
+    hipLaunchKernelGGL(finalize_kernel, dim3(npairs), dim3(kFinalizeThreads), 0, s, imgs, pairs, list, nlist,
+                       rowbuf, colbuf, accmask, acos_lut, fp, cursor, capacity, pair_off, pair_cnt, matches);
     return hipGetLastError();
 }
 

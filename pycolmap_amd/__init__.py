@@ -28,6 +28,8 @@ try:  # the compiled host layer; absent only before `python -m pycolmap_amd.buil
     from ._undistortion import _undistort_plan, undistort_images  # noqa: F401
     from ._patch_match import PatchMatchController, PatchMatchOptions, read_array, write_array  # noqa: F401
     from ._fusion import FusionOptions, StereoFusion  # noqa: F401
+    from ._ba_covariance import (  # noqa: F401
+        BACovariance, BACovarianceOptions, BACovarianceOptionsParams, estimate_ba_covariance)
     _HOST_LAYER_ERROR = None
 except ImportError as _e:  # pragma: no cover - exercised only on an unbuilt tree
     _HOST_LAYER_ERROR = _e

@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "amc_estimate_rig_absolute_poses", "amc_rigpose_result_free",
     "amc_undistort_opts_default", "amc_undistort_camera", "amc_undistort_points", "amc_undistort_images",
     "amc_ba_opts_default", "amc_bundle_adjust", "amc_bundle_adjust_masked",
+    "amc_bacov_opts_default", "amc_ba_covariance", "amc_bacov_result_free",
     "amc_filter_opts_default", "amc_filter_points3d", "amc_filter_result_free",
     "amc_triobs_opts_default", "amc_triangulate_observations", "amc_triobs_result_free",
     "amc_complete_opts_default", "amc_complete_tracks", "amc_complete_result_free",
@@ -296,6 +297,62 @@ def ba_inputs(camera_models, camera_params, camera_const, image_cameras, qvec, t
         if a.size and (a.min() < 0 or a.max() > 0xffffffff):
             raise ValueError(f"bundle adjustment: {name} has an index outside 0 .. 2^32 - 1")
     return (models, prm, cc, icam.astype(np.uint32), q, t, pc, X, oi.astype(np.uint32), op.astype(np.uint32), xy)
+
+
+class BacovOpts(C.Structure):  # amc_bacov_opts (include/amc_bacov.h)
+    _fields_ = [("loss_function_type", C.c_int32), ("want_points", C.c_int32), ("want_matrix", C.c_int32),
+                ("reserved", C.c_int32), ("loss_function_scale", C.c_double), ("damping", C.c_double)]
+
+
+class BacovResult(C.Structure):  # amc_bacov_result
+    _fields_ = [("success", C.c_int32), ("reserved", C.c_int32), ("failed_column", C.c_int64),
+                ("num_columns", C.c_uint64), ("num_points", C.c_uint64), ("min_pivot_ratio", C.c_double),
+                ("column_owner", C.POINTER(C.c_uint32)), ("column_coord", C.POINTER(C.c_uint32)),
+                ("matrix", C.POINTER(C.c_double)), ("point_present", C.POINTER(C.c_uint8)),
+                ("point_cov", C.POINTER(C.c_double)), ("host_ms", C.c_double), ("device_ms", C.c_double),
+                ("kernel_ms", C.c_double), ("copy_ms", C.c_double), ("phase_ms", C.c_double * 5)]
+
+
+BACOV_MAX_COLUMNS = 8192  # AMC_BACOV_MAX_COLUMNS
+BACOV_PHASES = ("evaluation", "formation", "factor", "inverse", "points")
+
+
+def bacov_options(options=None) -> "BacovOpts":
+    """amc_bacov_opts at its defaults (no library needed) with the given fields replaced; loss_function_type may be a
+    name; an unknown field or a value the library would refuse raises ValueError."""
+    o = BacovOpts(0, 1, 1, 0, 1.0, 1e-8)
+    for k, v in (options or {}).items():
+        if k not in dict(BacovOpts._fields_) or k == "reserved":
+            raise ValueError(f"ba_covariance: unknown option {k!r}")
+        if k == "loss_function_type" and isinstance(v, str):
+            if v.upper() not in BA_LOSSES:
+                raise ValueError(f"ba_covariance: unknown loss function type {v!r}")
+            v = BA_LOSSES[v.upper()]
+        setattr(o, k, type(getattr(o, k))(v))
+    if not 0 <= o.loss_function_type <= 2:
+        raise ValueError(f"ba_covariance: loss_function_type {o.loss_function_type} outside 0 .. 2")
+    if not (o.loss_function_scale > 0 and np.isfinite(o.loss_function_scale)):
+        raise ValueError(f"ba_covariance: loss_function_scale {o.loss_function_scale} is not positive and finite")
+    if not (o.damping >= 0 and np.isfinite(o.damping)):
+        raise ValueError(f"ba_covariance: damping {o.damping} is not non-negative and finite")
+    return o
+
+
+def bacov_inputs(camera_models, camera_params, camera_const, image_cameras, qvec, tvec, pose_const, xyz, obs_image,
+                 obs_point, obs_xy, point_const=None):
+    """ba_inputs' arrays plus the point mask (P,) uint8 or None, for amc_ba_covariance; malformed input is a ValueError
+    naming ba_covariance."""
+    try:
+        arrays = ba_inputs(camera_models, camera_params, camera_const, image_cameras, qvec, tvec, pose_const, xyz,
+                           obs_image, obs_point, obs_xy)
+    except ValueError as e:
+        raise ValueError(f"ba_covariance: {e}") from None
+    mask = None
+    if point_const is not None:
+        mask = np.ascontiguousarray(np.asarray(point_const).reshape(-1) != 0, dtype=np.uint8)
+        if mask.size != arrays[7].shape[0]:
+            raise ValueError(f"ba_covariance: {arrays[7].shape[0]} points, {mask.size} point_const flags")
+    return arrays + (mask,)
 
 
 class FilterOpts(C.Structure):  # amc_filter_opts (include/amc_filter.h)
@@ -1283,6 +1340,14 @@ def load() -> C.CDLL:
         lib.amc_ba_opts_default.restype = None
         lib.amc_bundle_adjust.argtypes = [C.c_void_p, C.POINTER(BaProblem), C.POINTER(BaOpts), C.POINTER(BaResult)]
         lib.amc_bundle_adjust.restype = C.c_int
+    if hasattr(lib, "amc_ba_covariance"):
+        lib.amc_bacov_opts_default.argtypes = [C.POINTER(BacovOpts)]
+        lib.amc_bacov_opts_default.restype = None
+        lib.amc_ba_covariance.argtypes = [C.c_void_p, C.POINTER(BaProblem), C.c_void_p, C.POINTER(BacovOpts),
+                                          C.POINTER(BacovResult)]
+        lib.amc_ba_covariance.restype = C.c_int
+        lib.amc_bacov_result_free.argtypes = [C.POINTER(BacovResult)]
+        lib.amc_bacov_result_free.restype = None
     if hasattr(lib, "amc_bundle_adjust_masked"):
         lib.amc_bundle_adjust_masked.argtypes = [C.c_void_p, C.POINTER(BaProblem), C.c_void_p, C.POINTER(BaOpts),
                                                  C.POINTER(BaResult)]
@@ -1801,6 +1866,41 @@ class Context:
         out = {k: getattr(res, k) for k, _ in BaResult._fields_}
         out["termination"] = BA_TERMINATIONS[res.termination]
         out.update(camera_params=prm, qvec=q, tvec=t, xyz=X)
+        return out
+
+    def ba_covariance(self, camera_models, camera_params, camera_const, image_cameras, qvec, tvec, pose_const, xyz,
+                      obs_image, obs_point, obs_xy, options=None, point_const=None):
+        """amc_ba_covariance: the covariance of the variable columns of bundle_adjust's flat problem at the parameters
+        given; the arguments are bundle_adjust's, options a dict of amc_bacov_opts fields.
+        Nothing is refined and the inputs are not modified.  Returns a dict: success, failed_column, num_columns,
+        min_pivot_ratio, column_owner / column_coord (m,), and on success matrix (m, m) with want_matrix and
+        point_present (P,) bool / point_cov (P, 3, 3) with want_points (None otherwise); host_ms, device_ms,
+        kernel_ms, copy_ms and phase_ms by BACOV_PHASES."""
+        models, prm, cc, icam, q, t, pc, X, oi, op, xy, mask = bacov_inputs(
+            camera_models, camera_params, camera_const, image_cameras, qvec, tvec, pose_const, xyz, obs_image,
+            obs_point, obs_xy, point_const)
+        o = bacov_options(options)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        pb = BaProblem(models.size, ptr(models), ptr(prm), ptr(cc), icam.size, ptr(icam), ptr(q), ptr(t), ptr(pc),
+                       X.shape[0], ptr(X), oi.size, ptr(oi), ptr(op), ptr(xy))
+        res = BacovResult()
+        _check(self._lib.amc_ba_covariance(self._h, C.byref(pb), None if mask is None else ptr(mask), C.byref(o),
+                                           C.byref(res)))
+        try:
+            m, npts = int(res.num_columns), X.shape[0]
+            a = lambda p, k: np.ctypeslib.as_array(p, (max(k, 1),))[:k].copy()  # noqa: E731
+            out = {"success": bool(res.success), "failed_column": int(res.failed_column), "num_columns": m,
+                   "min_pivot_ratio": float(res.min_pivot_ratio), "column_owner": a(res.column_owner, m),
+                   "column_coord": a(res.column_coord, m), "matrix": None, "point_present": None, "point_cov": None,
+                   "host_ms": res.host_ms, "device_ms": res.device_ms, "kernel_ms": res.kernel_ms,
+                   "copy_ms": res.copy_ms, "phase_ms": dict(zip(BACOV_PHASES, res.phase_ms))}
+            if res.matrix:
+                out["matrix"] = a(res.matrix, m * m).reshape(m, m)
+            if res.point_present:
+                out["point_present"] = a(res.point_present, npts).astype(bool)
+                out["point_cov"] = a(res.point_cov, 9 * npts).reshape(npts, 3, 3)
+        finally:
+            self._lib.amc_bacov_result_free(C.byref(res))
         return out
 
     def filter_points3d(self, camera_models, camera_params, image_cameras, qvec, tvec, xyz, track_offsets, obs_image,

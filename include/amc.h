@@ -92,6 +92,7 @@ typedef struct amc_match_result {
                                  scan), HIP events on the stream */
     double cross_kernel_ms;   /* candidate selection + reverse scan of candidate columns */
     uint32_t match_kernel_launches;
+    uint32_t scan_run;        /* longest run of streamed images the call's forward scans kept X segments over (1: none) */
     void* _priv;
 } amc_match_result;
 

@@ -125,7 +125,7 @@ class MatchResult(C.Structure):
                 ("pairs_mfma", C.c_uint64), ("pairs_dot4", C.c_uint64), ("pairs_guided_grid", C.c_uint64),
                 ("device_ms", C.c_double), ("match_kernel_ms", C.c_double),
                 ("cross_kernel_ms", C.c_double),
-                ("match_kernel_launches", C.c_uint32), ("_priv", C.c_void_p)]
+                ("match_kernel_launches", C.c_uint32), ("scan_run", C.c_uint32), ("_priv", C.c_void_p)]
 
 
 class SiftOpts(C.Structure):  # amc_sift_opts (include/amc_sift.h)
@@ -2322,7 +2322,7 @@ class Context:
                      pairs_dot4=int(res.pairs_dot4), device_ms=float(res.device_ms),
                      match_kernel_ms=float(res.match_kernel_ms),
                      cross_kernel_ms=float(res.cross_kernel_ms),
-                     match_kernel_launches=int(res.match_kernel_launches))
+                     match_kernel_launches=int(res.match_kernel_launches), scan_run=int(res.scan_run))
         return offsets, matches, stats
 
     @staticmethod

@@ -167,7 +167,7 @@ struct amc_ctx {
     ScanAccept h_accept{};
     float accept_ratio = 0.f, accept_distance = 0.f;
     bool accept_valid = false;
-    uint32_t* d_scalars = nullptr;  // [0] cursor, [1] queue head, [2] maxsq scratch, [3] resolve errors, [4] stream overrun, [5] mfma items, [7] copy parts taken, [8] [9] [10] lengths of the live lists (forward order, pair order, reverse order)
+    uint32_t* d_scalars = nullptr;  // [0] cursor, [1] queue head, [2] maxsq scratch, [3] resolve errors, [4] stream overrun, [5] mfma items, [6] forward scan's runs, [7] copy parts taken, [8] [9] [10] lengths of the live lists (forward order, pair order, reverse order)
     // per-batch scratch of the match loop: a batch's cross-check chain (resolve, candidate selection, reverse scan,
     // finalize) is done before the next batch's forward scan writes the tables (match_impl)
     struct MatchScratch {
@@ -177,6 +177,7 @@ struct amc_ctx {
         // mfma work items: group cuts of the two queue orders, scratch of the packing kernels, the descriptors
         DevBuf<uint32_t> d_grp, d_grp2, d_seg_base, d_grp_segs, d_grp_item_base;
         DevBuf<SegDesc> d_segs;
+        DevBuf<uint32_t> d_run_base, d_run_items;  // the forward scan's run table (match_mfma.hip, "Runs")
         DevBuf<Top2> d_rowbuf, d_colbuf;
         DevBuf<uint32_t> d_accmask;  // one accept bit per row-table entry (mfma pairs)
         DevBuf<GuidedDev> d_guided;  // guided matching: one filter model per pair of the batch
@@ -187,7 +188,7 @@ struct amc_ctx {
         void release_all() {
             d_pairs.release(); d_work.release(); d_order.release(); d_order2.release();
             d_grp.release(); d_grp2.release(); d_seg_base.release(); d_grp_segs.release();
-            d_grp_item_base.release(); d_segs.release();
+            d_grp_item_base.release(); d_segs.release(); d_run_base.release(); d_run_items.release();
             d_rowbuf.release(); d_colbuf.release(); d_accmask.release(); d_guided.release();
             d_pair_off.release(); d_pair_cnt.release(); d_matches.release();
             d_cand_cnt.release(); d_candbuf.release();
@@ -196,7 +197,7 @@ struct amc_ctx {
         }
         void release_large() {  // (amc_ctx_trim)
             d_rowbuf.release(); d_colbuf.release(); d_accmask.release(); d_matches.release(); d_candbuf.release();
-            d_segs.release(); d_seg_base.release();
+            d_segs.release(); d_seg_base.release(); d_run_items.release();
         }
     };
     MatchScratch ms;

@@ -426,9 +426,16 @@ struct CopyJob {
     unsigned long long n16 = 0;
     uint32_t parts = 0, pad_ = 0;
 };
+// run_items / run_len / nruns_dev: the forward scan's run table (launch_build_runs), or nullptr: every item is a run.
 hipError_t launch_match_mfma(int mode, const SegDesc* segs, const uint32_t* nitems_dev, uint32_t max_items,
                        uint32_t* queue_head, uint32_t* accmask, const ScanAccept* accept_dev, hipStream_t s,
-                       const CopyJob& job = CopyJob(), uint32_t* copy_head = nullptr);
+                       const CopyJob& job = CopyJob(), uint32_t* copy_head = nullptr,
+                       const uint32_t* run_items = nullptr, uint32_t run_len = 1, const uint32_t* nruns_dev = nullptr);
+// Runs of a forward scan (match_mfma.hip, "Runs"), behind launch_build_segments(0, ...) on the same stream: the groups
+// in blocks of R (2 .. 8) consecutive ones, run (block, t) = item t of each group of the block.  run_items holds
+// R entries per run - at most R x the launch's items - and run_base one entry per block; *nruns_dev = the runs.
+hipError_t launch_build_runs(const SegDesc* segs, const uint32_t* grp_segs, const uint32_t* grp_item_base, uint32_t ngroups,
+                       uint32_t R, uint32_t* run_base, uint32_t* run_items, uint32_t* nruns_dev, hipStream_t s);
 
 // The live-pair lists of a batch (match_common.hip).  Behind the scans nearly every pair of an exhaustive job has
 // nothing accepted; the per-pair kernels of the cross-check chain keep their grids (one workgroup per pair that COULD be

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "amc_ctx.h"
+#include "scan_run.h"
 
 using namespace amc;
 
@@ -63,6 +64,8 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
     const char* const d2h_env = std::getenv("AMC_D2H");  // "memcpy" / "stream": how a batch's matches reach the host (below)
     // (smaller copies are not worth a scan's prologue; the tests take the path with small inputs)
     const size_t fuse_min_bytes = (size_t)env_int("AMC_D2H_FUSE_MIN_BYTES", 1 << 20, 0, std::numeric_limits<long long>::max());
+    // the forward scan's run length (scan_run.h): 0 auto, 1 off, 2 / 4 / 8 forced (test and A/B hook)
+    const int scan_run_env = (int)env_int("AMC_SCAN_RUN", 0, 0, 8);
     const int hook_split_mode = (int)env_int("AMC_HOOK_SPLIT", 1, 0, 2);  // 0: off; 2: also calls of a few pairs (the tests' way to the path)
     const auto wall0 = std::chrono::steady_clock::now();
     double t_prepare = 0.0, t_collect = 0.0, t_enqueue = 0.0, t_scatter = 0.0;
@@ -159,7 +162,10 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
 
     uint64_t num_dist = 0, n_mfma = 0, n_dot4 = 0, n_grid = 0;
     double kernel_ms = 0.0, cross_ms = 0.0;
-    uint32_t kernel_launches = 0;
+    uint32_t kernel_launches = 0, scan_run_max = 0;
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+    const size_t scan_workgroups = 2 * (size_t)cus;  // (match_mfma.hip: two workgroups share a CU)
 
     int rc = AMC_OK;
     auto hc = [&](hipError_t e, const char* what) {
@@ -183,6 +189,7 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
         int set = 0;
         uint32_t total = 0;
         bool grouped_resolve = true;
+        int run = 1;  // forward scan: consecutive streamed images that share resident X segments (scan_run.h)
     };
     // rows of image 1 (padded) from pair i to the end of the call: how much is left when a batch is carved
     // (a running total, not an array: a loop-closure call has 10^7 pairs, and 80 MB of suffix sums cost more than the
@@ -355,6 +362,10 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
             c->h_grp[k].p[b.ngrp] = (uint32_t)nord;
             if (o.cross_check) b.ngrp2 = nimg1;  // (the cuts themselves: build_reverse_order)
             b.seg_cap = std::max(seg1 + kSegsPerItem * b.ngrp, o.cross_check ? seg2 + kSegsPerItem * b.ngrp2 : 0);
+            const uint32_t* ord = c->h_order[k].p;
+            b.run = choose_scan_run_by([hp, ord](size_t q) { return hp[ord[q]].slot1; }, c->h_grp[k].p, b.ngrp,
+                                       seg1 / kSegsPerItem, scan_workgroups, scan_run_env);
+            scan_run_max = std::max(scan_run_max, (uint32_t)b.run);
         }
         b.nwork_grid = 0;
         if (nwork) {
@@ -388,6 +399,10 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
         const int k = b.set;
         amc_ctx::MatchScratch& S = c->ms;
         const size_t nb = b.nb, nord = b.nord, nwork = b.nwork;
+        // the run table (match_mfma.hip, "Runs"): a run per block of b.run groups and item position, at most as many
+        // runs as the launch has items (a block's runs are the items of its longest group), b.run entries each
+        const size_t run_blocks = b.run > 1 ? (b.ngrp + b.run - 1) / b.run : 0;
+        const size_t run_entries = b.run > 1 ? (b.seg_cap / kSegsPerItem + 1) * b.run : 0;
         // device scratch only ever grows; growing frees the old allocation, so drain the stream first
         const bool grow = S.d_pairs.cap < nb || S.d_order.cap < nb || S.d_order2.cap < nb ||
                           S.d_rowbuf.cap < b.top_rows || S.d_colbuf.cap < b.top_cols ||
@@ -397,7 +412,8 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
                           S.d_live_scan.cap < live_scratch_words(nb) ||
                           S.d_work.cap < nwork || (geoms && S.d_guided.cap < nb) || S.d_segs.cap < b.seg_cap ||
                           S.d_seg_base.cap < nord || S.d_grp.cap < b.ngrp + 1 || S.d_grp2.cap < b.ngrp2 + 1 ||
-                          S.d_grp_segs.cap < std::max(b.ngrp, b.ngrp2) || S.d_grp_item_base.cap < std::max(b.ngrp, b.ngrp2);
+                          S.d_grp_segs.cap < std::max(b.ngrp, b.ngrp2) || S.d_grp_item_base.cap < std::max(b.ngrp, b.ngrp2) ||
+                          S.d_run_base.cap < run_blocks || S.d_run_items.cap < run_entries;
         if (grow && !sync_batch_streams("sync before growing device scratch")) return false;
         if (!hc(S.d_pairs.ensure(nb), "dev pairs") || !hc(S.d_order.ensure(nb), "dev order") ||
             !hc(S.d_order2.ensure(nb), "dev order2") ||
@@ -413,7 +429,8 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
             !hc(S.d_segs.ensure(b.seg_cap), "segment descriptors") || !hc(S.d_seg_base.ensure(nord), "segment bases") ||
             !hc(S.d_grp.ensure(b.ngrp + 1), "group cuts") || !hc(S.d_grp2.ensure(b.ngrp2 + 1), "group cuts") ||
             !hc(S.d_grp_segs.ensure(std::max(b.ngrp, b.ngrp2)), "group segments") ||
-            !hc(S.d_grp_item_base.ensure(std::max(b.ngrp, b.ngrp2)), "group items"))
+            !hc(S.d_grp_item_base.ensure(std::max(b.ngrp, b.ngrp2)), "group items") ||
+            !hc(S.d_run_base.ensure(run_blocks), "run bases") || !hc(S.d_run_items.ensure(run_entries), "run table"))
             return false;
         bool okq = hc(hipMemcpyAsync(S.d_pairs.p, c->h_pairs[k].p, nb * sizeof(PairDev),
                                      hipMemcpyHostToDevice, st), "H2D pairs") &&
@@ -437,6 +454,10 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
             !hc(launch_build_segments(0, c->d_imgs.p, S.d_pairs.p, S.d_order.p, S.d_grp.p, (uint32_t)b.ngrp,
                                       S.d_cand_cnt.p, S.d_candbuf.p, S.d_rowbuf.p, S.d_seg_base.p, S.d_grp_segs.p,
                                       S.d_grp_item_base.p, S.d_segs.p, c->d_scalars + 5, st), "segment packing"))
+            return false;
+        if (nord && b.run > 1 &&  // ... line item t of b.run consecutive streamed images up behind each other ...
+            !hc(launch_build_runs(S.d_segs.p, S.d_grp_segs.p, S.d_grp_item_base.p, (uint32_t)b.ngrp, (uint32_t)b.run,
+                                  S.d_run_base.p, S.d_run_items.p, c->d_scalars + 6, st), "run packing"))
             return false;
         if (!hc(hipEventRecord(c->bev[k][0], st), "event record")) return false;
         if (nord) {  // ... and scan them (the events bracket the scan kernel alone: bench.py's roofline leg)
@@ -462,7 +483,8 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
                 pending.set = -1;
             }
             if (!hc(launch_match_mfma(0, S.d_segs.p, c->d_scalars + 5, (uint32_t)std::min<size_t>(b.seg_cap, 0xFFFFFFFFu),
-                                      c->d_scalars + 1, S.d_accmask.p, c->d_accept, st, job, c->d_scalars + 7), "forward scan"))
+                                      c->d_scalars + 1, S.d_accmask.p, c->d_accept, st, job, c->d_scalars + 7,
+                                      b.run > 1 ? S.d_run_items.p : nullptr, (uint32_t)b.run, c->d_scalars + 6), "forward scan"))
                 return false;
             // that batch's matches are on the host when this scan is done
             if (done_set >= 0 && !hc(hipEventRecord(c->bev[done_set][4], st), "event record")) return false;
@@ -736,6 +758,7 @@ int amc::match_impl(amc_ctx* c, const uint32_t* slot1, const uint32_t* slot2, si
     out->device_ms = total_ms;
     out->match_kernel_ms = kernel_ms;
     out->match_kernel_launches = kernel_launches;
+    out->scan_run = scan_run_max;
     out->cross_kernel_ms = cross_ms;
     out->_priv = priv;
     c->last_hook_ms = t_hook;

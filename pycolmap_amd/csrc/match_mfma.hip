@@ -53,15 +53,17 @@
 // fills a workgroup; and the reverse scan's candidate lists (known only on the
 // device: the packing kernels read cand_cnt) are packed just as tightly.
 //
-// Shape.  One workgroup per item (dynamic queue, one ticket per item, taken at the top of the item before; items in
-// Y order so co-resident workgroups stream the same image out of L2; the next item's descriptor is fetched while the
-// current one is scanned): 256 threads, a segment (eight resident 16-row X tiles) per wave, one wave per SIMD - and
+// Shape.  One workgroup per item (dynamic queue; items in Y order so co-resident workgroups stream the same image out
+// of L2; the next item's descriptor is fetched while the current one is scanned).  The queue's ticket is a RUN of up to
+// R items - item t of R consecutive streamed images, which in an exhaustive job hold the same X segments: an item
+// marked so in the run table keeps its X rows in the registers instead of fetching them again ("Runs" below; R = 1 and
+// no table: a ticket is an item).  256 threads, a segment (eight resident 16-row X tiles) per wave, one wave per SIMD - and
 // TWO such workgroups on every CU, each popping its own items, so that every SIMD still holds two waves.  They are
 // independent: at an item boundary all four waves of a workgroup leave the loop together (they wait for the next
 // item's chunks and X rows, decode, and meet at two barriers: 6.7 % of an item's clocks, profiles/boundary/), and
 // the partner workgroup's wave then has the SIMD to itself instead of the matrix pipe of the whole CU standing idle.
 // A chunk crossing's barrier joins four waves on four SIMDs.  Both workgroups must fit: at most 256 registers per lane
-// (amdgpu_waves_per_eu pins it; MODE 0 compiles to 222 VGPRs, MODE 1 to 192, without scratch - check
+// (amdgpu_waves_per_eu pins it; MODE 0 compiles to 250 VGPRs, MODE 1 to 194, without scratch - check
 // -Rpass-analysis=kernel-resource-usage after every change, profiles/scanloop/kernel_resource_usage.txt) and at most
 // 80 KB of LDS (66 KB, ONE __shared__ object); launch_match_mfma asks the runtime.
 // Taking the ticket two items ahead and warming the next item's X rows in L2 were both built and measured, and
@@ -102,6 +104,9 @@ constexpr int kW = kSegsPerItem;        // waves per workgroup: a segment each
 constexpr int kWGPerCU = 2;             // workgroups that share a CU, one wave of each on every SIMD
 constexpr int kXT = kSegRows / 16;      // resident 16-row X tiles per wave
 constexpr int kKeyShift = 7, kKeyCarried = 127;
+// run table entries (launch_build_runs): an item index, with kRunSameX if the item's four X segments are those of the
+// run's previous item; kRunNone where a streamed image has no such item
+constexpr uint32_t kRunSameX = 0x80000000u, kRunNone = 0xFFFFFFFFu;
 
 // single LDS object (a second __shared__ object de-pipelines the DMA waits).  A ring of FOUR chunk buffers: while
 // chunk c is scanned, chunks c+1 and c+2 have landed (or are landing) and chunk c+3 is being fetched into the buffer
@@ -150,14 +155,15 @@ struct YFrag {
 #ifdef AMC_SCAN_STAMPS
 // Diagnostic build only (tools/scan_stamps.hip includes this file with the macro; libamc.so is compiled without it and
 // holds none of this): s_memtime stamps around the places where a wave's MFMA stream stops, summed per wave in scalar
-// registers and stored - running sums, lane 0 - behind every item.  Per (MODE, workgroup, wave) eight dwords, over the
+// registers and stored - running sums, lane 0 - behind every item.  Per (MODE, workgroup, wave) twelve dwords, over the
 // items that had a successor in the same workgroup:
 //   [0] clocks from arriving at a chunk crossing's s_waitcnt to leaving its s_barrier   [1] clocks from the
 //   __syncthreads() that ends an item's scan to the first MFMA of the next item   [2] clocks from an item's first MFMA
 //   to the next item's   [3] such items   [4] those of them this wave had rows in
-// and for the workgroup's last item: [5] as [0]   [6] first MFMA to the end of the epilogue   [7] 1
-constexpr int kStampMaxWG = 1024;
-__device__ uint32_t g_scan_stamps[2 * kStampMaxWG * kSegsPerItem * 8];
+// for the workgroup's last item: [5] as [0]   [6] first MFMA to the end of the epilogue   [7] 1
+// and of [1] and [3] the part of the successors that kept the X rows (kRunSameX): [8] clocks   [9] items
+constexpr int kStampMaxWG = 1024, kStampDwords = 12;
+__device__ uint32_t g_scan_stamps[2 * kStampMaxWG * kSegsPerItem * kStampDwords];
 #define AMC_STAMP() ((uint32_t)__builtin_amdgcn_s_memtime())
 #endif
 
@@ -187,9 +193,10 @@ __device__ __noinline__ __attribute__((used)) void copy_part(const uint4* __rest
 // and then only one workgroup fits a CU (launch_match_mfma checks the occupancy it gets).
 template <int MODE>
 __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kWGPerCU, kWGPerCU)))
-void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restrict__ nitems_p,
+void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restrict__ nruns_p,
                        uint32_t* __restrict__ queue_head, uint32_t* __restrict__ accmask,
-                       const ScanAccept* __restrict__ accept, CopyJob job, uint32_t* __restrict__ copy_head) {
+                       const ScanAccept* __restrict__ accept, CopyJob job, uint32_t* __restrict__ copy_head,
+                       const uint32_t* __restrict__ run_items, int run_len) {
     static_assert(kChunkBytes / 1024 == kW * kYS, "a chunk splits into 1 KiB DMA pieces, one per wave and step");
     static_assert(kBN * 4 == 512, "a chunk's rs128 block is half a wave's DMA");
     __shared__ __attribute__((aligned(16))) char smem[kLdsBytes];
@@ -212,13 +219,31 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
                           job.n16 * (part + 1) / job.parts, tid, 64 * kW);
         }
     }
-    const uint32_t nitems = *nitems_p;
+    const uint32_t nruns = *nruns_p;  // (without a run table: the items, every one a run of its own)
     const ScanAccept sa = *accept;  // twelve scalar registers for the whole kernel (re-read per row block it is four dependent scalar-cache round trips per X tile)
 
-    // the wave's descriptor of item q, one dword per lane (lanes 16.. hold 0)
-    auto load_desc = [&](uint32_t q) -> int {
+    // the entries of run r, one per lane: lanes run_len.. hold "none", and so does every lane of a run past the end
+    auto load_run = [&](uint32_t r) -> uint32_t {
+        uint32_t v = kRunNone;
+        if (r < nruns) {
+            if (run_items) {  // (wave-uniform: a kernel argument)
+                if (lane < run_len) v = run_items[(size_t)r * run_len + lane];
+            } else if (lane == 0) {
+                v = r;
+            }
+        }
+        return v;
+    };
+    // the first entry of a run behind position `after` (-1: from its start) that is an item: its position, or -1
+    auto next_entry = [&](uint32_t rv, int after) -> int {
+        const unsigned long long m = __ballot(rv != kRunNone) & (~0ull << (after + 1));
+        return m ? __builtin_ctzll(m) : -1;
+    };
+    // the wave's descriptor of the item of run entry e, one dword per lane (lanes 16.. hold 0)
+    auto load_desc = [&](uint32_t e) -> int {
         int v = 0;
-        if (q < nitems && lane < 16) v = reinterpret_cast<const int*>(segs + (size_t)q * kSegsPerItem + wid)[lane];
+        if (e != kRunNone && lane < 16)
+            v = reinterpret_cast<const int*>(segs + (size_t)(e & ~kRunSameX) * kSegsPerItem + wid)[lane];
         return v;
     };
     auto dword = [&](int dv, int f) -> int { return __builtin_amdgcn_readlane(dv, f); };
@@ -334,23 +359,51 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
             btile[xt] = -1;
         }
     };
+    // an item whose X rows are the ones this wave already holds (a run entry with kRunSameX): xf and xterm stay, the
+    // top-2 state starts over as load_x starts it
+    auto reset_x = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int xt = 0; xt < kXT; ++xt) {
+            best[xt] = ((-xterm[xt]) << kKeyShift) | kKeyCarried;
+            sec[xt] = best[xt];
+            btile[xt] = -1;
+        }
+    };
 
 #ifdef AMC_SCAN_STAMPS
-    uint32_t st_a = 0, st_first = 0, st_end = 0, st_sum[5] = {0, 0, 0, 0, 0};
-    bool st_prev = false, st_prev_active = false;
-    uint32_t* const st_slot = g_scan_stamps + ((size_t)(MODE * kStampMaxWG + min((int)blockIdx.x, kStampMaxWG - 1)) * kW + wid) * 8;
+    uint32_t st_a = 0, st_first = 0, st_end = 0, st_sum[5] = {0, 0, 0, 0, 0}, st_kept[2] = {0, 0};
+    bool st_prev = false, st_prev_active = false, st_keep_x = false;
+    uint32_t* const st_slot = g_scan_stamps + ((size_t)(MODE * kStampMaxWG + min((int)blockIdx.x, kStampMaxWG - 1)) * kW + wid) * kStampDwords;
 #endif
+    // Runs.  A ticket is a run: up to run_len items that follow each other in this workgroup, item t of consecutive
+    // streamed images, so that an entry marked kRunSameX finds its X rows in the registers.  The workgroup holds the
+    // entries of its run (rv), of its next run (rvn) and - in flight from the first item of a run on - of the run after
+    // that (rvn2): the next item's descriptor can then always be fetched at the top of an item, whichever run it is in.
+    // Without a table a ticket IS its entry, nothing is in flight for it and the queue is one ticket ahead, not two:
+    // the items are handed out exactly as they were before there were runs (a reverse scan has one or two items per
+    // workgroup, and a workgroup that holds a second ticket while another idles is what it cannot afford).
+    const bool table = MODE == 0 && run_items != nullptr;  // (wave-uniform)
+    uint32_t rv = kRunNone, rvn, rvn2 = kRunNone;
     if (tid == 0) *s_q = atomicAdd(queue_head, 1u);
     __syncthreads();
-    uint32_t q = *s_q;
-    int dv = load_desc(q);
-    if (q < nitems) {
+    rvn = load_run(*s_q);
+    if (table) {
+        __syncthreads();
+        if (tid == 0) *s_q = atomicAdd(queue_head, 1u);
+        __syncthreads();
+        rvn2 = load_run(*s_q);
+    }
+    int kpos = next_entry(rvn, -1);  // (a run of the table holds an item; a ticket past the end holds none)
+    uint32_t e = kpos >= 0 ? (uint32_t)__builtin_amdgcn_readlane((int)rvn, kpos) : kRunNone;
+    bool first = true;  // this item starts a run: the entries move up and a ticket is taken
+    int dv = load_desc(e);
+    if (e != kRunNone) {
         stage_head(dv);
         if (dword(dv, kDCnt) > 0) load_x(dv);
     }
     __syncthreads();  // everyone has read the slot before it is rewritten
 
-    while (q < nitems) {
+    while (e != kRunNone) {
         // chunks 0 .. 2 of this item's Y image are on their way and the X fragments are being loaded (issued by
         // the previous iteration or the prologue)
         const char* yprep = dptr(dv, kDYprep);  // the same in every descriptor of the item
@@ -361,7 +414,7 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
         // at a 128-row chunk leaves 64 padded rows per image on average).
         const int nchunks = (dword(dv, kDYrows) + kBN - 1) / kBN;
         const bool active = dword(dv, kDCnt) > 0;  // wave-uniform
-        if (tid == 0) *s_q = atomicAdd(queue_head, 1u);  // the next item, behind the loads already in flight
+        if (first && tid == 0) *s_q = atomicAdd(queue_head, 1u);  // the run after the next (no table: the next item), behind the loads already in flight
 
         i32x4 acc[2][2];
         // 19 VALU for 32 outputs: the scan only keeps, per lane, the top two of the per-unit
@@ -445,8 +498,22 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
         YFrag y0, y1;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // chunk 0 and this item's X rows landed
         __syncthreads();
-        const uint32_t qn = *s_q;
-        const int dvn = load_desc(qn);  // in flight during the scan
+        if (first) {  // (everything this wave loaded has landed)
+            rv = rvn;
+            if (table) {
+                rvn = rvn2;
+                rvn2 = load_run(*s_q);  // in flight during the scan
+            } else {
+                rvn = load_run(*s_q);  // (no load: the ticket itself)
+            }
+        }
+        // the next item: the run's next entry, or the next run's first
+        int kn = next_entry(rv, kpos);
+        const bool same_run = kn >= 0;
+        if (!same_run) kn = next_entry(rvn, -1);
+        const uint32_t en = kn < 0 ? kRunNone : (uint32_t)__builtin_amdgcn_readlane((int)(same_run ? rv : rvn), kn);
+        const bool keep_x = MODE == 0 && same_run && (en & kRunSameX) != 0;
+        const int dvn = load_desc(en);  // in flight during the scan
 #ifdef AMC_SCAN_STAMPS
         {
             const uint32_t now = AMC_STAMP();
@@ -456,9 +523,15 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
                 st_sum[2] += now - st_first;
                 st_sum[3] += 1;
                 st_sum[4] += st_prev_active ? 1 : 0;
+                if (st_keep_x) {  // this item kept the X rows of the one before
+                    st_kept[0] += now - st_end;
+                    st_kept[1] += 1;
+                }
                 if (lane == 0) {
 #pragma unroll
                     for (int k = 0; k < 5; ++k) st_slot[k] = st_sum[k];
+                    st_slot[8] = st_kept[0];
+                    st_slot[9] = st_kept[1];
                 }
             }
             st_a = 0;
@@ -596,9 +669,12 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
             asm volatile("v_mov_b32 %0, %1" : "=v"(et[xt]) : "v"(btile[xt]));
             ex[xt] = xterm[xt];
         }
-        if (qn < nitems) {
+        if (en != kRunNone) {
             stage_head(dvn);
-            if (dword(dvn, kDCnt) > 0) load_x(dvn);
+            if (dword(dvn, kDCnt) > 0) {
+                if (keep_x) reset_x();
+                else load_x(dvn);
+            }
         }
         if (active) {
             const int cnt = dword(dv, kDCnt);
@@ -655,13 +731,18 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
             }
         }
 #ifdef AMC_SCAN_STAMPS
-        if (qn >= nitems && lane == 0) {  // the workgroup's last item
+        if (en == kRunNone && lane == 0) {  // the workgroup's last item
             st_slot[5] = st_a;
             st_slot[6] = AMC_STAMP() - st_first;
             st_slot[7] = 1;
         }
 #endif
-        q = qn;
+#ifdef AMC_SCAN_STAMPS
+        st_keep_x = keep_x;
+#endif
+        e = en;
+        kpos = kn;
+        first = !same_run;
         dv = dvn;
     }
 }
@@ -834,9 +915,125 @@ hipError_t launch_build_segments(int mode, const ImageDev* imgs, const PairDev* 
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Runs (forward scan only).  In an exhaustive job item t of streamed image j and item t of image j + 1 hold the same
+// four X segments, for every X image below j - and a workgroup that scans them one after the other fetches those 64 KB
+// once.  The groups of the forward order are taken in BLOCKS of R consecutive groups; run (block, t) lists item t of
+// each group of the block that has one, in group order, "none" (kRunNone) elsewhere: run_items[nruns x R].  The order
+// only makes shared rows frequent.  Whether an entry may keep the X rows of the entry before it is read off the
+// descriptors themselves: kRunSameX is set where xprep, xrs and cnt agree in all four descriptors of the two items and
+// neither has a candidate list - whatever the pair list looks like, a wrong order costs speed and never a result.
+// The launch's LAST block (of kRunTailBlocks or more) is written as runs of one item each, in item order: a run is
+// what a workgroup can be left alone with when the queue is empty, and the launch ends on items as it did before.
+// ---------------------------------------------------------------------------------------------------
+constexpr uint32_t kRunTailBlocks = 8;
+__device__ __forceinline__ bool run_block_is_single(uint32_t b, uint32_t nblocks) {
+    return nblocks >= kRunTailBlocks && b + 1 == nblocks;
+}
+// one block: run_base = exclusive scan, over the blocks, of the largest item count among a block's groups; the total
+__global__ __launch_bounds__(1024) void run_scan_kernel(const uint32_t* __restrict__ grp_segs, uint32_t ngroups, uint32_t R,
+                                                        uint32_t* __restrict__ run_base, uint32_t* __restrict__ nruns_out) {
+    __shared__ uint32_t wsum[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint32_t nblocks = (ngroups + R - 1) / R;
+    uint32_t running = 0;
+    for (uint32_t base = 0; base < nblocks; base += 1024) {
+        const uint32_t b = base + tid;
+        uint32_t s = 0;
+        if (b < nblocks)
+            for (uint32_t g = b * R; g < min(b * R + R, ngroups); ++g) {
+                const uint32_t n = (grp_segs[g] + kSegsPerItem - 1) / kSegsPerItem;
+                s = run_block_is_single(b, nblocks) ? s + n : max(s, n);
+            }
+        uint32_t inc = s;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const uint32_t o = __shfl_up(inc, m);
+            if (lane >= (uint32_t)m) inc += o;
+        }
+        if (lane == 63) wsum[wid] = inc;
+        __syncthreads();
+        uint32_t wbase = 0, total = 0;
+        for (uint32_t k = 0; k < 16; ++k) {
+            if (k < wid) wbase += wsum[k];
+            total += wsum[k];
+        }
+        if (b < nblocks) run_base[b] = running + wbase + inc - s;
+        running += total;
+        __syncthreads();
+    }
+    if (tid == 0) *nruns_out = running;
+}
+
+// the X side of two items is the same rows, segment for segment (and read as rows, not through a candidate list)
+__device__ __forceinline__ bool items_share_x(const SegDesc* __restrict__ a, const SegDesc* __restrict__ b) {
+    bool same = true;
+    for (int w = 0; w < kSegsPerItem; ++w)
+        same = same && a[w].xprep == b[w].xprep && a[w].xrs == b[w].xrs && a[w].cnt == b[w].cnt && a[w].list == nullptr &&
+               b[w].list == nullptr;
+    return same;
+}
+
+// kFillY 256-thread blocks per block of R groups (behind seg_fill_kernel: it reads the descriptors)
+constexpr uint32_t kRunMax = 8;
+__global__ __launch_bounds__(256) void run_fill_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restrict__ grp_segs,
+                                                       const uint32_t* __restrict__ grp_item_base, uint32_t ngroups,
+                                                       uint32_t R, const uint32_t* __restrict__ run_base,
+                                                       uint32_t* __restrict__ run_items) {
+    __shared__ uint32_t s_items[kRunMax], s_base[kRunMax];
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
+    if (tid < R) {
+        const uint32_t g = b * R + tid;
+        s_items[tid] = g < ngroups ? (grp_segs[g] + kSegsPerItem - 1) / kSegsPerItem : 0u;
+        s_base[tid] = g < ngroups ? grp_item_base[g] : 0u;
+    }
+    __syncthreads();
+    uint32_t m = 0;
+    for (uint32_t p = 0; p < R; ++p) m = max(m, s_items[p]);
+    uint32_t* out = run_items + (size_t)run_base[b] * R;
+    if (run_block_is_single(b, gridDim.x)) {  // a run per item, group after group
+        uint32_t total = 0;
+        for (uint32_t p = 0; p < R; ++p) total += s_items[p];
+        for (uint32_t idx = blockIdx.y * 256 + tid; idx < total * R; idx += 256 * gridDim.y) {
+            uint32_t t = idx / R, p = 0;
+            const uint32_t pos = idx - t * R;
+            while (t >= s_items[p]) t -= s_items[p++];  // (t < total: p stays below R)
+            out[idx] = pos == 0 ? s_base[p] + t : kRunNone;
+        }
+        return;
+    }
+    for (uint32_t idx = blockIdx.y * 256 + tid; idx < m * R; idx += 256 * gridDim.y) {
+        const uint32_t t = idx / R, p = idx - t * R;
+        uint32_t entry = kRunNone;
+        if (t < s_items[p]) {
+            entry = s_base[p] + t;
+            int pp = (int)p - 1;  // the run's previous entry that is an item
+            while (pp >= 0 && t >= s_items[pp]) --pp;
+            if (pp >= 0 && items_share_x(segs + (size_t)entry * kSegsPerItem, segs + (size_t)(s_base[pp] + t) * kSegsPerItem))
+                entry |= kRunSameX;
+        }
+        out[idx] = entry;
+    }
+}
+
+hipError_t launch_build_runs(const SegDesc* segs, const uint32_t* grp_segs, const uint32_t* grp_item_base, uint32_t ngroups,
+                             uint32_t R, uint32_t* run_base, uint32_t* run_items, uint32_t* nruns_dev, hipStream_t s) {
+    if (R < 2 || R > kRunMax) return hipErrorInvalidValue;
+    if (ngroups == 0) return memset_async(nruns_dev, 0, sizeof(uint32_t), s);
+    const uint32_t nblocks = (ngroups + R - 1) / R;
+    hipLaunchKernelGGL(run_scan_kernel, dim3(1), dim3(1024), 0, s, grp_segs, ngroups, R, run_base, nruns_dev);
+    hipLaunchKernelGGL(run_fill_kernel, dim3(nblocks, kFillY), dim3(256), 0, s, segs, grp_segs, grp_item_base, ngroups, R,
+                       run_base, run_items);
+    return hipGetLastError();
+}
+
 hipError_t launch_match_mfma(int mode, const SegDesc* segs, const uint32_t* nitems_dev, uint32_t max_items,
                              uint32_t* queue_head, uint32_t* accmask, const ScanAccept* accept_dev, hipStream_t s,
-                             const CopyJob& job_in, uint32_t* copy_head) {
+                             const CopyJob& job_in, uint32_t* copy_head, const uint32_t* run_items, uint32_t run_len,
+                             const uint32_t* nruns_dev) {
+    if (run_items && (mode != 0 || run_len < 2 || run_len > kRunMax || !nruns_dev)) return hipErrorInvalidValue;
+    const uint32_t* const ntickets = run_items ? nruns_dev : nitems_dev;
+    const int rl = run_items ? (int)run_len : 1;
     if (max_items == 0) return hipSuccess;  // (the caller checks: a job is only handed to a launch that happens)
     CopyJob job = (mode == 0 && copy_head) ? job_in : CopyJob();
     // The persistent workgroups pop from these two counters: nothing is launched unless both were reset.
@@ -868,11 +1065,11 @@ hipError_t launch_match_mfma(int mode, const SegDesc* segs, const uint32_t* nite
     if (job.parts > grid) job.parts = grid;  // every part needs a workgroup
     if ((e = memset_async(queue_head, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
     if (mode == 0)
-        hipLaunchKernelGGL((match_mfma_kernel<0>), dim3(grid), dim3(64 * kW), 0, s, segs, nitems_dev, queue_head,
-                           accmask, accept_dev, job, copy_head);
+        hipLaunchKernelGGL((match_mfma_kernel<0>), dim3(grid), dim3(64 * kW), 0, s, segs, ntickets, queue_head,
+                           accmask, accept_dev, job, copy_head, run_items, rl);
     else
-        hipLaunchKernelGGL((match_mfma_kernel<1>), dim3(grid), dim3(64 * kW), 0, s, segs, nitems_dev, queue_head,
-                           accmask, accept_dev, job, copy_head);
+        hipLaunchKernelGGL((match_mfma_kernel<1>), dim3(grid), dim3(64 * kW), 0, s, segs, ntickets, queue_head,
+                           accmask, accept_dev, job, copy_head, run_items, rl);
     return hipGetLastError();
 }
 

@@ -21,7 +21,7 @@ import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 LIB = os.path.join(ROOT, "pycolmap_amd", "csrc", "_obj", "libamc_stamps.so")
-MAX_WG, WAVES = 1024, 4  # kStampMaxWG, kSegsPerItem (match_mfma.hip, amc_internal.h)
+MAX_WG, WAVES, DWORDS = 1024, 4, 12  # kStampMaxWG, kSegsPerItem, kStampDwords (match_mfma.hip, amc_internal.h)
 
 
 def main():
@@ -30,6 +30,7 @@ def main():
     ap.add_argument("--rows", type=int, default=4096)
     ap.add_argument("--grid", type=int, default=0)
     ap.add_argument("--repeat", type=int, default=3, help="matches run before the sums are read (the first is discarded)")
+    ap.add_argument("--run", type=int, default=0, help="AMC_SCAN_RUN: 0 auto, 1 off, 2 / 4 / 8 forced")
     ap.add_argument("--lib", default=LIB, help="a stamped library of another revision (default: the tree's own)")
     args = ap.parse_args()
     lib_path = os.path.abspath(args.lib)
@@ -38,6 +39,8 @@ def main():
     os.environ["AMC_LIB_PATH"] = lib_path
     if args.grid:
         os.environ["AMC_SCAN_GRID"] = str(args.grid)
+    if args.run:
+        os.environ["AMC_SCAN_RUN"] = str(args.run)
     import torch
     import bench
     from pycolmap_amd import _capi, synth
@@ -46,7 +49,7 @@ def main():
     s1, s2 = synth.exhaustive_pairs(args.images)
     lib = ctypes.CDLL(lib_path)
     lib.amc_scan_stamps_read.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    buf = np.zeros((2, MAX_WG, WAVES, 8), np.uint32)
+    buf = np.zeros((2, MAX_WG, WAVES, DWORDS), np.uint32)
     with _capi.Context(0) as ctx:
         ctx.reserve_slots(args.images)
         for k in range(args.images):
@@ -60,7 +63,7 @@ def main():
            "pairs_mfma": int(st["pairs_mfma"])}
     for mode, name in ((0, "forward_scan"), (1, "reverse_scan")):
         s = buf[mode].astype(np.float64)
-        wg_a, wg_b, wg_c, wg_n, tail_a, tail_c = [], [], [], [], [], []
+        wg_a, wg_b, wg_c, wg_n, tail_a, tail_c, wg_kept, wg_bk, wg_bl = [], [], [], [], [], [], [], [], []
         for wg in range(MAX_WG):
             w = s[wg][s[wg][:, 3] > 0]
             if len(w):
@@ -68,6 +71,13 @@ def main():
                 wg_b.append(float(np.mean(w[:, 1] / w[:, 2])))
                 wg_c.append(float(np.mean(w[:, 2] / w[:, 3])))
                 wg_n.append(float(w[0, 3]))
+                # boundaries of items that kept their X rows (run entries with kRunSameX), and of the others
+                wg_kept.append(float(np.mean(w[:, 9] / w[:, 3])))
+                k, l = w[w[:, 9] > 0], w[w[:, 3] > w[:, 9]]
+                if len(k):
+                    wg_bk.append(float(np.mean(k[:, 8] / k[:, 9])))
+                if len(l):
+                    wg_bl.append(float(np.mean((l[:, 1] - l[:, 8]) / (l[:, 3] - l[:, 9]))))
             t = s[wg][s[wg][:, 7] > 0]
             if len(t):
                 tail_a.append(float(np.mean(t[:, 5])))
@@ -76,7 +86,8 @@ def main():
         out[name] = {"workgroups_with_a_boundary": len(wg_a), "items_with_successor_per_workgroup_median": med(wg_n),
                      "crossings_share_a_over_c_median": med(wg_a), "crossings_share_min_max": [med([min(wg_a)]), med([max(wg_a)])] if wg_a else None,
                      "boundary_share_b_over_c_median": med(wg_b), "boundary_share_min_max": [med([min(wg_b)]), med([max(wg_b)])] if wg_b else None,
-                     "clocks_per_item_c_median": med(wg_c),
+                     "clocks_per_item_c_median": med(wg_c), "items_that_kept_x_share_median": med(wg_kept),
+                     "boundary_clocks_kept_x_median": med(wg_bk), "boundary_clocks_loaded_x_median": med(wg_bl),
                      "last_item_crossing_clocks_median": med(tail_a), "last_item_clocks_median": med(tail_c)}
     print(json.dumps(out))
 

@@ -101,33 +101,56 @@ def build_libamc(force: bool = False, verbose: bool = True) -> Path:
     return LIB
 
 
-HOST_SOURCES = ["module.cc", "controller.cc", "database.cc", "model_io.cc", "reconstruction.cc"]
+HOST_SOURCES = ["module.cc", "bind_reconstruction.cc", "bind_bundle.cc", "bind_triangulator.cc", "bind_mapper.cc", "bind_database.cc",
+                "controller.cc", "database.cc", "model_io.cc", "reconstruction.cc"]
 
 
 def build_host(force: bool = False, verbose: bool = True) -> Path:
     """The C++/pybind11 host layer (pycolmap API surface) -> pycolmap_amd/_pycolmap*.so, linked
-    against libamc.so (C ABI) and the system SQLite."""
+    against libamc.so (C ABI) and the system SQLite.  One object per source under csrc/host/_obj/, compiled in
+    parallel, then one link, as build_libamc does it."""
     import sysconfig
 
     import pybind11
     host = CSRC / "host"
+    obj_dir = host / "_obj"  # not under csrc/_obj/: clean_variants() removes what it does not know there
+    obj_dir.mkdir(exist_ok=True)
     ext = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
     out = PKG / f"_pycolmap{ext}"
-    srcs = [host / n for n in HOST_SOURCES]
-    deps = srcs + list(host.glob("*.h")) + list((ROOT / "include").glob("*.h")) + [LIB]
-    if not force and not _stale(out, deps):
-        return out
     sqlite_inc = next((p for p in ("/usr/include", "/opt/conda/include") if (Path(p) / "sqlite3.h").exists()), None)
     if sqlite_inc is None:
         raise RuntimeError("sqlite3.h not found")
-    cmd = ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden", "-Wall",
-           f"-I{pybind11.get_include()}", f"-I{sysconfig.get_paths()['include']}", f"-I{sqlite_inc}",
-           *map(str, srcs), f"-L{PKG}", "-l:libamc.so", "-l:libsqlite3.so.0", "-Wl,-rpath,$ORIGIN",
-           "-o", str(out)]
-    if verbose:
-        print("[build]", " ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    _stamp(out, deps)
+    cflags = ["-O2", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
+              f"-I{pybind11.get_include()}", f"-I{sysconfig.get_paths()['include']}", f"-I{sqlite_inc}"]
+    headers = list(host.glob("*.h")) + list((ROOT / "include").glob("*.h"))
+    objs, jobs = [], []
+    for name in HOST_SOURCES:
+        src = host / name
+        obj = obj_dir / (src.stem + ".o")
+        deps = [src] + headers
+        if force or _stale(obj, deps, " ".join(cflags)):
+            jobs.append((src, obj, deps))
+        objs.append(obj)
+
+    def compile_one(job):
+        src, obj, deps = job
+        cmd = ["g++", *cflags, "-c", str(src), "-o", str(obj)]
+        if verbose:
+            print("[build]", " ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+        _stamp(obj, deps, " ".join(cflags))
+
+    if jobs:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=max(1, min(8, os.cpu_count() or 1, len(jobs)))) as pool:
+            list(pool.map(compile_one, jobs))
+    if force or _stale(out, objs + [LIB]):
+        cmd = ["g++", "-shared", "-fPIC", "-fvisibility=hidden", *map(str, objs), f"-L{PKG}", "-l:libamc.so", "-l:libsqlite3.so.0",
+               "-Wl,-rpath,$ORIGIN", "-o", str(out)]
+        if verbose:
+            print("[build]", " ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+        _stamp(out, objs + [LIB])
     return out
 
 

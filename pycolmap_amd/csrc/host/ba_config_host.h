@@ -1,7 +1,7 @@
 // ba_config_host.h — COLMAP 3.9.1's BundleAdjustmentConfig and the set-up of BundleAdjuster::Solve on model_io's
 // structs: which images, cameras, points and observations of a model take part in an adjustment of a
 // part of it, what is constant, the flat problem of include/amc_ba.h with its point mask, and the write-back.  No Python
-// and no HIP here (the binding in module.cc calls amc_bundle_adjust_masked between Flatten and WriteBack):
+// and no HIP here (the binding in bind_bundle.cc calls amc_bundle_adjust_masked between Flatten and WriteBack):
 // tests/shim/ba_config_host_fuzz.cc runs it under ASan + UBSan.  A failed COLMAP CHECK is a std::invalid_argument in the
 // THROW_CHECK format (COLMAP aborts).
 #pragma once

@@ -1,5 +1,5 @@
 // ba_host.h — bundle_adjustment's controller on model_io's structs: which parameters are constant, the
-// flat problem of include/amc_ba.h, and the write-back.  No Python and no HIP here (the binding in module.cc calls
+// flat problem of include/amc_ba.h, and the write-back.  No Python and no HIP here (the binding in bind_bundle.cc calls
 // amc_bundle_adjust between Flatten and WriteBack): tests/shim/ba_host_fuzz.cc runs it under ASan + UBSan.
 #pragma once
 

@@ -22,11 +22,11 @@
 #include <string>
 #include <vector>
 
+#include "binding_support.h"
 #include "controller.h"
 #include "py_types.h"
 
 namespace amchost {
-using namespace pybind11::literals;
 
 // COLMAP camera models: id, name, number of parameters, focal / principal indices
 struct CameraModelInfo {
@@ -299,30 +299,7 @@ inline void BindCamera(py::module_& m) {
         .def("__deepcopy__", [](const PyCamera& c, const py::dict&) { return PyCamera(c); });
 }
 
-// ---- one lazily created context for the single-pair calls (device 0) ---------------------------
-struct EstimatorCtx {
-    std::mutex mu;
-    amc_ctx* ctx = nullptr;
-    amc_ctx* Get() {
-        if (!ctx) {
-            const int rc = amc_ctx_create(0, &ctx);
-            if (rc != AMC_OK) throw std::runtime_error(std::string("amc_ctx_create: ") + amc_last_error());
-            if (amc_ctx_reserve_slots(ctx, 2) != AMC_OK)
-                throw std::runtime_error(std::string("amc_ctx_reserve_slots: ") + amc_last_error());
-        }
-        return ctx;
-    }
-};
-inline EstimatorCtx& TheEstimatorCtx() {
-    static EstimatorCtx* e = new EstimatorCtx();  // intentionally leaked: no HIP calls at interpreter exit
-    return *e;
-}
-inline void EstCheck(int rc, const char* what) {
-    if (rc == AMC_OK) return;
-    const std::string msg = std::string(what) + ": " + amc_last_error();
-    if (rc == AMC_E_INVALID) throw std::invalid_argument(msg);
-    throw std::runtime_error(msg);
-}
+// (the single-pair calls run on binding_support.h's estimator context: EstimatorCtx, TheEstimatorCtx, EstCheck)
 
 using PointsArray = py::array_t<double, py::array::c_style | py::array::forcecast>;
 inline size_t CheckPoints(const PointsArray& a, const char* name) {

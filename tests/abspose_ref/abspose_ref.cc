@@ -1040,6 +1040,19 @@ void QuatPlus(const double* q, const double* d, double* o) {  // EigenQuaternion
     o[1] = w * q[1] - x * q[2] + y * q[3] + z * q[0];
     o[2] = w * q[2] + x * q[1] - y * q[0] + z * q[3];
 }
+// the camera-frame point q * P + t with its derivatives by (qx, qy, qz, qw, tx, ty, tz)
+void PosePoint(const double* q, const double* t, const double* P, D* pc) {
+    D qv[4], tv[3];
+    for (int i = 0; i < 4; ++i) { qv[i] = Cst(q[i]); qv[i].g[i] = 1.0; }
+    for (int i = 0; i < 3; ++i) { tv[i] = Cst(t[i]); tv[i].g[4 + i] = 1.0; }
+    D w0 = qv[1] * P[2] - qv[2] * P[1], w1 = qv[2] * P[0] - qv[0] * P[2], w2 = qv[0] * P[1] - qv[1] * P[0];
+    w0 = w0 + w0;
+    w1 = w1 + w1;
+    w2 = w2 + w2;
+    pc[0] = (P[0] + qv[3] * w0) + (qv[1] * w2 - qv[2] * w1) + tv[0];
+    pc[1] = (P[1] + qv[3] * w1) + (qv[2] * w0 - qv[0] * w2) + tv[1];
+    pc[2] = (P[2] + qv[3] * w2) + (qv[0] * w1 - qv[1] * w0) + tv[2];
+}
 struct RefOpts {
     int model;
     const double* params;
@@ -1056,19 +1069,10 @@ Eval Evaluate(const RefOpts& o, const double* q, const double* t, const double* 
     const double Jm[4][3] = {{q[3], q[2], -q[1]}, {-q[2], q[3], q[0]}, {q[1], -q[0], q[3]}, {-q[0], -q[1], -q[2]}};
     const std::vector<double> s = Sum64<28>(mask.size(), [&](size_t k, double* acc) {
         if (!mask[k]) return;
-        D qv[4], tv[3];
-        for (int i = 0; i < 4; ++i) { qv[i] = Cst(q[i]); qv[i].g[i] = 1.0; }
-        for (int i = 0; i < 3; ++i) { tv[i] = Cst(t[i]); tv[i].g[4 + i] = 1.0; }
-        const double* P = X + 3 * k;
-        D w0 = qv[1] * P[2] - qv[2] * P[1], w1 = qv[2] * P[0] - qv[0] * P[2], w2 = qv[0] * P[1] - qv[1] * P[0];
-        w0 = w0 + w0;
-        w1 = w1 + w1;
-        w2 = w2 + w2;
-        const D pc0 = (P[0] + qv[3] * w0) + (qv[1] * w2 - qv[2] * w1) + tv[0];
-        const D pc1 = (P[1] + qv[3] * w1) + (qv[2] * w0 - qv[0] * w2) + tv[1];
-        const D pc2 = (P[2] + qv[3] * w2) + (qv[0] * w1 - qv[1] * w0) + tv[2];
+        D pc[3];
+        PosePoint(q, t, X + 3 * k, pc);
         D rx, ry;
-        ImgFromCam(o.model, o.params, pc0, pc1, pc2, &rx, &ry);
+        ImgFromCam(o.model, o.params, pc[0], pc[1], pc[2], &rx, &ry);
         rx = rx - xy[2 * k];
         ry = ry - xy[2 * k + 1];
         const double sq = rx.a * rx.a + ry.a * ry.a, sum = 1.0 + sq * c;
@@ -1284,6 +1288,21 @@ double abspose_ref_atan(double x) { return Atan(x); }
 double abspose_ref_sin(double x) { return Sin(x); }
 double abspose_ref_cos(double x) { return Cos(x); }
 double abspose_ref_log(double x) { return Log(x); }
+
+// one correspondence's projection as the refinement evaluates it (12.7): the pixel and its derivatives by
+// (qx, qy, qz, qw, tx, ty, tz), row-major 2 x 7
+void abspose_ref_project(int model, const double* params, const double* q, const double* t, const double* X, double* xy,
+                         double* J) {
+    D pc[3], x, y;
+    PosePoint(q, t, X, pc);
+    ImgFromCam(model, params, pc[0], pc[1], pc[2], &x, &y);
+    xy[0] = x.a;
+    xy[1] = y.a;
+    for (int i = 0; i < 7; ++i) {
+        J[i] = x.g[i];
+        J[7 + i] = y.g[i];
+    }
+}
 
 int abspose_ref_p3p(const double* uv, const double* X, double* out) {
     const std::vector<Model> m = P3P(uv, X);

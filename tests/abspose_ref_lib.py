@@ -33,6 +33,8 @@ def load() -> C.CDLL:
         f = getattr(lib, f"abspose_ref_{fn}")
         f.restype = C.c_double
         f.argtypes = [C.c_double]
+    lib.abspose_ref_project.restype = None
+    lib.abspose_ref_project.argtypes = [C.c_int] + [C.c_void_p] * 6
     lib.abspose_ref_p3p.restype = C.c_int
     lib.abspose_ref_p3p.argtypes = [C.c_void_p] * 3
     lib.abspose_ref_epnp.restype = C.c_int
@@ -51,6 +53,17 @@ def load() -> C.CDLL:
 
 def scalar(fn: str, x: float) -> float:
     return getattr(load(), f"abspose_ref_{fn}")(float(x))
+
+
+def project(model, params, q, t, X):
+    """One correspondence as the refinement evaluates it (12.7): the pixel (2,) and its derivatives (2, 7) by
+    (qx, qy, qz, qw, tx, ty, tz)."""
+    prm = np.zeros(12)
+    prm[:len(params)] = params
+    f = lambda a, n: np.ascontiguousarray(a, dtype=np.float64).reshape(n)  # noqa: E731
+    xy, J = np.zeros(2), np.zeros((2, 7))
+    load().abspose_ref_project(int(model), _p(prm), _p(f(q, 4)), _p(f(t, 3)), _p(f(X, 3)), _p(xy), _p(J))
+    return xy, J
 
 
 def p3p(uv, X):

@@ -30,7 +30,12 @@ thirteen fields of the reference's `StereoFusionOptions`) fuses them on the GPU 
 (DESIGN.md section 23); the names `stereo_fusion` and `StereoFusionOptions` themselves stay undefined.  An adjustment's
 uncertainty resolves as well: `estimate_ba_covariance(options, reconstruction, bundle_adjuster)` with
 `BACovarianceOptions` and `BACovarianceOptionsParams` returns a `BACovariance` (or None) whose accessors give the pose,
-camera, point, cross and relative-pose blocks by id."""
+camera, point, cross and relative-pose blocks by id.  A pose is refined together with its camera
+by `refine_absolute_pose(cam_from_world, points2D, points3D, inlier_mask, camera, refinement_options)` and
+`estimate_and_refine_absolute_pose(points2D, points3D, camera, estimation_options, refinement_options)`, which honour
+`refine_focal_length` and `refine_extra_params` and update the camera in place, and a mapper registers an image that way
+with `register_next_image_and_refine(mapper, options, image_id)`; `pose_refinement` and
+`absolute_pose_estimation` keep refusing the two flags."""
 import pycolmap_amd as _impl
 from pycolmap_amd import *  # noqa: F401,F403
 from pycolmap_amd import __version__  # noqa: F401
@@ -41,4 +46,4 @@ globals().update({n: getattr(_impl, n) for n in _PUBLIC})
 
 def __getattr__(name):
     raise AttributeError(f"pycolmap.{name} is outside pycolmap_amd's scope (SIFT feature extraction, exhaustive / sequential "
-                         f"matching + two-view verification, known-pose triangulation, absolute pose, image undistortion, bundle adjustment of a minimal Reconstruction behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}; also in scope: point filtering, and incremental triangulation of an image (CorrespondenceGraph, IncrementalTriangulator.triangulate_image), and the adjustment of a part of the model (BundleAdjustmentConfig, BundleAdjuster.solve), and track completion and merging (complete_tracks, complete_all_tracks, merge_tracks, merge_all_tracks with the triangulator as first argument), and retriangulation of under-reconstructed image pairs (retriangulate with the triangulator as first argument), and the mapper's image ranking, registration and local bundle (IncrementalMapper.find_next_images, register_next_image, find_local_bundle with IncrementalMapperOptions and ImageSelectionMethod), and the start of a model (register_initial_image_pair, adjust_global_bundle, filter_images with the mapper as first argument), and PatchMatch stereo on a dense workspace (PatchMatchController(options, workspace_path).run() with PatchMatchOptions, and read_array, write_array for its files; patch_match_stereo and stereo_fusion stay undefined), and stereo fusion of those maps (StereoFusion(options, workspace_path).run() and write(output_path) with FusionOptions, DESIGN.md section 23; the names stereo_fusion and StereoFusionOptions stay undefined), and the covariance of an adjustment (estimate_ba_covariance(options, reconstruction, bundle_adjuster) with BACovarianceOptions and BACovarianceOptionsParams, returning a BACovariance; DESIGN.md section 24)")
+                         f"matching + two-view verification, known-pose triangulation, absolute pose, image undistortion, bundle adjustment of a minimal Reconstruction behind the pycolmap API); available: {', '.join(sorted(_PUBLIC))}; also in scope: point filtering, and incremental triangulation of an image (CorrespondenceGraph, IncrementalTriangulator.triangulate_image), and the adjustment of a part of the model (BundleAdjustmentConfig, BundleAdjuster.solve), and track completion and merging (complete_tracks, complete_all_tracks, merge_tracks, merge_all_tracks with the triangulator as first argument), and retriangulation of under-reconstructed image pairs (retriangulate with the triangulator as first argument), and the mapper's image ranking, registration and local bundle (IncrementalMapper.find_next_images, register_next_image, find_local_bundle with IncrementalMapperOptions and ImageSelectionMethod), and the start of a model (register_initial_image_pair, adjust_global_bundle, filter_images with the mapper as first argument), and PatchMatch stereo on a dense workspace (PatchMatchController(options, workspace_path).run() with PatchMatchOptions, and read_array, write_array for its files; patch_match_stereo and stereo_fusion stay undefined), and stereo fusion of those maps (StereoFusion(options, workspace_path).run() and write(output_path) with FusionOptions, DESIGN.md section 23; the names stereo_fusion and StereoFusionOptions stay undefined), and the covariance of an adjustment (estimate_ba_covariance(options, reconstruction, bundle_adjuster) with BACovarianceOptions and BACovarianceOptionsParams, returning a BACovariance; DESIGN.md section 24), and the refinement of a pose together with its camera's focal length and distortion (refine_absolute_pose, estimate_and_refine_absolute_pose, and register_next_image_and_refine with the mapper as first argument; DESIGN.md section 25)")

@@ -30,6 +30,8 @@ try:  # the compiled host layer; absent only before `python -m pycolmap_amd.buil
     from ._fusion import FusionOptions, StereoFusion  # noqa: F401
     from ._ba_covariance import (  # noqa: F401
         BACovariance, BACovarianceOptions, BACovarianceOptionsParams, estimate_ba_covariance)
+    from ._pose_intrinsics import (  # noqa: F401
+        estimate_and_refine_absolute_pose, refine_absolute_pose, register_next_image_and_refine)
     _HOST_LAYER_ERROR = None
 except ImportError as _e:  # pragma: no cover - exercised only on an unbuilt tree
     _HOST_LAYER_ERROR = _e

@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = [
     "amc_pair_tri_opts_default", "amc_triangulate_pairs", "amc_pair_tri_result_free",
     "amc_patch_match_opts_default", "amc_patch_match", "amc_patch_match_result_free",
     "amc_fusion_opts_default", "amc_fuse_depth_maps", "amc_fusion_result_free",
+    "amc_refine_poses_and_cameras", "amc_estimate_poses_and_cameras", "amc_absrefine_result_free",
 ]
 COMM_ID_BYTES = 128
 RANSAC_F, RANSAC_H, RANSAC_E = 0, 1, 2
@@ -166,6 +167,16 @@ class AbsPoseResult(C.Structure):
                 ("focal_factor", C.POINTER(C.c_double)), ("covariance", C.POINTER(C.c_double)),
                 ("inlier_mask", C.POINTER(C.c_uint8)), ("device_ms", C.c_double), ("kernel_ms", C.c_double),
                 ("num_batches", C.c_uint32), ("_priv", C.c_void_p)]
+
+
+class AbsRefineResult(C.Structure):  # amc_absrefine_result (include/amc_absrefine.h)
+    _fields_ = [("nqueries", C.c_size_t), ("ncorr", C.c_size_t), ("success", C.POINTER(C.c_uint8)),
+                ("qvec", C.POINTER(C.c_double)), ("tvec", C.POINTER(C.c_double)),
+                ("num_inliers", C.POINTER(C.c_uint32)), ("num_trials", C.POINTER(C.c_uint64)),
+                ("focal_factor", C.POINTER(C.c_double)), ("covariance", C.POINTER(C.c_double)),
+                ("inlier_mask", C.POINTER(C.c_uint8)), ("camera_params", C.POINTER(C.c_double)),
+                ("device_ms", C.c_double), ("kernel_ms", C.c_double), ("num_batches", C.c_uint32),
+                ("_priv", C.c_void_p)]
 
 
 def abspose_options(estimation=None, refinement=None):
@@ -1328,6 +1339,17 @@ def load() -> C.CDLL:
         lib.amc_refine_absolute_poses.restype = C.c_int
         lib.amc_abspose_result_free.argtypes = [C.POINTER(AbsPoseResult)]
         lib.amc_abspose_result_free.restype = None
+    if hasattr(lib, "amc_refine_poses_and_cameras"):  # (absent from a library built from an older revision)
+        lib.amc_estimate_poses_and_cameras.argtypes = ([C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 +
+                                                       [C.POINTER(AbsPoseOpts), C.POINTER(AbsPoseRefineOpts), C.c_int,
+                                                        C.POINTER(AbsRefineResult)])
+        lib.amc_estimate_poses_and_cameras.restype = C.c_int
+        lib.amc_refine_poses_and_cameras.argtypes = ([C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7 +
+                                                     [C.POINTER(AbsPoseRefineOpts), C.c_int,
+                                                      C.POINTER(AbsRefineResult)])
+        lib.amc_refine_poses_and_cameras.restype = C.c_int
+        lib.amc_absrefine_result_free.argtypes = [C.POINTER(AbsRefineResult)]
+        lib.amc_absrefine_result_free.restype = None
     if hasattr(lib, "amc_estimate_rig_absolute_poses"):
         lib.amc_estimate_rig_absolute_poses.argtypes = ([C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7 +
                                                         [C.POINTER(RansacOpts), C.POINTER(AbsPoseRefineOpts), C.c_int,
@@ -1837,6 +1859,56 @@ class Context:
                 out["covariance"] = a(res.covariance, (nq, 36)).reshape(nq, 6, 6)
         finally:
             self._lib.amc_abspose_result_free(C.byref(res))
+        return out
+
+    def estimate_poses_and_cameras(self, offsets, camera_models, camera_params, points2D, points3D, estimation=None,
+                                   refinement=None, return_covariance=False):
+        """amc_estimate_poses_and_cameras: estimate_absolute_poses' LO-RANSAC per focal-length factor, then one joint
+        refinement of the RANSAC's pose and the scaled camera.  refinement's refine_focal_length
+        / refine_extra_params are honoured.  Returns estimate_absolute_poses' dict plus camera_params (Q, 12)."""
+        off, models, prm, p2, p3 = abspose_inputs(offsets, camera_models, camera_params, points2D, points3D)
+        eo, ro = abspose_options(estimation, refinement)
+        res = AbsRefineResult()
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _check(self._lib.amc_estimate_poses_and_cameras(self._h, ptr(off), off.size - 1, ptr(models), ptr(prm),
+                                                         ptr(p2), ptr(p3), C.byref(eo), C.byref(ro),
+                                                         int(bool(return_covariance)), C.byref(res)))
+        return self._absrefine_out(res, off.size - 1, int(off[-1]), return_covariance)
+
+    def refine_poses_and_cameras(self, offsets, camera_models, camera_params, points2D, points3D, qvec, tvec,
+                                 inlier_mask, refinement=None, return_covariance=False):
+        """amc_refine_poses_and_cameras: refine_absolute_poses with the camera's focal lengths (refine_focal_length) and
+        extra parameters (refine_extra_params) refined with the pose; the same dict plus camera_params (Q, 12): the
+        refined camera of a successful query, the input of a failed one."""
+        off, models, prm, p2, p3 = abspose_inputs(offsets, camera_models, camera_params, points2D, points3D)
+        nq, n = off.size - 1, int(off[-1])
+        q = np.ascontiguousarray(qvec, dtype=np.float64).reshape(-1, 4)
+        t = np.ascontiguousarray(tvec, dtype=np.float64).reshape(-1, 3)
+        m = np.ascontiguousarray(inlier_mask, dtype=bool).reshape(-1).astype(np.uint8)
+        if q.shape[0] != nq or t.shape[0] != nq or m.size != n:
+            raise ValueError(f"refine_poses_and_cameras: {nq} queries and {n} correspondences by offsets, {q.shape[0]} "
+                             f"rotations, {t.shape[0]} translations, {m.size} mask entries")
+        _, ro = abspose_options(None, refinement)
+        res = AbsRefineResult()
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _check(self._lib.amc_refine_poses_and_cameras(self._h, ptr(off), nq, ptr(models), ptr(prm), ptr(p2), ptr(p3),
+                                                       ptr(q), ptr(t), ptr(m), C.byref(ro),
+                                                       int(bool(return_covariance)), C.byref(res)))
+        return self._absrefine_out(res, nq, n, return_covariance)
+
+    def _absrefine_out(self, res, nq, n, cov):
+        try:
+            a = lambda p, shape: np.ctypeslib.as_array(p, (max(shape[0], 1),) + shape[1:])[:shape[0]].copy()  # noqa: E731
+            out = {"success": a(res.success, (nq,)).astype(bool), "qvec": a(res.qvec, (nq, 4)),
+                   "tvec": a(res.tvec, (nq, 3)), "num_inliers": a(res.num_inliers, (nq,)),
+                   "num_trials": a(res.num_trials, (nq,)), "focal_factor": a(res.focal_factor, (nq,)),
+                   "inlier_mask": a(res.inlier_mask, (n,)).astype(bool),
+                   "camera_params": a(res.camera_params, (nq, 12)), "device_ms": res.device_ms,
+                   "kernel_ms": res.kernel_ms, "num_batches": int(res.num_batches)}
+            if cov:
+                out["covariance"] = a(res.covariance, (nq, 36)).reshape(nq, 6, 6)
+        finally:
+            self._lib.amc_absrefine_result_free(C.byref(res))
         return out
 
     def bundle_adjust(self, camera_models, camera_params, camera_const, image_cameras, qvec, tvec, pose_const, xyz,

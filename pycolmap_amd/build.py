@@ -19,7 +19,7 @@ OBJ = CSRC / "_obj"
 LIB = PKG / "libamc.so"
 
 HIP_SOURCES = ["amc_api.hip", "amc_match.hip", "amc_verify.hip", "amc_comm.hip", "match_common.hip", "match_dot4.hip", "match_guided.hip", "match_mfma.hip", "tvg_e.hip", "tvg_fh.hip", "tvg_e_big.hip",
-               "tvg_fh_big.hip", "pose.hip", "camera.hip", "sift.hip", "tri.hip", "abspose.hip", "rigpose.hip", "undistort.hip", "ba.hip", "filter.hip", "triobs.hip", "tracks.hip", "retri.hip", "mapper.hip", "initpair.hip", "patchmatch.hip", "fusion.hip", "bacov.hip"]
+               "tvg_fh_big.hip", "pose.hip", "camera.hip", "sift.hip", "tri.hip", "abspose.hip", "rigpose.hip", "undistort.hip", "ba.hip", "filter.hip", "triobs.hip", "tracks.hip", "retri.hip", "mapper.hip", "initpair.hip", "patchmatch.hip", "fusion.hip", "bacov.hip", "absrefine.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950",
     "-O3",

@@ -145,6 +145,7 @@ bool register_next_image_with(PyMapper& mp, const MapperOptions& o, uint32_t ima
         size_t num_inliers = 0;
         double focal_factor = 1.0, q[4] = {0, 0, 0, 1}, tv[3] = {0, 0, 0};
         std::vector<uint8_t> mask(n, 0);
+        std::vector<double> refined_params;  // the solver's camera, when it returns one: it replaces the scaling
         if (!solver.is_none()) {
             py::dict d, est;
             d["camera_model"] = cmodel;
@@ -162,6 +163,10 @@ bool register_next_image_with(PyMapper& mp, const MapperOptions& o, uint32_t ima
             est["min_num_trials"] = eo.min_num_trials;
             est["max_num_trials"] = eo.max_num_trials;
             d["estimation"] = est;
+            py::dict rfn;  // the rule's refinement flags, for a solver that refines the camera with the pose (25.6)
+            rfn["refine_focal_length"] = rule.refine_focal_length;
+            rfn["refine_extra_params"] = rule.refine_extra_params;
+            d["refinement"] = rfn;
             const py::dict out = solver(d);
             const auto sq = CArray<double>::ensure(out["qvec"]);
             const auto stv = CArray<double>::ensure(out["tvec"]);
@@ -174,6 +179,12 @@ bool register_next_image_with(PyMapper& mp, const MapperOptions& o, uint32_t ima
             std::copy(sq.data(), sq.data() + 4, q);
             std::copy(stv.data(), stv.data() + 3, tv);
             std::copy(sm.data(), sm.data() + n, mask.begin());
+            if (out.contains("camera_params")) {
+                const auto sp = CArray<double>::ensure(out["camera_params"]);
+                if (!sp || sp.size() != 12)
+                    throw py::value_error("register_next_image: the solver's camera_params are not 12 values");
+                refined_params.assign(sp.data(), sp.data() + 12);
+            }
         } else {
             const uint64_t off[2] = {0, n};
             ResultGuard<amc_abspose_result, amc_abspose_result_free> res;
@@ -195,7 +206,12 @@ bool register_next_image_with(PyMapper& mp, const MapperOptions& o, uint32_t ima
         ok = success && num_inliers >= static_cast<size_t>(o.abs_pose_min_num_inliers);
         if (ok) {
             std::set<uint64_t> modified = t.modified;
-            ApplyRegistration(c, pairs, mask.data(), q, tv, rule.estimate_focal_length, focal_factor, &model, &ix, &modified);
+            ApplyRegistration(c, pairs, mask.data(), q, tv, rule.estimate_focal_length && refined_params.empty(), focal_factor, &model, &ix,
+                              &modified);
+            if (!refined_params.empty()) {
+                std::vector<double>& cp = model.cameras[cam->second].params;
+                for (size_t k = 0; k < cp.size() && k < 12; ++k) cp[k] = refined_params[k];
+            }
             r.images[py::int_(image_id)] = py::module_::import("copy").attr("copy")(mp.candidate_images.at(image_id));
             update_from_model(r, model);
             t.modified.swap(modified);

@@ -63,7 +63,7 @@
 // item's chunks and X rows, decode, and meet at two barriers: 6.7 % of an item's clocks, profiles/boundary/), and
 // the partner workgroup's wave then has the SIMD to itself instead of the matrix pipe of the whole CU standing idle.
 // A chunk crossing's barrier joins four waves on four SIMDs.  Both workgroups must fit: at most 256 registers per lane
-// (amdgpu_waves_per_eu pins it; MODE 0 compiles to 250 VGPRs, MODE 1 to 194, without scratch - check
+// (amdgpu_waves_per_eu pins it; MODE 0 compiles to 246 VGPRs, MODE 1 to 194, without scratch - check
 // -Rpass-analysis=kernel-resource-usage after every change, profiles/scanloop/kernel_resource_usage.txt) and at most
 // 80 KB of LDS (66 KB, ONE __shared__ object); launch_match_mfma asks the runtime.
 // Taking the ticket two items ahead and warming the next item's X rows in L2 were both built and measured, and
@@ -155,14 +155,18 @@ struct YFrag {
 #ifdef AMC_SCAN_STAMPS
 // Diagnostic build only (tools/scan_stamps.hip includes this file with the macro; libamc.so is compiled without it and
 // holds none of this): s_memtime stamps around the places where a wave's MFMA stream stops, summed per wave in scalar
-// registers and stored - running sums, lane 0 - behind every item.  Per (MODE, workgroup, wave) twelve dwords, over the
+// registers and stored - running sums, lane 0 - behind every item.  Per (MODE, workgroup, wave) sixteen dwords, over the
 // items that had a successor in the same workgroup:
 //   [0] clocks from arriving at a chunk crossing's s_waitcnt to leaving its s_barrier   [1] clocks from the
 //   __syncthreads() that ends an item's scan to the first MFMA of the next item   [2] clocks from an item's first MFMA
 //   to the next item's   [3] such items   [4] those of them this wave had rows in
 // for the workgroup's last item: [5] as [0]   [6] first MFMA to the end of the epilogue   [7] 1
 // and of [1] and [3] the part of the successors that kept the X rows (kRunSameX): [8] clocks   [9] items
-constexpr int kStampMaxWG = 1024, kStampDwords = 12;
+// [1] split: [10] clocks from that __syncthreads() to arriving at the next item's top wait (the next item's loads issued,
+// this item decoded and stored)   [11] clocks in that wait and its barrier (what is left of the loads' round trips, and
+// the other waves); the rest of [1] is the way to the first MFMA.  [12], [13]: [10] and [11] of the successors that kept
+// the X rows
+constexpr int kStampMaxWG = 1024, kStampDwords = 16;
 __device__ uint32_t g_scan_stamps[2 * kStampMaxWG * kSegsPerItem * kStampDwords];
 #define AMC_STAMP() ((uint32_t)__builtin_amdgcn_s_memtime())
 #endif
@@ -372,6 +376,7 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
 
 #ifdef AMC_SCAN_STAMPS
     uint32_t st_a = 0, st_first = 0, st_end = 0, st_sum[5] = {0, 0, 0, 0, 0}, st_kept[2] = {0, 0};
+    uint32_t st_w0 = 0, st_w1 = 0, st_split[4] = {0, 0, 0, 0};
     bool st_prev = false, st_prev_active = false, st_keep_x = false;
     uint32_t* const st_slot = g_scan_stamps + ((size_t)(MODE * kStampMaxWG + min((int)blockIdx.x, kStampMaxWG - 1)) * kW + wid) * kStampDwords;
 #endif
@@ -496,8 +501,14 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
         // (step, xt = 0..kXT-1) in order; acc[0] holds even xt, acc[1] odd xt.  Each phase
         // issues the MFMAs of the NEXT one, then runs the VALU of the current one.
         YFrag y0, y1;
+#ifdef AMC_SCAN_STAMPS
+        st_w0 = AMC_STAMP();
+#endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // chunk 0 and this item's X rows landed
         __syncthreads();
+#ifdef AMC_SCAN_STAMPS
+        st_w1 = AMC_STAMP();
+#endif
         if (first) {  // (everything this wave loaded has landed)
             rv = rvn;
             if (table) {
@@ -523,15 +534,21 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
                 st_sum[2] += now - st_first;
                 st_sum[3] += 1;
                 st_sum[4] += st_prev_active ? 1 : 0;
+                st_split[0] += st_w0 - st_end;
+                st_split[1] += st_w1 - st_w0;
                 if (st_keep_x) {  // this item kept the X rows of the one before
                     st_kept[0] += now - st_end;
                     st_kept[1] += 1;
+                    st_split[2] += st_w0 - st_end;
+                    st_split[3] += st_w1 - st_w0;
                 }
                 if (lane == 0) {
 #pragma unroll
                     for (int k = 0; k < 5; ++k) st_slot[k] = st_sum[k];
                     st_slot[8] = st_kept[0];
                     st_slot[9] = st_kept[1];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) st_slot[10 + k] = st_split[k];
                 }
             }
             st_a = 0;
@@ -678,34 +695,74 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
         }
         if (active) {
             const int cnt = dword(dv, kDCnt);
-            uint32_t bits_lo = 0;
+            // Merge the four lane quarters (they saw different Y rows of every block; equal values keep the lower tile)
+            // and decode, TWO X tiles' worth of instructions instead of eight: the merge is a reduce-scatter, not a
+            // butterfly.  v_permlane32_swap exchanges the upper half of one register with the lower half of another:
+            // applied to the states of the X tiles xt and xt + 4 it leaves, in the lower 32 lanes, both halves' states
+            // of tile xt side by side and in the upper 32 lanes those of tile xt + 4 - one merge serves two tiles.
+            // v_permlane16_swap does the same with 16-lane rows for the pairs that are left.  Behind both rounds two
+            // register sets hold all 128 rows of the segment, one row per lane: set k, lane quarter q = X tile
+            // 2 k + (q & 1) + 4 (q >> 1), and the decode, the acceptance test and the store run twice, in all lanes,
+            // where they ran eight times in sixteen.  (The epilogue runs against the partner workgroup's scan on the
+            // same SIMD: its cost is its instruction count.  profiles/headfetch/README.md.)
+            // A lane's tile: the quarter's own of its block's four (-1 while nothing beat the floor)
+            int mb[kXT], ms[kXT], mt[kXT];
 #pragma unroll
             for (int xt = 0; xt < kXT; ++xt) {
-                const int kl = xt * 16 + l15;
-                // merge the four lane quarters (they saw different Y rows of every block): equal values keep the
-                // lower tile.  A lane's tile: the quarter's own of its block's four (-1 while nothing beat the floor)
-                int b = eb[xt], s = es[xt], t = et[xt] < 0 ? -1 : et[xt] * kSPB + lq;
+                mb[xt] = eb[xt];
+                ms[xt] = es[xt];
+                mt[xt] = et[xt] < 0 ? -1 : et[xt] * kSPB + lq;
+            }
+            auto merge = [&](int a, int o) __attribute__((always_inline)) {  // state o into state a
+                const int b = mb[a], t = mt[a], ob = mb[o], ot = mt[o];
+                const bool ow = (ob > b) || (ob == b && (unsigned)ot < (unsigned)t);
+                ms[a] = max(max(ms[a], ms[o]), ow ? b : ob);
+                mt[a] = ow ? ot : t;
+                mb[a] = ow ? ob : b;
+            };
+            auto swap32 = [&](int& x, int& y) __attribute__((always_inline)) {
+                const auto r = __builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)y, false, false);
+                x = (int)r[0];
+                y = (int)r[1];
+            };
+            auto swap16 = [&](int& x, int& y) __attribute__((always_inline)) {
+                const auto r = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)y, false, false);
+                x = (int)r[0];
+                y = (int)r[1];
+            };
+            static_assert(kXT == 8, "two rounds of pairing leave two register sets");
 #pragma unroll
-                for (int m = 16; m <= 32; m <<= 1) {
-                    const int ob = __shfl_xor(b, m);
-                    const int os = __shfl_xor(s, m);
-                    const int ot = __shfl_xor(t, m);
-                    const bool ow = (ob > b) || (ob == b && (unsigned)ot < (unsigned)t);
-                    s = max(max(s, os), ow ? b : ob);
-                    t = ow ? ot : t;
-                    b = ow ? ob : b;
-                }
+            for (int xt = 0; xt < 4; ++xt) {  // lanes 0..31: tile xt, quarters q and q + 2; lanes 32..63: tile xt + 4
+                swap32(mb[xt], mb[xt + 4]);
+                swap32(ms[xt], ms[xt + 4]);
+                swap32(mt[xt], mt[xt + 4]);
+                merge(xt, xt + 4);
+            }
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {  // rows of 16 lanes: tiles 2k, 2k + 1, 2k + 4, 2k + 5
+                swap16(mb[2 * k], mb[2 * k + 1]);
+                swap16(ms[2 * k], ms[2 * k + 1]);
+                swap16(mt[2 * k], mt[2 * k + 1]);
+                merge(2 * k, 2 * k + 1);
+            }
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int xtl = 2 * k + (lq & 1) + 4 * (lq >> 1);  // this lane's X tile
+                const int kl = xtl * 16 + l15;
+                const int exl = (lq & 2) ? ((lq & 1) ? ex[2 * k + 5] : ex[2 * k + 4]) : ((lq & 1) ? ex[2 * k + 1] : ex[2 * k]);
+                const int b = mb[2 * k], s = ms[2 * k], t = mt[2 * k];
                 bool acc_bit = false;
-                const bool live = lq == 0 && kl < cnt;
+                const bool live = kl < cnt;
                 Top2 o;
-                o.best_v = (uint32_t)(b + ex[xt]);
+                o.best_v = (uint32_t)(b + exl);
                 o.best_idx = o.best_v ? (uint32_t)t : 0xFFFFFFFFu;  // TILE of the best
-                o.second_v = (uint32_t)(s + ex[xt]);
+                o.second_v = (uint32_t)(s + exl);
                 o.pad = 0;
                 // a larger second only ever rejects: rows failing now can be forgotten
                 // (scan_accept.h: thresholds instead of acos; a superset of what the exact tests keep)
                 if (MODE == 0) acc_bit = live && scan_may_accept(sa, o.best_v, o.second_v);
-                const uint32_t bits = MODE == 0 ? (uint32_t)__ballot(acc_bit) : 0u;  // (lanes 0..15: the X tile's rows)
+                // (16 bits per lane quarter: the rows of its X tile)
+                const unsigned long long bits = MODE == 0 ? (unsigned long long)__ballot(acc_bit) : 0ull;
                 // MODE 0 stores what is read: every reader of the row table tests the row's accept bit first
                 // (resolve_index* side 0, select_candidates, finalize), so a row the scan rejects here is never looked
                 // at.  The unit is the X tile - 16 rows, 256 contiguous bytes - stored whole if any of its rows is
@@ -713,20 +770,18 @@ void match_mfma_kernel(const SegDesc* __restrict__ segs, const uint32_t* __restr
                 // headline step less, and on a dense one (a third of the rows accepted) the stores stay the full lines
                 // they were - 16-byte records scattered one in three cost the scan 0.8 % there.  MODE 1 stores every
                 // candidate row: finalize reads cols[j] without a mask.
-                if (live && (MODE == 1 || bits != 0)) {
+                const bool tile_any = MODE == 0 && ((uint32_t)(bits >> (16 * lq)) & 0xFFFFu) != 0;
+                if (live && (MODE == 1 || tile_any)) {
                     Top2* out = reinterpret_cast<Top2*>(const_cast<char*>(dptr(dv, kDOut)));
                     int row = kl;  // MODE 0: `out` points at the segment's first row
                     if (MODE == 1) row = (int)reinterpret_cast<const uint32_t*>(dptr(dv, kDList))[kl];
                     out[row] = o;
                 }
-                if (MODE == 0) {  // accept bits of 32 rows = two X tiles
-                    if (xt & 1) {
-                        // a word without a bit stays as the batch's memset left it (enqueue_scan zeroes the mask)
-                        const uint32_t word = bits_lo | (bits << 16);
-                        if (lane == 0 && word != 0) accmask[(uint32_t)dword(dv, kDAccword) + (xt >> 1)] = word;
-                    } else {
-                        bits_lo = bits;
-                    }
+                if (MODE == 0) {  // accept bits of 32 rows = two X tiles: the lower quarters' and the upper quarters'
+                    // a word without a bit stays as the batch's memset left it (enqueue_scan zeroes the mask)
+                    const uint32_t w_lo = (uint32_t)bits, w_hi = (uint32_t)(bits >> 32);
+                    if (lane == 0 && w_lo != 0) accmask[(uint32_t)dword(dv, kDAccword) + k] = w_lo;
+                    if (lane == 0 && w_hi != 0) accmask[(uint32_t)dword(dv, kDAccword) + k + 2] = w_hi;
                 }
             }
         }

@@ -4,7 +4,7 @@
 #define AMC_SCAN_STAMPS 1
 #include "../pycolmap_amd/csrc/match_mfma.hip"
 
-// dst: 2 (MODE) x max_wg x kSegsPerItem (waves of a workgroup, 4) x kStampDwords (12) dwords; returns the number of dwords, or -1.  reset != 0 zeroes the sums first
+// dst: 2 (MODE) x max_wg x kSegsPerItem (waves of a workgroup, 4) x kStampDwords (16) dwords; returns the number of dwords, or -1.  reset != 0 zeroes the sums first
 // and copies nothing.
 extern "C" __attribute__((visibility("default"))) int amc_scan_stamps_read(uint32_t* dst, int reset) {
     const size_t bytes = sizeof(uint32_t) * 2 * amc::kStampMaxWG * amc::kSegsPerItem * amc::kStampDwords;

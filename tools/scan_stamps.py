@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Where an item's clocks go in the match scan: runs one exhaustive match through the stamped diagnostic library
 (tools/scan_stamps_build.sh) and reports, as medians over workgroups, the share of an item's clocks spent at chunk
-crossings (a / c) and at the item boundary (b / c).  The stamps are described in match_mfma.hip (AMC_SCAN_STAMPS).
+crossings (a / c) and at the item boundary (b / c), and the boundary's split: from the end of the scan to the next item's
+top wait (its loads issued, this item decoded and stored), then the wait itself; the rest is the way to the first MFMA.  The stamps are described in match_mfma.hip (AMC_SCAN_STAMPS).
 Needs a GPU; not in the test suite.
 
     bash tools/scan_stamps_build.sh && python tools/scan_stamps.py --images 8 --rows 4096 --grid 28
@@ -21,7 +22,7 @@ import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 LIB = os.path.join(ROOT, "pycolmap_amd", "csrc", "_obj", "libamc_stamps.so")
-MAX_WG, WAVES, DWORDS = 1024, 4, 12  # kStampMaxWG, kSegsPerItem, kStampDwords (match_mfma.hip, amc_internal.h)
+MAX_WG, WAVES, DWORDS = 1024, 4, 16  # kStampMaxWG, kSegsPerItem, kStampDwords (match_mfma.hip, amc_internal.h)
 
 
 def main():
@@ -60,10 +61,11 @@ def main():
             _, _, st = ctx.match_pairs(s1, s2, kernel="mfma")
         assert lib.amc_scan_stamps_read(buf.ctypes.data, 0) == buf.size
     out = {"images": args.images, "rows": args.rows, "grid_cap": args.grid, "matches_summed": max(1, args.repeat - 1),
-           "pairs_mfma": int(st["pairs_mfma"])}
+           "pairs_mfma": int(st["pairs_mfma"]), "scan_run": int(st["scan_run"])}
     for mode, name in ((0, "forward_scan"), (1, "reverse_scan")):
         s = buf[mode].astype(np.float64)
         wg_a, wg_b, wg_c, wg_n, tail_a, tail_c, wg_kept, wg_bk, wg_bl = [], [], [], [], [], [], [], [], []
+        sp = {k: [] for k in ("issue_all", "wait_all", "issue_kept", "wait_kept", "issue_loaded", "wait_loaded")}
         for wg in range(MAX_WG):
             w = s[wg][s[wg][:, 3] > 0]
             if len(w):
@@ -78,6 +80,15 @@ def main():
                     wg_bk.append(float(np.mean(k[:, 8] / k[:, 9])))
                 if len(l):
                     wg_bl.append(float(np.mean((l[:, 1] - l[:, 8]) / (l[:, 3] - l[:, 9]))))
+                # the boundary's split: scan end -> at the top wait (loads issued, item decoded) -> wait passed
+                sp["issue_all"].append(float(np.mean(w[:, 10] / w[:, 3])))
+                sp["wait_all"].append(float(np.mean(w[:, 11] / w[:, 3])))
+                if len(k):
+                    sp["issue_kept"].append(float(np.mean(k[:, 12] / k[:, 9])))
+                    sp["wait_kept"].append(float(np.mean(k[:, 13] / k[:, 9])))
+                if len(l):
+                    sp["issue_loaded"].append(float(np.mean((l[:, 10] - l[:, 12]) / (l[:, 3] - l[:, 9]))))
+                    sp["wait_loaded"].append(float(np.mean((l[:, 11] - l[:, 13]) / (l[:, 3] - l[:, 9]))))
             t = s[wg][s[wg][:, 7] > 0]
             if len(t):
                 tail_a.append(float(np.mean(t[:, 5])))
@@ -88,6 +99,8 @@ def main():
                      "boundary_share_b_over_c_median": med(wg_b), "boundary_share_min_max": [med([min(wg_b)]), med([max(wg_b)])] if wg_b else None,
                      "clocks_per_item_c_median": med(wg_c), "items_that_kept_x_share_median": med(wg_kept),
                      "boundary_clocks_kept_x_median": med(wg_bk), "boundary_clocks_loaded_x_median": med(wg_bl),
+                     "boundary_clocks_median": med([b * c for b, c in zip(wg_b, wg_c)]),
+                     "boundary_split_clocks_median": {k: med(v) for k, v in sp.items()},
                      "last_item_crossing_clocks_median": med(tail_a), "last_item_clocks_median": med(tail_c)}
     print(json.dumps(out))
 
